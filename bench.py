@@ -1,9 +1,15 @@
 #!/usr/bin/env python
 """bench.py -- images/s of the RANSAC-voting hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: the driver launches it under torch.distributed.run, one rank per GPU, RCCL; launched BARE with --gpus N > 1 it
      starts its N ranks itself the same way)
+
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes the keypoints of the last timed
+step to DIR/keypoints.npy (float32 [global batch, K, 2]) when --dump-outputs is given, and prints the result line.  The timed
+steps draw their hypothesis seeds from a generator reseeded at the start of the timed region, so that two runs with the same
+arguments vote on the same inputs with the same draws and their dumps can be compared output for output.  Everything else
+below (the other legs, per-kernel figures, rooflines, the CPU baseline) runs only with --full.
 
 A *step* is one ``ransac_voting_layer_v3(mask, vertex, 512, inlier_thresh=0.99)`` call through the drop-in Python API
 on a device-resident synthetic batch (free-running device RNG, exactly the call of resnet18.py:71), followed -- whenever
@@ -25,7 +31,7 @@ Workload = BASELINE config 3: 480x640, K=9, 512 hypotheses, ~2 % foreground, 64 
 Steps cycle over --rotate (default 3) distinct device-resident batches, so that neither the 256 MiB Infinity Cache nor
 the L2 holds a step's inputs from the step before.
 
-One JSON line on rank 0.  Besides the contract fields it carries
+One JSON line on rank 0: the contract fields and ``step_ms``.  With --full it also carries
   value_at_rho_0.90  the same call on fields with 9.5 % outlier pixels (the staged count's gain depends on clean fields)
   step_ms          per-step HIP events on the launch stream: median / p10 / p90 (the contract's ``ms_per_step`` is the wall
                    clock over the K steps, barrier + synchronize on both sides, max over ranks)
@@ -135,6 +141,12 @@ def main():
                          "chip needs ~60-100 steps (20-30 ms) to reach steady clocks -- tools/clock_ramp.py: 0.335 ms/step at "
                          "step 8, 0.300 at step 30, 0.279 from step 60 on -- so a 25-step run would time the ramp, not the path")
     ap.add_argument("--config", default="cfg3", help="image shape / K / hn / foreground of this BASELINE config")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run and report everything else: the two-stream, noisy-field, un_pnp / decode and "
+                         "sustained legs (N = 1), the other scaling mode and exchange variant (N > 1), the kernel durations inside "
+                         "calls, the rooflines, the CPU baseline; the --no-* options below leave parts of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the keypoints of the last timed step (rank 0: all ranks' images) to DIR/keypoints.npy, float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-two-stream", action="store_true",
                     help="N = 1: skip the two-stream extra (profiling runs: overlapped launches would blur per-kernel durations)")
@@ -161,12 +173,15 @@ def main():
                          "(clean_pvnet_amd/rccl.py: no cross-stream events); 'torch' = torch.distributed.all_gather_into_tensor (its own "
                          "stream + two events per step); 'auto' (default) = rccl when every rank could create its communicator, else torch")
     ap.add_argument("--extras", action="store_true",
-                    help="also time config 2 (B=1 latency) and v3+estimate; off by default so that a rocprofv3 "
-                         "--stats run of the default command sees the count kernel at ONE problem size")
+                    help="also time config 2 (B=1 latency) and v3+estimate (implies --full); off by default so that a rocprofv3 "
+                         "--stats run of the --full command sees the count kernel at ONE problem size")
     ap.add_argument("--cpu-sample", type=int, default=8, help="distinct images the CPU oracle cycles over")
     ap.add_argument("--backend", default=None, choices=["nccl", "gloo"],
                     help="collective backend for N > 1 (default: nccl = RCCL; gloo when the ranks outnumber the node's GPUs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    args.full = args.full or args.extras
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # a bare `python bench.py --gpus N`: start the ranks ourselves (the driver's own torchrun command keeps working)
@@ -267,6 +282,9 @@ def main():
             prewarm_done[0] = max(prewarm_done[0], n_pre)
         for i in range(warmup):
             step_fn(i)
+        # the pre-warm runs a clock-dependent number of steps: reseed, so that the timed steps draw the same hypothesis seeds
+        # in every run with the same arguments (--dump-outputs)
+        torch.manual_seed(1234 + rank)
         if use_dist:
             dist.barrier()
         torch.cuda.synchronize()
@@ -339,6 +357,51 @@ def main():
     drain()
     ms_per_step = 1e3 * elapsed / args.steps
     value = global_batch * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "keypoints.npy"), out.float().cpu().numpy())
+
+    def finish():
+        if use_dist:
+            dist.barrier()
+            torch.cuda.synchronize()
+            if comm is not None:
+                comm.destroy()
+            dist.destroy_process_group()
+
+    head = None
+    if rank == 0:
+        head = {
+            "metric": metric_name(H, W, K, hn, world, args.batch, weak), "value": round(value, 1), "unit": "images/s",
+            "value_strong": round(value, 1) if (not weak or world == 1) else None,
+            "value_weak": round(value, 1) if (weak or world == 1) else None,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
+            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "BASELINE config 3 (%s): %dx%d, K=%d, %d hypotheses, ~%.0f%% foreground, int64 mask, contiguous "
+                                   "[B,H,W,K,2] f32 vertex; global batch %d in contiguous shards of %d images per GPU; "
+                                   "ransac_voting_layer_v3 (+ one RCCL all_gather of [B,K,2] per step for N>1, see extra.exchange); steps "
+                                   "cycle over %d distinct device-resident batches"
+                                   % (args.config, H, W, K, hn, 100 * (cfg["fg"] if not isinstance(cfg["fg"], tuple) else cfg["fg"][1]),
+                                      global_batch, B, len(batches)),
+                       "batch_per_gpu": B, "global_batch": global_batch, "H": H, "W": W, "K": K, "hn": hn,
+                       "inlier_thresh": thresh,
+                       "arithmetic": "IEEE binary32, one rounding per source-level operation, NO fused multiply-add: inlier counts are "
+                                     "bit-exact against the reference's kernel compiled without contraction (oracle/_ref, tests/test_ref_pin.py); "
+                                     "nvcc's default contraction moves <= 1e-5 of the reference's own inlier decisions (libref_ransac_voting_fma.so) -- "
+                                     "unverifiable without nvcc; normal equations in binary64 (DESIGN.md 3)",
+                       "parallelism": ("x%d GPUs, %d images per GPU (weak scaling: global batch %d)" % (world, B, global_batch)) if weak
+                                      else ("batch-sharded x%d (strong scaling: %d images in total)" % (world, global_batch))},
+            "step_ms": {"median": round(pct(per_step, 0.5), 4), "p10": round(pct(per_step, 0.1), 4),
+                        "p90": round(pct(per_step, 0.9), 4), "wall": round(ms_per_step, 4),
+                        "how": "torch.cuda.Event pairs around every step on the launch stream (rank 0); wall = perf_counter over the timed region / steps, max over ranks"},
+        }
+    if not args.full:
+        if head is not None:
+            print(json.dumps(head), flush=True)
+        finish()
+        return head
+
     last = batches[(args.warmup + args.steps - 1) % len(batches)]
     # known-answer sanity of what was timed: voting recovers the keypoints the field was built from
     err = float((out[lo:hi] - last["kpt_2d"]).abs().max()) if B > 0 else 0.0
@@ -708,29 +771,10 @@ def main():
             cpu_baseline = cpu_leg(d0["mask"], d0["vertex"], tn0, hn, K, thresh, args.cpu_sample, synth, ext)
 
         result = {
-            "metric": metric_name(H, W, K, hn, world, args.batch, weak), "value": round(value, 1), "unit": "images/s",
+            **head,
             "value_strong": round(value, 1) if (not weak or world == 1) else (other or {}).get("_value"),
             "value_weak": round(value, 1) if (weak or world == 1) else (other or {}).get("_value"),
             "value_at_rho_0.90": noisy["images_per_s"] if noisy else None,
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "BASELINE config 3 (%s): %dx%d, K=%d, %d hypotheses, ~%.0f%% foreground, int64 mask, contiguous "
-                                   "[B,H,W,K,2] f32 vertex; global batch %d in contiguous shards of %d images per GPU; "
-                                   "ransac_voting_layer_v3 (+ one RCCL all_gather of [B,K,2] per step for N>1, see extra.exchange); steps "
-                                   "cycle over %d distinct device-resident batches"
-                                   % (args.config, H, W, K, hn, 100 * (cfg["fg"] if not isinstance(cfg["fg"], tuple) else cfg["fg"][1]),
-                                      global_batch, B, len(batches)),
-                       "batch_per_gpu": B, "global_batch": global_batch, "H": H, "W": W, "K": K, "hn": hn,
-                       "inlier_thresh": thresh,
-                       "arithmetic": "IEEE binary32, one rounding per source-level operation, NO fused multiply-add: inlier counts are "
-                                     "bit-exact against the reference's kernel compiled without contraction (oracle/_ref, tests/test_ref_pin.py); "
-                                     "nvcc's default contraction moves <= 1e-5 of the reference's own inlier decisions (libref_ransac_voting_fma.so) -- "
-                                     "unverifiable without nvcc; normal equations in binary64 (DESIGN.md 3)",
-                       "parallelism": ("x%d GPUs, %d images per GPU (weak scaling: global batch %d)" % (world, B, global_batch)) if weak
-                                      else ("batch-sharded x%d (strong scaling: %d images in total)" % (world, global_batch))},
-            "step_ms": {"median": round(pct(per_step, 0.5), 4), "p10": round(pct(per_step, 0.1), 4),
-                        "p90": round(pct(per_step, 0.9), 4), "wall": round(ms_per_step, 4),
-                        "how": "torch.cuda.Event pairs around every step on the launch stream (rank 0); wall = perf_counter over the timed region / steps, max over ranks"},
             # N > 1: what a SCALE record needs to be judged without reading `extra` (round 6, VERDICT r5 #2c)
             "multi_gpu": ({"ranks": world, "backend": backend, "rccl_ranks": (coll_ranks if backend == "nccl" else None),
                            "collective_ranks": coll_ranks, "shard_sizes": shard_sizes,
@@ -742,12 +786,7 @@ def main():
             "roofline_compact": roofline_compact, "roofline_valu": roofline_valu, "cpu_baseline": cpu_baseline, "extra": extra,
         }
         print(json.dumps(result), flush=True)
-    if use_dist:
-        dist.barrier()
-        torch.cuda.synchronize()
-        if comm is not None:
-            comm.destroy()
-        dist.destroy_process_group()
+    finish()
     return result
 
 

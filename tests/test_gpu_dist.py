@@ -23,7 +23,7 @@ def test_bench_under_torchrun_one_rank_executes_the_rccl_exchange(gpu):
     all_gather_into_tensor in EVERY step, barrier + max-over-ranks timing -- the N > 1 code path, one rank."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
            "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
-           "--batch", "4", "--rotate", "2", "--no-cpu-baseline"]
+           "--batch", "4", "--rotate", "2", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=_env(), timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -183,7 +183,7 @@ def test_bare_bench_gpus_2_launches_its_own_ranks(gpu):
     for k in ("WORLD_SIZE", "LOCAL_RANK", "TORCHELASTIC_RUN_ID", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--batch", "5",
-           "--rotate", "2", "--prewarm-ms", "20"]
+           "--rotate", "2", "--prewarm-ms", "20", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -200,14 +200,14 @@ def test_bare_bench_gpus_2_launches_its_own_ranks(gpu):
 
 
 def test_bare_bench_gpus_8_the_drivers_literal_command_on_one_gpu(gpu):
-    """`python bench.py --gpus 8 --steps 20 --warmup 5` -- the driver's literal N = 8 command (VERDICT r5 #2a) -- with eight ranks
+    """`python bench.py --gpus 8 --steps 20 --warmup 5` -- the driver's literal N = 8 command (VERDICT r5 #2a), plus --full for the per-rank figures -- with eight ranks
     sharing this box's one GPU: BASELINE config 3 read literally (64 images in shards of 8), every rank in the collective, the
     strong- and weak-scaling values at the top level, the multi_gpu block filled in, rc 0.  (Ranks sharing a device exchange over
     gloo -- RCCL refuses two ranks on one device; on the 8-GPU node the same lines run over RCCL.)"""
     env = _env()
     for k in ("WORLD_SIZE", "LOCAL_RANK", "TORCHELASTIC_RUN_ID", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -231,7 +231,7 @@ def test_bench_one_rank_rccl_group_survives_an_injected_communicator_fault(gpu, 
     communicator is given up, the step's exchange goes through torch.distributed's collective, the line says why, rc 0."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
            "--master-port", str(29537 + ["load", "before_init", "inside_init"].index(stage)), os.path.join(ROOT, "bench.py"),
-           "--gpus", "1", "--steps", "3", "--warmup", "2", "--batch", "4", "--rotate", "2", "--no-cpu-baseline", "--no-sustained",
+           "--gpus", "1", "--steps", "3", "--warmup", "2", "--batch", "4", "--rotate", "2", "--full", "--no-cpu-baseline", "--no-sustained",
            "--no-side-legs", "--no-two-stream"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=dict(_env(), PVV_RCCL_FAULT="0:" + stage), timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -1,20 +1,19 @@
 """GPU: the HIP path against the committed golden fixtures produced by the reference's own Python glue
 (tests/golden/make_golden.py).  Tolerance: tests/tolerances.py -- 1e-4 abs + 2e-6 rel, plus the reference's OWN measured
 deviation from the exact (rational) least-squares solution of the same inlier set (its binary32 accumulation)."""
-import os
 
 import numpy as np
 import pytest
 import torch
 
+from tests import fixtures
 from tests import tolerances as tol
 
 pytestmark = pytest.mark.gpu
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def gold(name, gpu):
-    c = dict(np.load(os.path.join(GOLD, name + ".npz")))
+    c = fixtures.load(name)
     t = {k: torch.from_numpy(v).to(gpu) for k, v in c.items() if isinstance(v, np.ndarray) and v.ndim > 0}
     return c, t
 

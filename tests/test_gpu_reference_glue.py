@@ -22,11 +22,11 @@ import numpy as np
 import pytest
 import torch
 
+from tests import fixtures
 from tests import refglue
 from tests import tolerances as tol
 
 pytestmark = pytest.mark.gpu
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 torch11 = refglue.torch11_fixture()        # the torch-1.1 shims the reference's code needs: held for this module only, then restored
 
 
@@ -64,7 +64,7 @@ V3_CASES = [("v3_basic", "ransac_voting_layer_v3", "reference"), ("v3_subsample"
 def test_reference_glue_on_hip_kernels_equals_golden_and_the_fused_layer(oracle, pkg, gpu, ref, name, fn, singular):
     import clean_pvnet_amd.ransac_voting_gpu as product
     import lib.csrc.ransac_voting.ransac_voting as ext
-    c = dict(np.load(os.path.join(GOLD, name + ".npz")))
+    c = fixtures.load(name)
     hn, thresh = int(c["hn"]), float(c["thresh"])
     kw = {"max_num": int(c["max_num"])} if "max_num" in c else {}
     n_img = c["mask"].shape[0]
@@ -105,7 +105,7 @@ def test_reference_glue_on_hip_kernels_equals_golden_and_the_fused_layer(oracle,
 def test_reference_estimate_on_hip_kernels_equals_golden_and_the_fused_layer(oracle, pkg, gpu, ref, name):
     import clean_pvnet_amd.ransac_voting_gpu as product
     import lib.csrc.ransac_voting.ransac_voting as ext
-    c = dict(np.load(os.path.join(GOLD, name + ".npz")))
+    c = fixtures.load(name)
     rh, mh = int(c["round_hyp_num"]), int(c["min_hyp_num"])
     kw = {"max_num": int(c["max_num"])} if "max_num" in c else {}
     rounds = []

@@ -5,13 +5,13 @@ import os
 import numpy as np
 import pytest
 
+from tests import fixtures
 from tests import tolerances as tol
 
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def gold(name):
-    return dict(np.load(os.path.join(GOLD, name + ".npz")))
+    return fixtures.load(name)
 
 
 def _case(oracle, synth, cfg="cfg1", seed=1234, **over):

@@ -2,16 +2,15 @@
 with the oracle's two kernels underneath, which must reproduce the committed golden fixtures bit for bit (they were
 generated exactly so, from the SOURCE files, by tests/golden/make_golden.py).  The GPU counterpart
 (tests/test_gpu_reference_glue.py) runs the same code objects on top of the HIP extension."""
-import os
 import types
 
 import numpy as np
 import pytest
 import torch
 
+from tests import fixtures
 from tests import refglue
 
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 torch11 = refglue.torch11_fixture()        # the torch-1.1 shims the reference's code needs: held for this module only, then restored
 needs_pyc = pytest.mark.skipif(not refglue.available(), reason="oracle/_ref/*.pyc not built (make -C oracle _ref_py needs /root/reference)")
 
@@ -28,14 +27,14 @@ def oracle_extension(oracle):
 @needs_pyc
 def test_reference_glue_bytecode_reproduces_the_golden_fixtures_on_cpu(oracle):
     ref = refglue.load_glue(extension=oracle_extension(oracle))
-    c = dict(np.load(os.path.join(GOLD, "v3_basic.npz")))
+    c = fixtures.load("v3_basic")
     d = refglue.Draws(ref.ransac_voting, idxs=list(c["idxs"][:2]))
     ref.ransac_voting = d
     out = ref.ransac_voting_layer_v3(torch.from_numpy(c["mask"]), torch.from_numpy(c["vertex"]), int(c["hn"]),
                                      inlier_thresh=float(c["thresh"]))
     assert np.array_equal(out.numpy(), c["out"])
     assert len(d.drawn) == 2 and not d.idxs
-    c = dict(np.load(os.path.join(GOLD, "v3_subsample.npz")))
+    c = fixtures.load("v3_subsample")
     d = refglue.Draws(d.ext, idxs=list(c["idxs"]), selection=list(c["selection"]))
     ref.ransac_voting = d
     with d.patch_uniform():

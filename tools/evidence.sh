@@ -18,9 +18,9 @@ cp $(find $PWD/gpurun_out/prof_$TAG/trace -name "*kernel_stats.csv" | head -1) $
 grep "^{" $PWD/gpurun_out/prof_$TAG/bench_trace.log | tail -1 > $OUT/bench_under_rocprof.json
 du -sh $PWD/gpurun_out/prof_$TAG >> $OUT/profile.log
 rm -rf $PWD/gpurun_out/prof_$TAG
-python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
-python bench.py --no-cpu-baseline --extras --steps 50 > $OUT/bench_extras.json 2> $OUT/bench_extras.err
-python -m torch.distributed.run --nnodes=1 --nproc-per-node=1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --no-cpu-baseline > $OUT/bench_torchrun1.json 2> $OUT/bench_torchrun1.err
+python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
+python bench.py --full --no-cpu-baseline --extras --steps 50 > $OUT/bench_extras.json 2> $OUT/bench_extras.err
+python -m torch.distributed.run --nnodes=1 --nproc-per-node=1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --full --no-cpu-baseline > $OUT/bench_torchrun1.json 2> $OUT/bench_torchrun1.err
 python tools/config_bench.py --out $OUT/configs.json > $OUT/configs.log 2>&1
 bash tools/trace_rows.sh $TAG cfg2_B1 cfg3_B8_shard_of_8gpu cfg3_B64 default_path_hn128_maxnum100_B64 default_path_hn128_maxnum100_B1 cfg3_B64_decode_fused cfg2_B1_decode_fused cfg3_B64_planar_vertex > $OUT/gaps.log 2>&1
 # staged vs full count pass: the BASELINE configs, and config 3 / 5 over outlier fractions (AUTO's break-even, profiles/DESIGN_rounds_1-4.md 4.7)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Copy the judged summaries of one gpurun profiling session into profiles/ (round tag: third argument, default r02):
     python tools/refresh_profiles.py gpurun_out/prof_<tag> gpurun_out/<dir with bench_default.json, bench_extras.json, configs.json> [r02]
-The session is produced on the GPU box by tools/profile_bench.sh <tag> plus `python bench.py [--extras]`."""
+The session is produced on the GPU box by tools/profile_bench.sh <tag> plus `python bench.py --full [--extras]`."""
 import csv, glob, json, os, re, subprocess, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -72,7 +72,7 @@ old.update({"kernel": " + ".join(pass_kernels), "FETCH_SIZE_KB": fetch, "WRITE_S
             "images_per_launch": 64, "kernels": pass_kernels,
             "per_kernel_KB": {k: {"FETCH_SIZE": kb(k, "FETCH_SIZE"), "WRITE_SIZE": kb(k, "WRITE_SIZE")} for k in pass_kernels},
             "source": "%s (tools/profile_bench.sh: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE in separate passes, python "
-                      "bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-two-stream), round tag %s; 'launch' = one count "
+                      "bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-two-stream), round tag %s; 'launch' = one count "
                       "pass (the sum over the kernels listed)" % (prof, TAG)})
 json.dump(old, open(pmc_path, "w"), indent=1)
 # the two HBM-facing kernels of the front end (bench.py's roofline_scan / roofline_compact read this)
@@ -165,7 +165,7 @@ def kernel_block(summary, kern):
 
 
 call = {"workload": old.get("workload"), "round": TAG,
-        "command": "python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-two-stream --no-side-legs",
+        "command": "python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-two-stream --no-side-legs",
         "how": "separate rocprofv3 --pmc passes of that command (tools/profile_bench.sh), per launch: the mean over the launches of the "
                "bench batch; hbm_bytes = (fetch_correction x FETCH_SIZE + WRITE_SIZE) x 1024; valu_busy = SQ_ACTIVE_INST_VALU x 4 / 1024 "
                "SIMDs / (GRBM_GUI_ACTIVE / 8 XCDs); mfma_busy = SQ_VALU_MFMA_BUSY_CYCLES / 1024 SIMDs / (GRBM_GUI_ACTIVE / 8); gathers and "
