@@ -46,6 +46,31 @@ struct MaskArgs {
 
 constexpr uint32_t kTileNzMask = 0xfffu;   // tiles[] word: foreground pixels (0..2048) | weight sum (<= 2048*255) << 12
 
+// Element type of the caller's seg / vertex field (PVV_FLAG_SEG_* / PVV_FLAG_VERTEX_*; the pointers keep their float type).
+// Every kernel widens a 2-byte element to f32 as it loads it and works on f32 from there: f16 -> f32 is the hardware convert,
+// bf16 -> f32 is `bits << 16`.  Both are exact and keep order, NaN, +-inf and subnormals (the build flushes no denormals), so
+// a native read gives exactly the numbers of the caller's `.float()` copy.
+enum { kElemF32 = 0, kElemF16 = 1, kElemBF16 = 2 };
+template <int ET> struct Elem;
+template <> struct Elem<kElemF32> { typedef float raw; };
+template <> struct Elem<kElemF16> { typedef _Float16 raw; };
+template <> struct Elem<kElemBF16> { typedef uint16_t raw; };
+
+__device__ __forceinline__ float widen(float v) { return v; }
+__device__ __forceinline__ float widen(_Float16 v) { return (float)v; }
+__device__ __forceinline__ float widen(uint16_t v) { return __builtin_bit_cast(float, (uint32_t)v << 16); }
+
+// two 2-byte elements of one 4-byte word, the lower address in the low half
+template <int ET>
+__device__ __forceinline__ float2 widen_pair(uint32_t w)
+{
+    static_assert(ET != kElemF32, "2-byte elements only");
+    if constexpr (ET == kElemF16)
+        return make_float2((float)__builtin_bit_cast(_Float16, (uint16_t)w), (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16)));
+    else
+        return make_float2(__builtin_bit_cast(float, w << 16), __builtin_bit_cast(float, w & 0xffff0000u));
+}
+
 template <int ES>
 __device__ __forceinline__ uint64_t load_elem(const void *base, int64_t off)
 {
@@ -55,27 +80,30 @@ __device__ __forceinline__ uint64_t load_elem(const void *base, int64_t off)
     return ((const uint64_t *)base)[off];
 }
 
-// torch.argmax over the class axis: first maximal index, a NaN beats everything (and the first NaN wins)
+// torch.argmax over the class axis: first maximal index, a NaN beats everything (and the first NaN wins).  ST: the seg's
+// element type; the comparison runs on the widened values, which order exactly as the 2-byte ones.
+template <int ST>
 __device__ __forceinline__ int argmax_class(const MaskArgs &a, int b, int p)
 {
+    typedef typename Elem<ST>::raw raw_t;
     const int y = p / a.W;
     const int x = p - y * a.W;
-    const float *q = a.seg + (int64_t)b * a.gb + (int64_t)y * a.gh + (int64_t)x * a.gw;
-    float best = q[0];
+    const raw_t *q = (const raw_t *)a.seg + (int64_t)b * a.gb + (int64_t)y * a.gh + (int64_t)x * a.gw;
+    float best = widen(q[0]);
     int idx = 0;
     for (int c = 1; c < a.C; ++c) {
-        const float v = q[(int64_t)c * a.gc];
+        const float v = widen(q[(int64_t)c * a.gc]);
         if (v > best || (v != v && best == best)) { best = v; idx = c; }
     }
     return idx;
 }
 
 // weight of pixel p of image b: 0 = background; v3: low byte (P:125-126 sums the bytes), estimate: 1 (P:207-208).
-template <int ES>
+template <int ES, int ST>
 __device__ __forceinline__ int mask_weight(const MaskArgs &a, int b, int p)
 {
     if (a.seg) {
-        const int idx = argmax_class(a, b, p);
+        const int idx = argmax_class<ST>(a, b, p);
         if (a.mask_out) a.mask_out[(int64_t)b * a.HW + p] = idx;
         return a.mode == 0 ? (idx & 0xFF) : (idx == 1 ? 1 : 0);
     }
@@ -135,7 +163,7 @@ template <> struct RawElem<2> { typedef uint16_t type; };
 template <> struct RawElem<4> { typedef uint32_t type; };
 template <> struct RawElem<8> { typedef uint64_t type; };
 
-template <int ES, bool AHEAD, int MODE /*MaskArgs.mode, compile-time here*/>
+template <int ES, bool AHEAD, int MODE /*MaskArgs.mode, compile-time here*/, int ST = kElemF32 /*seg element type*/>
 __global__ __launch_bounds__(kBlock) void k_tile_scan(MaskArgs a, uint32_t *__restrict__ tiles,
                                                       unsigned short *__restrict__ tile_list,
                                                       float *__restrict__ tile_draw, int total_tiles)
@@ -182,7 +210,7 @@ __global__ __launch_bounds__(kBlock) void k_tile_scan(MaskArgs a, uint32_t *__re
                 const uint64_t v = (uint64_t)cur[s];               // 0 beyond the image
                 w = MODE == 0 ? (int)(v & 0xFF) : (v == 1 ? 1 : 0);
             } else if (p < a.HW) {
-                w = mask_weight<ES>(a, b, p);
+                w = mask_weight<ES, ST>(a, b, p);
             }
             m[s] = __ballot(w != 0);
             pc[s] = __popcll(m[s]);                                // (scalar)
@@ -229,29 +257,57 @@ __global__ __launch_bounds__(kBlock) void k_tile_scan(MaskArgs a, uint32_t *__re
 // WRITE_MASK: also store the int64 mask here (two 16-byte stores per 4 pixels).  The host defers that store to
 // k_mask_from_lists on a side stream whenever the tile lists stay complete (no k_tile_subsample): 8 B per pixel written
 // behind a 8 B per pixel read would double the traffic of this kernel (70 us instead of 27 at B = 64).
-// Needs: gw == 1, gh == W, H*W % 4 == 0, the planes 16-byte aligned (host: seg2_ok).
+// Needs: gw == 1, gh == W, H*W % 4 == 0, gb and gc multiples of 4, the planes aligned to 4 elements (host: make_front).
+// ST: the seg's element type.  2-byte logits are read with one 8-byte non-temporal load per 4 pixels (half the bytes of the
+// f32 scan, same pixel -> thread mapping); the four raw words are loaded under their guards (0 bits = 0.0f outside the image)
+// and widened only after all four loads are in flight, then the comparison orders exactly as in 2 bytes.
 // ---------------------------------------------------------------------------------------------
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef long long i64x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
-template <bool WRITE_MASK>
+// 4 consecutive 2-byte logits (one 8-byte word pair), widened
+template <int ST>
+__device__ __forceinline__ f32x4 widen_logits4(u32x2 w)
+{
+    const float2 lo = widen_pair<ST>(w.x), hi = widen_pair<ST>(w.y);
+    return f32x4{lo.x, lo.y, hi.x, hi.y};
+}
+
+template <bool WRITE_MASK, int ST = kElemF32>
 __global__ __launch_bounds__(kBlock) void k_tile_scan_seg2(MaskArgs a, uint32_t *__restrict__ tiles,
                                                            unsigned short *__restrict__ tile_list,
                                                            float *__restrict__ tile_draw)
 {
+    typedef typename Elem<ST>::raw raw_t;
     __shared__ int seg[8];                                         // (half, wave) counts
     const int g = blockIdx.x;
     const int b = g / a.T, t = g - b * a.T;
     const int lane = lane_id(), wave = threadIdx.x >> 6;
-    const float *p0 = a.seg + (int64_t)b * a.gb + (int64_t)t * kTile + 4 * threadIdx.x;
-    const float *p1 = p0 + a.gc;
+    const raw_t *p0 = (const raw_t *)a.seg + (int64_t)b * a.gb + (int64_t)t * kTile + 4 * threadIdx.x;
+    const raw_t *p1 = p0 + a.gc;
     constexpr int kHalf = kTile / 2;                               // 1024 pixels = 256 threads x 4
     f32x4 v0[2], v1[2];
+    if constexpr (ST == kElemF32) {
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        const bool in = t * kTile + s * kHalf + 4 * (int)threadIdx.x < a.HW;   // HW % 4 == 0: a vector is inside or outside
-        v0[s] = in ? __builtin_nontemporal_load((const f32x4 *)(p0 + s * kHalf)) : f32x4{0.f, 0.f, 0.f, 0.f};
-        v1[s] = in ? __builtin_nontemporal_load((const f32x4 *)(p1 + s * kHalf)) : f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int s = 0; s < 2; ++s) {
+            const bool in = t * kTile + s * kHalf + 4 * (int)threadIdx.x < a.HW;   // HW % 4 == 0: a vector is inside or outside
+            v0[s] = in ? __builtin_nontemporal_load((const f32x4 *)(p0 + s * kHalf)) : f32x4{0.f, 0.f, 0.f, 0.f};
+            v1[s] = in ? __builtin_nontemporal_load((const f32x4 *)(p1 + s * kHalf)) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    } else {
+        u32x2 w0[2], w1[2];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const bool in = t * kTile + s * kHalf + 4 * (int)threadIdx.x < a.HW;
+            w0[s] = in ? __builtin_nontemporal_load((const u32x2 *)(p0 + s * kHalf)) : u32x2{0u, 0u};
+            w1[s] = in ? __builtin_nontemporal_load((const u32x2 *)(p1 + s * kHalf)) : u32x2{0u, 0u};
+        }
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            v0[s] = widen_logits4<ST>(w0[s]);
+            v1[s] = widen_logits4<ST>(w1[s]);
+        }
     }
     unsigned m4[2];
     int excl[2];
@@ -436,17 +492,44 @@ __global__ __launch_bounds__(kBlock) void k_tile_subsample(MaskArgs a, uint32_t 
 }
 
 struct VertexArgs {
-    const float *vertex;
+    const float *vertex;     // elements of k_compact_hyp's VT (a 2-byte field keeps the pointer type, as in the C ABI)
     int64_t sb, sh, sw, sk, sc;
     int K;
-    int vec2;  // sc == 1 and every other stride even: (x,y) is one aligned 8-byte load
+    int vec2;  // sc == 1, every other stride even, pointer aligned to 2 elements: (x,y) is one aligned 8-byte (f32) or 4-byte
+               // (2-byte elements) load.  Otherwise -- e.g. the planar view of resnet18.py:66-68, where consecutive rows
+               // are consecutive addresses of each plane -- two scalar loads through the strides.
 };
 
-__device__ __forceinline__ float2 load_vertex(const VertexArgs &v, int b, int y, int x, int vi)
+// What load_vertex returns: the f32 pair itself, or the raw bits of a 2-byte pair -- the vec2 path's 4-byte word in .x (the
+// lower address in the low half), the scalar path's two elements in .x and .y.  The bits are not touched where they are
+// loaded, so a load under a guard needs no wait inside it; widen_vertex runs once the loads of a batch are in flight.
+template <int VT> struct VertexRaw { typedef uint2 type; };
+template <> struct VertexRaw<kElemF32> { typedef float2 type; };
+
+template <int VT>
+__device__ __forceinline__ typename VertexRaw<VT>::type load_vertex(const VertexArgs &v, int b, int y, int x, int vi)
 {
-    const float *src = v.vertex + (int64_t)b * v.sb + (int64_t)y * v.sh + (int64_t)x * v.sw + (int64_t)vi * v.sk;
-    if (v.vec2) return *(const float2 *)src;
-    return make_float2(src[0], src[v.sc]);
+    if constexpr (VT == kElemF32) {
+        const float *src = v.vertex + (int64_t)b * v.sb + (int64_t)y * v.sh + (int64_t)x * v.sw + (int64_t)vi * v.sk;
+        if (v.vec2) return *(const float2 *)src;
+        return make_float2(src[0], src[v.sc]);
+    } else {
+        const uint16_t *src = (const uint16_t *)v.vertex + (int64_t)b * v.sb + (int64_t)y * v.sh + (int64_t)x * v.sw + (int64_t)vi * v.sk;
+        if (v.vec2) return make_uint2(*(const uint32_t *)src, 0u);
+        return make_uint2(src[0], src[v.sc]);
+    }
+}
+
+template <int VT>
+__device__ __forceinline__ float2 widen_vertex(const VertexArgs &v, typename VertexRaw<VT>::type r)
+{
+    if constexpr (VT == kElemF32) {
+        return r;
+    } else {
+        typedef typename Elem<VT>::raw raw_t;
+        if (v.vec2) return widen_pair<VT>(r.x);
+        return make_float2(widen(__builtin_bit_cast(raw_t, (uint16_t)r.x)), widen(__builtin_bit_cast(raw_t, (uint16_t)r.y)));
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -498,7 +581,9 @@ __device__ __forceinline__ int select_pixel(const int *prefix, int T, const unsi
 //  * the other T blocks (compaction): pixel list of tile x - h.blocks -> rows of the image's compacted arrays:
 //    coords[b][r] = (x,y) (P:140-141) and dirs[b][vi][r] = vertex[b,y,x,vi,:] (P:142-143, planar per keypoint so that
 //    the count kernel's loads are unit-stride).
-// Dynamic LDS: T ints (the tile prefix of the hypothesis blocks).
+// Dynamic LDS: T ints (the tile prefix of the hypothesis blocks).  VT: the vertex field's element type (the only read of it;
+// coords and dirs are f32 whatever it is).
+template <int VT>
 __global__ __launch_bounds__(kBlock) void k_compact_hyp(MaskArgs a, VertexArgs v, HypArgs h,
                                                         const uint32_t *__restrict__ tiles,
                                                         const unsigned short *__restrict__ tile_list,
@@ -643,7 +728,8 @@ __global__ __launch_bounds__(kBlock) void k_compact_hyp(MaskArgs a, VertexArgs v
             }
         }
         const int y0 = p0 / a.W, x0 = p0 - y0 * a.W, y1 = p1 / a.W, x1 = p1 - y1 * a.W;
-        const float2 d0 = load_vertex(v, b, y0, x0, vi), d1 = load_vertex(v, b, y1, x1, vi);
+        const typename VertexRaw<VT>::type r0 = load_vertex<VT>(v, b, y0, x0, vi), r1 = load_vertex<VT>(v, b, y1, x1, vi);
+        const float2 d0 = widen_vertex<VT>(v, r0), d1 = widen_vertex<VT>(v, r1);
         h.hyps[o] = hypothesis_exact(d0.x, d0.y, (float)x0, (float)y0, d1.x, d1.y, (float)x1, (float)y1);
         if (h.draws_out) { h.draws_out[2 * o] = p0; h.draws_out[2 * o + 1] = p1; }
         return;
@@ -771,13 +857,16 @@ __global__ __launch_bounds__(kBlock) void k_compact_hyp(MaskArgs a, VertexArgs v
         coords[(size_t)b * a.cap + before + li] = make_float2((float)x, (float)y);
         float2 *drow = dirs + (size_t)b * v.K * a.cap + before + li;
         for (int v0 = 0; v0 < v.K; v0 += kKeys) {
-            float2 d[kKeys];
+            typename VertexRaw<VT>::type d[kKeys];
 #pragma unroll
             for (int u = 0; u < kKeys; ++u)
-                if (v0 + u < v.K) d[u] = load_vertex(v, b, y, x, v0 + u);
+                if (v0 + u < v.K) d[u] = load_vertex<VT>(v, b, y, x, v0 + u);
 #pragma unroll
             for (int u = 0; u < kKeys; ++u)
-                if (v0 + u < v.K) drow[(size_t)(v0 + u) * a.cap] = d[u];
+                if (v0 + u < v.K) {
+                    if constexpr (VT == kElemF32) drow[(size_t)(v0 + u) * a.cap] = d[u];
+                    else drow[(size_t)(v0 + u) * a.cap] = widen_vertex<VT>(v, d[u]);
+                }
         }
     }
 }

@@ -142,7 +142,12 @@ int validate(const pvv_problem *p)
     if (((long long)p->H * p->W + kTile - 1) / kTile > kMaxTiles) return fail(PVV_E_ARG, "H*W too large (more than 16000 tiles of 2048 pixels)");
     if ((long long)p->K * p->hn >= (1ll << 23)) return fail(PVV_E_ARG, "K*hn must be < 2^23");
     if (p->count_kernel < PVV_COUNT_AUTO || p->count_kernel > PVV_COUNT_STAGED_ESTIMATE) return fail(PVV_E_ARG, "unknown count_kernel");
-    if (p->flags & ~PVV_FLAG_DEVICE_RNG) return fail(PVV_E_ARG, "unknown bits in flags");
+    if (p->flags & ~(PVV_FLAG_DEVICE_RNG | PVV_FLAG_VERTEX_F16 | PVV_FLAG_VERTEX_BF16 | PVV_FLAG_SEG_F16 | PVV_FLAG_SEG_BF16))
+        return fail(PVV_E_ARG, "unknown bits in flags");
+    if ((p->flags & PVV_FLAG_VERTEX_F16) && (p->flags & PVV_FLAG_VERTEX_BF16))
+        return fail(PVV_E_ARG, "flags: PVV_FLAG_VERTEX_F16 and PVV_FLAG_VERTEX_BF16 are exclusive");
+    if ((p->flags & PVV_FLAG_SEG_F16) && (p->flags & PVV_FLAG_SEG_BF16))
+        return fail(PVV_E_ARG, "flags: PVV_FLAG_SEG_F16 and PVV_FLAG_SEG_BF16 are exclusive");
     if (p->mask_elem_size != 1 && p->mask_elem_size != 2 && p->mask_elem_size != 4 &&
         p->mask_elem_size != 8)
         return fail(PVV_E_ARG, "mask_elem_size must be 1, 2, 4 or 8");
@@ -697,7 +702,7 @@ int launch_count_any(const pvv_problem *p, const Layout &L, char *ws, hipStream_
     return PVV_OK;
 }
 
-template <int ES, int MODE>
+template <int ES, int MODE, int ST = kElemF32>
 void launch_scan(const MaskArgs &m, const Layout &L, char *ws, int B, hipStream_t st)
 {
     const long long total = (long long)L.T * B;
@@ -705,9 +710,10 @@ void launch_scan(const MaskArgs &m, const Layout &L, char *ws, int B, hipStream_
     unsigned short *lists = (unsigned short *)(ws + L.tile_list);
     float *draws = (float *)(ws + L.tile_draw);
     // the read-ahead needs a contiguous mask; a strided mask or the fused argmax keep one short-lived block per tile
-    // (their loads are not issued ahead, and a persistent block would walk its tiles one load latency at a time)
+    // (their loads are not issued ahead, and a persistent block would walk its tiles one load latency at a time); ST: the
+    // fused argmax's seg element type
     if (!(m.contig && !m.seg)) {
-        hipLaunchKernelGGL((k_tile_scan<ES, false, MODE>), dim3((unsigned)total), dim3(kBlock), 0, st, m, tiles, lists, draws, (int)total);
+        hipLaunchKernelGGL((k_tile_scan<ES, false, MODE, ST>), dim3((unsigned)total), dim3(kBlock), 0, st, m, tiles, lists, draws, (int)total);
         return;
     }
     // ONE tile per block.  Round 2 made this kernel persistent over the resident blocks (8 per CU, every block 4-5 tiles with
@@ -728,7 +734,8 @@ struct Front {
     VertexArgs v;
     HypArgs h;
     bool can_subsample;
-    bool seg2;                // two-class seg in two contiguous planes: k_tile_scan_seg2 (16-byte loads)
+    bool seg2;                // two-class seg in two contiguous planes: k_tile_scan_seg2 (4 pixels per load)
+    int vt, st;               // element types (kElem*) of the vertex field and of the seg logits: PVV_FLAG_VERTEX_* / _SEG_*
     long long *mask_deferred; // != nullptr: the scan does not write the int64 mask; k_mask_from_lists does, on the side stream
 };
 
@@ -765,9 +772,13 @@ Front make_front(const pvv_problem *p, int mode, const void *d_mask, const float
     const long long max_weight = mode == 1 ? 1 : (d_seg ? (p->seg_classes > 1 ? p->seg_classes - 1 : 1) : 255);
     f.can_subsample = (long long)p->max_num < max_weight * (long long)p->H * p->W;
     m.want_draws = (f.can_subsample && !m.fuse_sub) ? 1 : 0;     // fused subsampling evaluates its draws on demand (compaction.hpp)
-    // decode_keypoint's real layout (resnet18.py:69,93): a two-class seg in two contiguous float32 planes
+    f.vt = (p->flags & PVV_FLAG_VERTEX_F16) ? kElemF16 : (p->flags & PVV_FLAG_VERTEX_BF16) ? kElemBF16 : kElemF32;
+    f.st = (p->flags & PVV_FLAG_SEG_F16) ? kElemF16 : (p->flags & PVV_FLAG_SEG_BF16) ? kElemBF16 : kElemF32;
+    const int seg_es = f.st == kElemF32 ? 4 : 2, vertex_es = f.vt == kElemF32 ? 4 : 2;
+    // decode_keypoint's real layout (resnet18.py:69,93): a two-class seg in two contiguous planes, every 4 pixels one aligned
+    // load (16 bytes of f32, 8 of f16 / bf16)
     f.seg2 = d_seg && p->seg_classes == 2 && m.gw == 1 && m.gh == p->W && (((long long)p->H * p->W) & 3) == 0 && (m.gb & 3) == 0 &&
-             (m.gc & 3) == 0 && ((uintptr_t)d_seg & 15) == 0;
+             (m.gc & 3) == 0 && ((uintptr_t)d_seg % (4 * seg_es)) == 0;
     // ... whose int64 mask (8 B per pixel, as much as the scan reads) can be written from the tile lists beside the rest of
     // the call instead of by the scan, when the lists stay complete (k_tile_subsample would rewrite them) and the batch is
     // large enough for the two cross-stream events to pay (measured: B = 64 480x640, scan 70.5 -> ~27 us)
@@ -781,7 +792,7 @@ Front make_front(const pvv_problem *p, int mode, const void *d_mask, const float
     v.sk = p->vertex_stride[3]; v.sc = p->vertex_stride[4];
     v.K = p->K;
     v.vec2 = (v.sc == 1 && !(v.sb & 1) && !(v.sh & 1) && !(v.sw & 1) && !(v.sk & 1) &&
-              ((uintptr_t)d_vertex % 8 == 0)) ? 1 : 0;
+              ((uintptr_t)d_vertex % (2 * vertex_es) == 0)) ? 1 : 0;
     HypArgs &h = f.h;
     h.idxs = d_idxs; h.idxs2 = d_idxs2;
     h.hn = p->hn; h.hn_first = hn_first < 0 ? p->hn : hn_first;
@@ -805,9 +816,22 @@ int run_scan(const pvv_problem *p, const Front &f, char *ws, const Layout &L, hi
         uint32_t *tiles = (uint32_t *)(ws + L.tiles);
         unsigned short *lists = (unsigned short *)(ws + L.tile_list);
         float *draws = (float *)(ws + L.tile_draw);
-        if (write_mask) hipLaunchKernelGGL(k_tile_scan_seg2<true>, dim3(total), dim3(kBlock), 0, st, m, tiles, lists, draws);
-        else hipLaunchKernelGGL(k_tile_scan_seg2<false>, dim3(total), dim3(kBlock), 0, st, m, tiles, lists, draws);
+        auto go2 = [&](auto et) {
+            constexpr int ST = decltype(et)::value;
+            if (write_mask) hipLaunchKernelGGL((k_tile_scan_seg2<true, ST>), dim3(total), dim3(kBlock), 0, st, m, tiles, lists, draws);
+            else hipLaunchKernelGGL((k_tile_scan_seg2<false, ST>), dim3(total), dim3(kBlock), 0, st, m, tiles, lists, draws);
+        };
+        if (f.st == kElemF16) go2(std::integral_constant<int, kElemF16>{});
+        else if (f.st == kElemBF16) go2(std::integral_constant<int, kElemBF16>{});
+        else go2(std::integral_constant<int, kElemF32>{});
         return check_launch("k_tile_scan_seg2");
+    }
+    if (f.m.seg && f.st != kElemF32) {
+        // 2-byte logits, generic layout: the argmax reads seg only (never the mask) and only the decode calls (mode 0) pass
+        // one, so one instantiation per element type
+        if (f.st == kElemF16) launch_scan<8, 0, kElemF16>(f.m, L, ws, p->B, st);
+        else launch_scan<8, 0, kElemBF16>(f.m, L, ws, p->B, st);
+        return check_launch("k_tile_scan");
     }
     // (the mask's interpretation -- low byte for v3, == 1 for the estimate -- is a template parameter of the scan)
     auto go = [&](auto es) {
@@ -942,10 +966,16 @@ int run_front(const pvv_problem *p, int mode, const void *d_mask, const float *d
         if (int e = check_launch("k_tile_subsample")) return e;
     }
     if (int e = mark(p, PVV_MARK_SCAN, st)) return e;
-    hipLaunchKernelGGL(k_compact_hyp, dim3(L.T + f.h.blocks, p->B), dim3(kBlock), sizeof(int) * (size_t)L.T, st, f.m, f.v,
-                       f.h, (const uint32_t *)(ws + L.tiles), (const unsigned short *)(ws + L.tile_list),
-                       (const float *)(ws + L.tile_draw), (int *)(ws + L.tn), (float2 *)(ws + L.coords),
-                       (float2 *)(ws + L.dirs));
+    auto compact = [&](auto et) {
+        constexpr int VT = decltype(et)::value;
+        hipLaunchKernelGGL(k_compact_hyp<VT>, dim3(L.T + f.h.blocks, p->B), dim3(kBlock), sizeof(int) * (size_t)L.T, st, f.m, f.v,
+                           f.h, (const uint32_t *)(ws + L.tiles), (const unsigned short *)(ws + L.tile_list),
+                           (const float *)(ws + L.tile_draw), (int *)(ws + L.tn), (float2 *)(ws + L.coords),
+                           (float2 *)(ws + L.dirs));
+    };
+    if (f.vt == kElemF16) compact(std::integral_constant<int, kElemF16>{});
+    else if (f.vt == kElemBF16) compact(std::integral_constant<int, kElemBF16>{});
+    else compact(std::integral_constant<int, kElemF32>{});
     if (int e = check_launch("k_compact_hyp")) return e;
     if (int e = mark(p, PVV_MARK_COMPACT, st)) return e;
     if (defer_mask) {

@@ -169,13 +169,33 @@ int mask_elem_size(const at::Tensor &mask)
     }
 }
 
+// The flag bit of a 2-byte field (PVV_FLAG_VERTEX_* / PVV_FLAG_SEG_*): the kernels read float16 / bfloat16 as they are and
+// widen each element exactly, so the outputs equal the call on the float32 copy -- which is never made.
+int32_t half_flag(const at::Tensor &t, const char *name, int32_t f16, int32_t bf16)
+{
+    switch (t.scalar_type()) {
+    case at::kFloat: return 0;
+    case at::kHalf: return f16;
+    case at::kBFloat16: return bf16;
+    default: TORCH_CHECK(false, name, " must be float32, float16 or bfloat16, got ", t.scalar_type());
+    }
+}
+
+// data pointer of a float32 / float16 / bfloat16 field as the C ABI takes it (the flag bits say what it points to)
+const float *field_ptr(const at::Tensor &t) { return (const float *)t.data_ptr(); }
+
+int32_t seg_flag(const at::Tensor &seg) { return half_flag(seg, "seg", PVV_FLAG_SEG_F16, PVV_FLAG_SEG_BF16); }
+
+// float32 outputs on the field's device, whatever the field's dtype
+at::TensorOptions f32_like(const at::Tensor &t) { return t.options().dtype(at::kFloat); }
+
 pvv_problem make_problem(const at::Tensor &mask, const at::Tensor &vertex, int64_t hn, double thresh,
                          int64_t min_num, int64_t max_num, int64_t policy, int64_t seed)
 {
     TORCH_CHECK(mask.is_cuda(), "mask must be a CUDA tensor");
     TORCH_CHECK(vertex.is_cuda(), "vertex must be a CUDA tensor");
     same_device(mask, vertex, "vertex");
-    TORCH_CHECK(vertex.scalar_type() == at::kFloat, "vertex must be float32, got ", vertex.scalar_type());
+    const int32_t vflag = half_flag(vertex, "vertex", PVV_FLAG_VERTEX_F16, PVV_FLAG_VERTEX_BF16);
     TORCH_CHECK(vertex.dim() == 5 && vertex.size(4) == 2, "vertex must be [b,h,w,vn,2]");
     TORCH_CHECK(mask.dim() == 3 && mask.size(0) == vertex.size(0) && mask.size(1) == vertex.size(1) &&
                     mask.size(2) == vertex.size(2),
@@ -197,6 +217,7 @@ pvv_problem make_problem(const at::Tensor &mask, const at::Tensor &vertex, int64
     for (int i = 0; i < 3; ++i) p.mask_stride[i] = mask.stride(i);
     for (int i = 0; i < 5; ++i) p.vertex_stride[i] = vertex.stride(i);
     p.seed = (uint64_t)seed;
+    p.flags = vflag;
     return p;
 }
 
@@ -242,7 +263,7 @@ void promise_device_rng(pvv_problem &p, const std::optional<at::Tensor> &idxs, c
 // (clean_pvnet_amd.dist.GatherBuffer), so that the exchange needs no copy -- instead of a fresh tensor
 at::Tensor result_buffer(const std::optional<at::Tensor> &out, const pvv_problem &p, const at::Tensor &vertex)
 {
-    if (!out.has_value()) return at::empty({p.B, p.K, 2}, vertex.options());
+    if (!out.has_value()) return at::empty({p.B, p.K, 2}, f32_like(vertex));
     check_dev(*out, "out", at::kFloat);
     same_device(vertex, *out, "out");
     TORCH_CHECK(out->dim() == 3 && out->size(0) == p.B && out->size(1) == p.K && out->size(2) == 2, "out must be [b,vn,2] = [", p.B, ",", p.K, ",2]");
@@ -286,7 +307,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> ransac_voting_v3(
     auto out = result_buffer(out_buf, p, vertex);
     auto win = at::empty({p.B, p.K}, vertex.options().dtype(at::kInt));
     auto tn = at::empty({p.B}, vertex.options().dtype(at::kInt));
-    ok(pvv_ransac_voting_v3(&p, mask.data_ptr(), vertex.data_ptr<float>(), ip, sp, ws.data_ptr(),
+    ok(pvv_ransac_voting_v3(&p, mask.data_ptr(), field_ptr(vertex), ip, sp, ws.data_ptr(),
                             (size_t)ws.numel(), out.data_ptr<float>(), win.data_ptr<int32_t>(),
                             tn.data_ptr<int32_t>(), cur_stream(vertex)),
        "ransac_voting_v3");
@@ -302,7 +323,6 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> decode_keypoint_v3(
 {
     const c10::DeviceGuard device_guard(vertex.device());   // launch on the tensors' GPU, whatever the current device is
     TORCH_CHECK(seg.is_cuda(), "seg must be a CUDA tensor");
-    TORCH_CHECK(seg.scalar_type() == at::kFloat, "seg must be float32, got ", seg.scalar_type());
     TORCH_CHECK(seg.dim() == 4 && vertex.dim() == 5 && seg.size(0) == vertex.size(0) && seg.size(2) == vertex.size(1) &&
                     seg.size(3) == vertex.size(2),
                 "seg must be [b,c,h,w] matching vertex [b,h,w,vn,2]");
@@ -312,15 +332,16 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> decode_keypoint_v3(
     p.count_kernel = (int32_t)count_kernel;
     p.seg_classes = (int32_t)seg.size(1);
     for (int i = 0; i < 4; ++i) p.seg_stride[i] = seg.stride(i);
+    p.flags |= seg_flag(seg);
     cap_for_selection(selection, p);
     const int32_t *ip = opt_idxs(idxs, vertex, p);
     const float *sp = opt_selection(selection, vertex, p);
     promise_device_rng(p, idxs, std::nullopt, selection);
     at::Tensor ws = make_workspace(p, vertex);
-    auto out = at::empty({p.B, p.K, 2}, vertex.options());
+    auto out = at::empty({p.B, p.K, 2}, f32_like(vertex));
     auto win = at::empty({p.B, p.K}, vertex.options().dtype(at::kInt));
     auto tn = at::empty({p.B}, vertex.options().dtype(at::kInt));
-    ok(pvv_decode_keypoint_v3(&p, seg.data_ptr<float>(), vertex.data_ptr<float>(), ip, sp, ws.data_ptr(),
+    ok(pvv_decode_keypoint_v3(&p, field_ptr(seg), field_ptr(vertex), ip, sp, ws.data_ptr(),
                               (size_t)ws.numel(), mask.data_ptr<int64_t>(), out.data_ptr<float>(),
                               win.data_ptr<int32_t>(), tn.data_ptr<int32_t>(), cur_stream(vertex)),
        "decode_keypoint_v3");
@@ -337,7 +358,6 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tenso
 {
     const c10::DeviceGuard device_guard(vertex.device());
     TORCH_CHECK(seg.is_cuda(), "seg must be a CUDA tensor");
-    TORCH_CHECK(seg.scalar_type() == at::kFloat, "seg must be float32, got ", seg.scalar_type());
     TORCH_CHECK(seg.dim() == 4 && vertex.dim() == 5 && seg.size(0) == vertex.size(0) && seg.size(2) == vertex.size(1) &&
                     seg.size(3) == vertex.size(2),
                 "seg must be [b,c,h,w] matching vertex [b,h,w,vn,2]");
@@ -348,6 +368,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tenso
     p.count_kernel = (int32_t)count_kernel;
     p.seg_classes = (int32_t)seg.size(1);
     for (int i = 0; i < 4; ++i) p.seg_stride[i] = seg.stride(i);
+    p.flags |= seg_flag(seg);
     cap_for_selection(selection, p);
     const int32_t *ip = opt_idxs(idxs, vertex, p);
     pvv_problem pe = p;
@@ -358,12 +379,12 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tenso
     const size_t n = pvv_workspace_bytes_un_pnp(&p, (int32_t)hyp_est);
     TORCH_CHECK(n > 0, "invalid voting problem: ", pvv_last_error());
     at::Tensor ws = at::empty({(int64_t)n}, vertex.options().dtype(at::kByte));
-    auto kpt = at::empty({p.B, p.K, 2}, vertex.options());
-    auto cov = at::empty({p.B, p.K, 2, 2}, vertex.options());
-    auto weights = at::empty({p.B, p.K, 3}, vertex.options());
+    auto kpt = at::empty({p.B, p.K, 2}, f32_like(vertex));
+    auto cov = at::empty({p.B, p.K, 2, 2}, f32_like(vertex));
+    auto weights = at::empty({p.B, p.K, 3}, f32_like(vertex));
     auto win = at::empty({p.B, p.K}, vertex.options().dtype(at::kInt));
     auto tn = at::empty({p.B}, vertex.options().dtype(at::kInt));
-    ok(pvv_decode_keypoint_un_pnp(&p, (int32_t)hyp_est, seg.data_ptr<float>(), vertex.data_ptr<float>(), ip, ie, sp,
+    ok(pvv_decode_keypoint_un_pnp(&p, (int32_t)hyp_est, field_ptr(seg), field_ptr(vertex), ip, ie, sp,
                                   ws.data_ptr(), n, mask.data_ptr<int64_t>(), kpt.data_ptr<float>(), cov.data_ptr<float>(),
                                   weights.data_ptr<float>(), win.data_ptr<int32_t>(), tn.data_ptr<int32_t>(),
                                   cur_stream(vertex)),
@@ -391,18 +412,18 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> estimate_
     const float *sp = opt_selection(selection, vertex, p);
     promise_device_rng(p, idxs, std::nullopt, selection);
     at::Tensor ws = make_workspace(p, vertex);
-    auto cov = at::empty({p.B, p.K, 2, 2}, vertex.options());
+    auto cov = at::empty({p.B, p.K, 2, 2}, f32_like(vertex));
     auto tn = at::empty({p.B}, vertex.options().dtype(at::kInt));
     at::Tensor hyp, counts;
     if (want_hyp) {
-        hyp = at::empty({p.B, p.K, p.hn, 2}, vertex.options());
+        hyp = at::empty({p.B, p.K, p.hn, 2}, f32_like(vertex));
         counts = at::empty({p.B, p.K, p.hn}, vertex.options().dtype(at::kInt));
     } else {
-        hyp = at::empty({0}, vertex.options());
+        hyp = at::empty({0}, f32_like(vertex));
         counts = at::empty({0}, vertex.options().dtype(at::kInt));
     }
-    auto weights = at::empty({p.B, p.K, 3}, vertex.options());
-    ok(pvv_estimate_voting_distribution(&p, mask.data_ptr(), vertex.data_ptr<float>(), ip, sp,
+    auto weights = at::empty({p.B, p.K, 3}, f32_like(vertex));
+    ok(pvv_estimate_voting_distribution(&p, mask.data_ptr(), field_ptr(vertex), ip, sp,
                                         mean.data_ptr<float>(), ws.data_ptr(), (size_t)ws.numel(),
                                         cov.data_ptr<float>(), want_hyp ? hyp.data_ptr<float>() : nullptr,
                                         want_hyp ? counts.data_ptr<int32_t>() : nullptr,
@@ -431,8 +452,8 @@ std::vector<double> count_kernel_ms_in_pipeline(std::vector<at::Tensor> masks, s
         p.ev_count_end = (void *)ev[2 * r + 1];
         p.flags |= PVV_FLAG_DEVICE_RNG;
         at::Tensor ws = make_workspace(p, vertex);
-        auto out = at::empty({p.B, p.K, 2}, vertex.options());
-        ok(pvv_ransac_voting_v3(&p, mask.data_ptr(), vertex.data_ptr<float>(), nullptr, nullptr, ws.data_ptr(),
+        auto out = at::empty({p.B, p.K, 2}, f32_like(vertex));
+        ok(pvv_ransac_voting_v3(&p, mask.data_ptr(), field_ptr(vertex), nullptr, nullptr, ws.data_ptr(),
                                 (size_t)ws.numel(), out.data_ptr<float>(), nullptr, nullptr, cur_stream(vertex)),
            "ransac_voting_v3");
         keep.push_back(ws);
@@ -461,7 +482,7 @@ std::vector<std::vector<double>> stage_ms_in_pipeline(std::vector<at::Tensor> ma
     // means (optional, with estimate: one [b,vn,2] float32 tensor per vertex field): the keypoints the estimate is taken about --
     // its staged pass orders the chunks by them; empty: zeros (row-major order, the timing of rounds 2-4)
     TORCH_CHECK(means.empty() || (estimate && means.size() == vertices.size()), "means: one per vertex field, estimate only");
-    // segs (optional, one [b,c,h,w] float32 tensor per vertex field): time pvv_decode_keypoint_v3 -- the class argmax fused
+    // segs (optional, one [b,c,h,w] float32 / float16 / bfloat16 tensor per vertex field): time pvv_decode_keypoint_v3 -- the class argmax fused
     // into the mask scan, the int64 mask written out -- instead of pvv_ransac_voting_v3; `masks` may then be empty
     const bool fused = !segs.empty();
     TORCH_CHECK(!vertices.empty() && (fused ? segs.size() == vertices.size() : masks.size() == vertices.size()),
@@ -476,8 +497,9 @@ std::vector<std::vector<double>> stage_ms_in_pipeline(std::vector<at::Tensor> ma
         at::Tensor mask;
         if (fused) {
             const at::Tensor &seg = segs[r % segs.size()];
-            TORCH_CHECK(seg.is_cuda() && seg.scalar_type() == at::kFloat && seg.dim() == 4 && seg.size(0) == vertex.size(0) &&
-                            seg.size(2) == vertex.size(1) && seg.size(3) == vertex.size(2), "seg must be float32 [b,c,h,w] matching vertex");
+            seg_flag(seg);
+            TORCH_CHECK(seg.is_cuda() && seg.dim() == 4 && seg.size(0) == vertex.size(0) && seg.size(2) == vertex.size(1) &&
+                            seg.size(3) == vertex.size(2), "seg must be a float32 / float16 / bfloat16 [b,c,h,w] matching vertex");
             mask = at::empty({seg.size(0), seg.size(2), seg.size(3)}, seg.options().dtype(at::kLong));
         } else {
             mask = masks[r % masks.size()];
@@ -489,6 +511,7 @@ std::vector<std::vector<double>> stage_ms_in_pipeline(std::vector<at::Tensor> ma
             const at::Tensor &seg = segs[r % segs.size()];
             p.seg_classes = (int32_t)seg.size(1);
             for (int i = 0; i < 4; ++i) p.seg_stride[i] = seg.stride(i);
+            p.flags |= seg_flag(seg);
         }
         std::vector<void *> marks(PVV_N_MARKS);
         for (int i = 0; i < PVV_N_MARKS; ++i) marks[(size_t)i] = (void *)ev[(size_t)PVV_N_MARKS * (size_t)r + (size_t)i];
@@ -497,7 +520,7 @@ std::vector<std::vector<double>> stage_ms_in_pipeline(std::vector<at::Tensor> ma
         p.ev_marks = marks.data();
         p.flags |= PVV_FLAG_DEVICE_RNG;
         at::Tensor ws = make_workspace(p, vertex);
-        auto out = at::empty({p.B, p.K, 2}, vertex.options());
+        auto out = at::empty({p.B, p.K, 2}, f32_like(vertex));
         if (estimate) {      // estimate_voting_distribution_with_mean with round_hyp_num hypotheses in total (mean = zeros: timing only)
             if (means.empty()) out.zero_();
             else {
@@ -506,20 +529,20 @@ std::vector<std::vector<double>> stage_ms_in_pipeline(std::vector<at::Tensor> ma
                 TORCH_CHECK(mn.dim() == 3 && mn.size(0) == p.B && mn.size(1) == p.K && mn.size(2) == 2, "mean must be [b,vn,2]");
                 out.copy_(mn);
             }
-            auto cov = at::empty({p.B, p.K, 2, 2}, vertex.options());
-            ok(pvv_estimate_voting_distribution(&p, mask.data_ptr(), vertex.data_ptr<float>(), nullptr, nullptr, out.data_ptr<float>(),
+            auto cov = at::empty({p.B, p.K, 2, 2}, f32_like(vertex));
+            ok(pvv_estimate_voting_distribution(&p, mask.data_ptr(), field_ptr(vertex), nullptr, nullptr, out.data_ptr<float>(),
                                                 ws.data_ptr(), (size_t)ws.numel(), cov.data_ptr<float>(), nullptr, nullptr, nullptr,
                                                 nullptr, cur_stream(vertex)),
                "estimate_voting_distribution");
             keep.push_back(cov);
         } else if (fused) {
-            ok(pvv_decode_keypoint_v3(&p, segs[r % segs.size()].data_ptr<float>(), vertex.data_ptr<float>(), nullptr, nullptr, ws.data_ptr(),
+            ok(pvv_decode_keypoint_v3(&p, field_ptr(segs[r % segs.size()]), field_ptr(vertex), nullptr, nullptr, ws.data_ptr(),
                                       (size_t)ws.numel(), mask.data_ptr<int64_t>(), out.data_ptr<float>(), nullptr, nullptr,
                                       cur_stream(vertex)),
                "decode_keypoint_v3");
             keep.push_back(mask);
         } else {
-            ok(pvv_ransac_voting_v3(&p, mask.data_ptr(), vertex.data_ptr<float>(), nullptr, nullptr, ws.data_ptr(),
+            ok(pvv_ransac_voting_v3(&p, mask.data_ptr(), field_ptr(vertex), nullptr, nullptr, ws.data_ptr(),
                                     (size_t)ws.numel(), out.data_ptr<float>(), nullptr, nullptr, cur_stream(vertex)),
                "ransac_voting_v3");
         }

@@ -19,8 +19,11 @@ def decode_keypoint(output, un_pnp=False, *, idxs=None, selection=None, singular
     """In-place update of ``output`` exactly like the reference method: adds ``mask`` [b,h,w] int64, ``kpt_2d``
     [b,vn,2] and -- with ``un_pnp`` (``cfg.test.un_pnp``, config.py:75) -- ``var`` [b,vn,2,2].
 
-    ``output['seg']`` is [b,c,h,w] float32 logits, ``output['vertex']`` [b,2*vn,h,w] float32; both may be channel
-    slices of one network output tensor (resnet18.py:93-94), no copy is made.
+    ``output['seg']`` is [b,c,h,w] logits, ``output['vertex']`` [b,2*vn,h,w]; both may be channel slices of one network
+    output tensor (resnet18.py:93-94), no copy is made.  Each may be float32, float16 or bfloat16 (a network run under
+    ``torch.autocast`` or in half precision), independently: the kernels widen every element as they read it, which is
+    exact, so every output is bit-identical to the call on ``.float()`` copies -- and stays float32 (``mask`` int64).
+    A seg of any other dtype is converted with ``.float()``.
 
     ``un_pnp`` with a two-class ``seg`` (PVNet's) runs ``ransac_voting_layer_v3`` and
     ``estimate_voting_distribution_with_mean`` (resnet18.py:71-72) as ONE call -- one mask scan, one compaction, one
@@ -42,7 +45,7 @@ def decode_keypoint(output, un_pnp=False, *, idxs=None, selection=None, singular
     b, vn_2, h, w = ver.shape
     vertex = ver.permute(0, 2, 3, 1).view(b, h, w, vn_2 // 2, 2)              # resnet18.py:66-68, a strided view
     seed = _next_seed() if seed is None else int(seed)
-    segf = seg.float()
+    segf = seg if seg.dtype in (torch.float32, torch.float16, torch.bfloat16) else seg.float()
     fused = un_pnp and seg.shape[1] == 2
     if un_pnp:
         hn, max_num = 512, 30000                                             # resnet18.py:71
@@ -72,8 +75,9 @@ def decode_keypoint(output, un_pnp=False, *, idxs=None, selection=None, singular
             if t is not None:
                 parts[k].append(t)
     if b == 0:
-        parts = {"mask": [seg.new_zeros((0, h, w), dtype=torch.int64)], "kpt_2d": [ver.new_zeros((0, vn_2 // 2, 2))],
-                 "var": [ver.new_zeros((0, vn_2 // 2, 2, 2))], "var_weights": [ver.new_zeros((0, vn_2 // 2, 3))]}
+        f32 = torch.float32
+        parts = {"mask": [seg.new_zeros((0, h, w), dtype=torch.int64)], "kpt_2d": [ver.new_zeros((0, vn_2 // 2, 2), dtype=f32)],
+                 "var": [ver.new_zeros((0, vn_2 // 2, 2, 2), dtype=f32)], "var_weights": [ver.new_zeros((0, vn_2 // 2, 3), dtype=f32)]}
     cat = lambda ts: ts[0] if len(ts) == 1 else torch.cat(ts)                 # noqa: E731
     output.update({"mask": cat(parts["mask"]), "kpt_2d": cat(parts["kpt_2d"])})
     if un_pnp:

@@ -120,8 +120,9 @@ def sharded_vote(vote_fn, mask_local, vertex_local, batch, *args, group=None, se
         kwargs = dict(kwargs, seed=int(seed), first_image=shard_bounds(batch, world, rank)[0])
     if vertex_local.shape[0] == 0:
         # a trailing rank of an uneven split (batch=9 on 8 GPUs leaves ranks 5-7 without an image) still has to enter
-        # the collective: zero rows of the layer's result shape, no launch
-        local = vertex_local.new_zeros((0, vertex_local.shape[3], 2))
+        # the collective: zero rows of the layer's result shape and dtype (float32 whatever the vertex dtype, as on the
+        # ranks that vote: a bf16 / f16 field must not make the empty ranks' byte counts differ), no launch
+        local = vertex_local.new_zeros((0, vertex_local.shape[3], 2), dtype=torch.float32)
     else:
         local = vote_fn(mask_local, vertex_local, *args, **kwargs)
     return gather_results(local, batch, group)

@@ -7,6 +7,10 @@ differs is how the work is done: the reference loops over the batch in Python wi
 torch launches and >=3 host syncs per image; here one call launches a fixed sequence of
 HIP kernels for the whole batch on the current stream and never reads anything back.
 
+``vertex`` may be float32, float16 or bfloat16 (the fields of a network run under ``torch.autocast`` or in half
+precision): the kernels widen every element as they read it, which is exact, so every output is bit-identical to the
+same call on ``vertex.float()`` -- no copy is made -- and stays float32.  Other dtypes (float64 included) are refused.
+
 Keyword-only additions (all default to reference behaviour):
   idxs       injected hypothesis index pairs ``[b,hn,vn,2]`` int32 (the ``random_`` draws of
              :145 / :235); None = counter-based RNG on the device
@@ -60,7 +64,7 @@ def _vote_v3(mask, vertex, round_hyp_num, inlier_thresh, min_num, max_num, idxs,
              first_image=0, out=None):
     b = vertex.shape[0]
     if b == 0:                      # an empty shard (dist.sharded_vote on a trailing rank): nothing to launch
-        return vertex.new_zeros((0, vertex.shape[3], 2)) if out is None else out
+        return vertex.new_zeros((0, vertex.shape[3], 2), dtype=torch.float32) if out is None else out
     if out is not None and tuple(out.shape) != (b, vertex.shape[3], 2):
         raise ValueError("out must be [b,vn,2] = %r, got %r" % ((b, vertex.shape[3], 2), tuple(out.shape)))
     mask = _as_mask(mask, False)
@@ -155,11 +159,12 @@ def estimate_voting_distribution_with_mean(mask, vertex, mean, round_hyp_num=256
     del topk
     b = vertex.shape[0]
     if b == 0:
-        empty = (mean, vertex.new_zeros((0, vertex.shape[3], 2, 2)))
+        f32 = torch.float32
+        empty = (mean, vertex.new_zeros((0, vertex.shape[3], 2, 2), dtype=f32))
         if output_hyp:
             hn0 = int(np.ceil(min_hyp_num / round_hyp_num)) * int(round_hyp_num)
-            empty += (vertex.new_zeros((0, vertex.shape[3], hn0, 2)), vertex.new_zeros((0, vertex.shape[3], hn0)))
-        return empty + ((vertex.new_zeros((0, vertex.shape[3], 3)),) if return_weights else ())
+            empty += (vertex.new_zeros((0, vertex.shape[3], hn0, 2), dtype=f32), vertex.new_zeros((0, vertex.shape[3], hn0), dtype=f32))
+        return empty + ((vertex.new_zeros((0, vertex.shape[3], 3), dtype=f32),) if return_weights else ())
     hn_total = int(np.ceil(min_hyp_num / round_hyp_num)) * int(round_hyp_num)
     mask = _as_mask(mask, True)
     mean_c = mean.contiguous().float()

@@ -149,6 +149,17 @@ typedef struct pvv_problem {
                                     kernel and evaluate draws on demand), and pvv_workspace_bytes() leaves the 4 B x H x W per
                                     image of draw storage out: -27 % at 480x640, B = 64.  A call that sets the flag and
                                     passes one of those pointers fails with PVV_E_ARG */
+/* 2-byte input fields (ABI v8, additive).  With a vertex bit, d_vertex points to [B,H,W,K,2] float16 / bfloat16 elements
+ * (it keeps its `const float *` type: cast), vertex_stride stays in ELEMENTS; the seg bits say the same of d_seg and are
+ * read by pvv_decode_keypoint_v3 and pvv_decode_keypoint_un_pnp only.  The kernels widen each element to float32 as they
+ * load it -- exact, order-, NaN-, inf- and subnormal-preserving -- so every output is bit-identical to the same call on the
+ * float32 copy of the field, and stays float32; nothing is copied and the workspace is the same size.  Setting both bits of
+ * one pair fails with PVV_E_ARG.  A library that predates these bits rejects them ("unknown bits in flags" from
+ * pvv_workspace_bytes): the feature test for C hosts. */
+#define PVV_FLAG_VERTEX_F16 2
+#define PVV_FLAG_VERTEX_BF16 4
+#define PVV_FLAG_SEG_F16 8
+#define PVV_FLAG_SEG_BF16 16
 
 /* pvv_problem.d_status bits */
 #define PVV_STATUS_SKIPPED 1     /* foreground_num < min_num: the image's keypoints are zeros (P:129-132 / P:211-216) */
@@ -225,7 +236,7 @@ size_t pvv_workspace_bytes(const pvv_problem *p);
 
 /* ransac_voting_layer_v3 (P:112-199).
  *   d_mask      [B,H,W] integer/bool mask, foreground = low byte != 0 (P:125)
- *   d_vertex    [B,H,W,K,2] f32 through p->vertex_stride
+ *   d_vertex    [B,H,W,K,2] f32 through p->vertex_stride (f16 / bf16 with PVV_FLAG_VERTEX_F16 / _BF16)
  *   d_idxs      [B,hn,K,2] i32 injected index pairs of P:145, or NULL (device RNG)
  *   d_selection [B,H,W] f32 injected U(0,1) draws of P:136, or NULL (device RNG)
  *   d_out       [B,K,2] f32 keypoint means
@@ -243,7 +254,7 @@ int pvv_ransac_voting_v3(const pvv_problem *p, const void *d_mask,
  * argmax fused into the mask scan: mask = argmax(seg, 1) (first maximum; a NaN
  * logit wins, as torch.argmax) is computed while the foreground is counted, so
  * the int64 mask is written once and never read back.
- *   d_seg       [B,C,H,W] f32 class logits through p->seg_stride
+ *   d_seg       [B,C,H,W] f32 class logits through p->seg_stride (f16 / bf16 with PVV_FLAG_SEG_F16 / _BF16)
  *   d_mask_out  [B,H,W] i64, contiguous: the `mask` entry of the output dict
  *               (resnet18.py:72,76); may be NULL when the caller does not need it
  * everything else as pvv_ransac_voting_v3 (foreground = class != 0). */
