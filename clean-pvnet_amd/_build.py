@@ -4,6 +4,7 @@
   ransac_voting.so   pybind11/torch shim over that C ABI, host compiler only
   libpvnet_nn.so     ADD-S nearest-neighbour search (include/pvnet_nn.h)
   libpvnet_pnp.so    batched uncertainty-PnP refinement (include/pvnet_pnp.h)
+  libpvnet_pose.so   batched pose with its start: P3P / DLT + the same refinement (include/pvnet_pose.h)
 
 Both land next to this file so they travel with the source tree (a JIT cache
 under ~/.cache would not).  hipcc cross-compiles for gfx950 without a GPU.
@@ -22,6 +23,7 @@ LIB = os.path.join(HERE, "libpvnet_vote.so")
 EXT = os.path.join(HERE, "ransac_voting.so")
 NNLIB = os.path.join(HERE, "libpvnet_nn.so")
 PNPLIB = os.path.join(HERE, "libpvnet_pnp.so")
+POSELIB = os.path.join(HERE, "libpvnet_pose.so")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
 # -ffp-contract=off is part of the numerical contract (bit-exact inlier counts), not a tuning flag.
@@ -73,14 +75,24 @@ def build_nn(force=False, verbose=False):
 def build_pnp(force=False, verbose=False):
     """libpvnet_pnp.so: the batched uncertainty-PnP refinement (include/pvnet_pnp.h), hipcc, no torch.  binary64
     throughout and not part of the bit-exactness contract: default fp-contract."""
-    src = os.path.join(CSRC, "pvnet_pnp.hip")
-    hdr = os.path.join(INCLUDE, "pvnet_pnp.h")
-    if not force and _newer(PNPLIB, src, hdr):
-        return PNPLIB
+    return _build_pnp_lib("pvnet_pnp", PNPLIB, force, verbose)
+
+
+def build_pose(force=False, verbose=False):
+    """libpvnet_pose.so: the batched pose with its start on the device (include/pvnet_pose.h), the refinement shared with
+    libpvnet_pnp.so through csrc/pnp_lm.hpp; hipcc, no torch, flags as build_pnp."""
+    return _build_pnp_lib("pvnet_pose", POSELIB, force, verbose)
+
+
+def _build_pnp_lib(name, target, force, verbose):
+    src = os.path.join(CSRC, name + ".hip")
+    hdr = os.path.join(INCLUDE, name + ".h")
+    if not force and _newer(target, src, hdr, os.path.join(CSRC, "pnp_lm.hpp")):
+        return target
     hipcc = shutil.which("hipcc") or os.path.join(ROCM, "bin", "hipcc")
     _run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-Wall",
-          "-I" + INCLUDE, "-o", PNPLIB, src], verbose)
-    return PNPLIB
+          "-I" + INCLUDE, "-o", target, src], verbose)
+    return target
 
 
 def build_ext(force=False, verbose=False):
@@ -107,7 +119,8 @@ def build_ext(force=False, verbose=False):
 
 
 def build_all(force=False, verbose=False):
-    return build_lib(force, verbose), build_ext(force, verbose), build_nn(force, verbose), build_pnp(force, verbose)
+    return (build_lib(force, verbose), build_ext(force, verbose), build_nn(force, verbose), build_pnp(force, verbose),
+            build_pose(force, verbose))
 
 
 if __name__ == "__main__":

@@ -10,7 +10,8 @@ one launch refines every pose.  There is no CPU fallback.
 Initial pose.  The reference starts from ``cv2.solvePnP(..., SOLVEPNP_P3P)`` on the four best-weighted keypoints
 (un_pnp_utils.py:28-32).  With OpenCV importable that call is made exactly so; without it (this image has no cv2) the
 start is a DLT over all keypoints (>= 6, not coplanar -- PVNet's 8 surface points + centre), orthogonalised: a different
-start inside the same basin; the refinement converges to the same minimum (tests/test_pnp.py).
+start inside the same basin; the refinement converges to the same minimum (tests/test_pnp.py).  ``uncertainty_pnp_batched``
+without ``init_rt`` computes that start on the device (``pose.py``, the same selection and solvers in HIP).
 """
 import ctypes
 import os
@@ -113,10 +114,12 @@ def p3p_depths(f, P):
     """Grunert's perspective-three-point solution: unit bearings ``f`` [3,3] of the object points ``P`` [3,3] -> the (up
     to four) depth triples (s1, s2, s3) with ``|s_i f_i - s_j f_j| = |P_i - P_j|``.  With s2 = u s1, s3 = v s1 the three
     cosine-law equations reduce to a quartic in v (Haralick et al., "Review and analysis of solutions of the three point
-    perspective pose estimation problem", 1994, eqs. 9-11)."""
+    perspective pose estimation problem", 1994, eqs. 9-11).  A collinear triple (sine of its angle <= 1e-6) has none."""
     a2 = float(((P[1] - P[2]) ** 2).sum()); b2 = float(((P[0] - P[2]) ** 2).sum()); c2 = float(((P[0] - P[1]) ** 2).sum())
     if min(a2, b2, c2) <= 0:
         return []
+    if float((np.cross(P[0] - P[1], P[0] - P[2]) ** 2).sum()) <= 1e-12 * c2 * b2:
+        return []                                   # collinear: the rotation about the line is undetermined
     ca, cb, cg = float(f[1] @ f[2]), float(f[0] @ f[2]), float(f[0] @ f[1])
     q, r = (a2 - c2) / b2, (a2 + c2) / b2
     coef = [(q - 1) ** 2 - 4 * c2 / b2 * ca ** 2,
@@ -254,17 +257,25 @@ def uncertainty_pnp_v2(points_2d, covars, points_3d, camera_matrix, type='single
     return np.concatenate([rodrigues(result_rt[:3]), result_rt[3:, None]], axis=-1)
 
 
-def uncertainty_pnp_batched(points_2d, weights_2d, points_3d, camera_matrix, init_rt, max_iterations=0,
+def uncertainty_pnp_batched(points_2d, weights_2d, points_3d, camera_matrix, init_rt=None, max_iterations=0,
                             function_tolerance=0.0, return_info=False):
     """The refinement for a whole batch on the device, one launch on the current stream, nothing read back.
     :param points_2d:      [b,pn,2] CUDA tensor (any float dtype; e.g. ``output['kpt_2d']``)
     :param weights_2d:     [b,pn,3] (wxx,wxy,wyy), e.g. ``output['var_weights']``
     :param points_3d:      [pn,3] (one object model) or [b,pn,3]
     :param camera_matrix:  [3,3] or [b,3,3]
-    :param init_rt:        [b,6] angle-axis + translation
+    :param init_rt:        [b,6] angle-axis + translation, or None: the reference's start computed on the device in the
+                           same launch (``pose.pose_batched(..., method="p3p")``: P3P on the four best-weighted keypoints,
+                           the weighted DLT when P3P has no solution; with pn == 4 the P3P pose is the result,
+                           un_pnp_utils.py:34-38).  An image without a start comes back as NaN.
     :return:               rt [b,6] float64 (and info [b,4]: initial cost, final cost, iterations, termination)
     """
     import torch
+    if init_rt is None:
+        from .pose import pose_batched
+        out = pose_batched(points_2d, points_3d, camera_matrix, weights_2d=weights_2d, method="p3p",
+                           max_iterations=max_iterations, function_tolerance=function_tolerance)
+        return (out["rt"], out["info"]) if return_info else out["rt"]
     dev = points_2d.device
     assert dev.type == "cuda", "uncertainty_pnp_batched needs CUDA tensors (no CPU path exists)"
     f64 = lambda t: t.to(device=dev, dtype=torch.float64).contiguous()          # noqa: E731

@@ -13,11 +13,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(HERE)))
 
 def main(argv):
     if "build_ext" not in argv:
-        sys.exit("usage: python setup.py build_ext --inplace   (builds libpvnet_pnp.so in clean-pvnet_amd/)")
+        sys.exit("usage: python setup.py build_ext --inplace   (builds libpvnet_pnp.so and libpvnet_pose.so in clean-pvnet_amd/)")
     spec = importlib.util.spec_from_file_location("_pvnet_vote_build", os.path.join(ROOT, "clean-pvnet_amd", "_build.py"))
     b = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(b)
-    for path in (b.build_pnp(verbose=True),):
+    for path in (b.build_pnp(verbose=True), b.build_pose(verbose=True)):
         print("built", os.path.relpath(path, ROOT))
 
 
