@@ -5,6 +5,8 @@
   libpvnet_nn.so     ADD-S nearest-neighbour search (include/pvnet_nn.h)
   libpvnet_pnp.so    batched uncertainty-PnP refinement (include/pvnet_pnp.h)
   libpvnet_pose.so   batched pose with its start: P3P / DLT + the same refinement (include/pvnet_pose.h)
+  libpvnet_metrics.so  batched pose scores: ADD, ADD-S with its search, 2D projection, 5 cm 5 degrees, mask IoU
+                     (include/pvnet_metrics.h)
 
 Both land next to this file so they travel with the source tree (a JIT cache
 under ~/.cache would not).  hipcc cross-compiles for gfx950 without a GPU.
@@ -24,6 +26,7 @@ EXT = os.path.join(HERE, "ransac_voting.so")
 NNLIB = os.path.join(HERE, "libpvnet_nn.so")
 PNPLIB = os.path.join(HERE, "libpvnet_pnp.so")
 POSELIB = os.path.join(HERE, "libpvnet_pose.so")
+METRICSLIB = os.path.join(HERE, "libpvnet_metrics.so")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
 # -ffp-contract=off is part of the numerical contract (bit-exact inlier counts), not a tuning flag.
@@ -70,6 +73,18 @@ def build_nn(force=False, verbose=False):
     hipcc = shutil.which("hipcc") or os.path.join(ROCM, "bin", "hipcc")
     _run([hipcc, *HIPCC_FLAGS, "-I" + INCLUDE, "-o", NNLIB, src], verbose)
     return NNLIB
+
+
+def build_metrics(force=False, verbose=False):
+    """libpvnet_metrics.so: the batched pose scores (include/pvnet_metrics.h), hipcc, no torch.  The flags of build_nn: the
+    ADD-S indices and the stated operation order need -ffp-contract=off."""
+    src = os.path.join(CSRC, "pvnet_metrics.hip")
+    hdr = os.path.join(INCLUDE, "pvnet_metrics.h")
+    if not force and _newer(METRICSLIB, src, hdr):
+        return METRICSLIB
+    hipcc = shutil.which("hipcc") or os.path.join(ROCM, "bin", "hipcc")
+    _run([hipcc, *HIPCC_FLAGS, "-I" + INCLUDE, "-o", METRICSLIB, src], verbose)
+    return METRICSLIB
 
 
 def build_pnp(force=False, verbose=False):
@@ -120,7 +135,7 @@ def build_ext(force=False, verbose=False):
 
 def build_all(force=False, verbose=False):
     return (build_lib(force, verbose), build_ext(force, verbose), build_nn(force, verbose), build_pnp(force, verbose),
-            build_pose(force, verbose))
+            build_pose(force, verbose), build_metrics(force, verbose))
 
 
 if __name__ == "__main__":

@@ -1,0 +1,185 @@
+"""Pose scores for a whole batch on the device (``libpvnet_metrics.so``, include/pvnet_metrics.h).
+
+The reference scores one image at a time on the host: ``Evaluator.evaluate`` (lib/evaluators/linemod/pvnet.py:175-205, the
+same in custom/pvnet.py:88-107 and tless_test/pvnet.py:107-125) calls ``add_metric``, ``projection_2d``,
+``cm_degree_5_metric`` and ``mask_iou`` in numpy, and for a symmetric object ``nn_utils.find_nearest_point_idx`` with its
+copies to the device and back.  Here the five values of every (prediction, ground truth) pair of a batch -- ADD, ADD-S with
+its nearest-neighbour search, the mean 2D projection distance, the translation and the angular distance -- come from one
+call on the current stream, reading ``output['pose']`` where ``pose.solve_pose`` left it; ``PoseEvaluator`` turns them into
+the reference's hit counts on the device and reads back once, in ``summarize()``.  There is no CPU fallback.
+"""
+import ctypes
+import os
+
+_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libpvnet_metrics.so")
+try:
+    _lib = ctypes.CDLL(_LIB)
+except OSError as e:
+    raise ImportError("clean_pvnet_amd.metrics: libpvnet_metrics.so is not built (run `python __graft_entry__.py`); "
+                      "there is no CPU fallback. Original error: %s" % (e,)) from e
+_lib.pvm_adds_slabs.restype = ctypes.c_int
+_lib.pvm_adds_slabs.argtypes = [ctypes.c_int, ctypes.c_int]
+_lib.pvm_workspace_bytes.restype = ctypes.c_size_t
+_lib.pvm_workspace_bytes.argtypes = [ctypes.c_int] * 3
+_lib.pvm_pose_metrics_batched.restype = ctypes.c_int
+_lib.pvm_pose_metrics_batched.argtypes = [ctypes.c_void_p] * 8 + [ctypes.c_int] * 4 + [ctypes.c_void_p]
+_lib.pvm_mask_iou_batched.restype = ctypes.c_int
+_lib.pvm_mask_iou_batched.argtypes = ([ctypes.c_void_p] * 2 + [ctypes.c_longlong] * 2 + [ctypes.c_int] * 2 +
+                                      [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3 + [ctypes.c_void_p])
+
+COLUMNS = ("add", "adds", "proj2d", "trans_cm", "ang_deg")          # PVM_ADD ... PVM_ANG_DEG
+
+
+def _need_cuda(t, what):
+    import torch
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+        raise RuntimeError("clean_pvnet_amd.metrics: %s must be a CUDA tensor; there is no CPU fallback" % what)
+
+
+def adds_slabs(b, n):
+    """The slab count the ADD-S search picks for a batch of ``b`` images and ``n`` model points (``pvm_adds_slabs``)."""
+    return int(_lib.pvm_adds_slabs(int(b), int(n)))
+
+
+def pose_metrics(pose_pred, pose_gt, model, K, *, symmetric=False, return_idx=False, slabs=0):
+    """ADD, ADD-S, 2D projection, translation and angle of ``b`` pose pairs, on the device, nothing read back.
+    :param pose_pred:  [b,3,4] CUDA tensor (``output['pose']``); a row with a non-finite value gives NaN in every value
+    :param pose_gt:    [b,3,4]
+    :param model:      [N,3] float32 CUDA tensor, the object model
+    :param K:          [3,3] or [b,3,3] CUDA tensor
+    :param symmetric:  a bool, or a [b] bool CUDA tensor: ``adds`` is computed where it is set and NaN elsewhere
+    :param return_idx: also return ``adds_idx`` [b,N] int32, the neighbour indices (zeros where ``adds`` is NaN)
+    :param slabs:      how many slabs the search splits the predicted cloud into; 0 lets the library choose.  The result
+                       does not depend on it (a test and tuning hook).
+    :return:           dict of [b] float64 CUDA tensors ``add``, ``adds``, ``proj2d``, ``trans_cm``, ``ang_deg``
+    """
+    import torch
+    for t, what in ((pose_pred, "pose_pred"), (pose_gt, "pose_gt"), (model, "model"), (K, "K")):
+        _need_cuda(t, what)
+    dev = pose_pred.device
+    pp = pose_pred.to(dtype=torch.float64).contiguous()
+    pg = pose_gt.to(device=dev, dtype=torch.float64).contiguous()
+    md = model.to(device=dev, dtype=torch.float32).contiguous()
+    Km = K.to(device=dev, dtype=torch.float64).contiguous()
+    b = pp.shape[0]
+    assert pp.shape == (b, 3, 4) and pg.shape == (b, 3, 4), (pp.shape, pg.shape)
+    assert md.dim() == 2 and md.shape[1] == 3 and md.shape[0] > 0, md.shape
+    assert Km.shape in ((3, 3), (b, 3, 3)), Km.shape
+    n = md.shape[0]
+    if isinstance(symmetric, torch.Tensor):
+        _need_cuda(symmetric, "symmetric")
+        assert symmetric.shape == (b,), symmetric.shape
+        sym = (symmetric != 0).to(torch.uint8).contiguous()
+    else:
+        sym = torch.ones(b, dtype=torch.uint8, device=dev) if symmetric else None
+    metrics = torch.empty(b, 5, dtype=torch.float64, device=dev)
+    idx = torch.empty(b, n, dtype=torch.int32, device=dev) if return_idx else None
+    if b:
+        nbytes = int(_lib.pvm_workspace_bytes(b, n, int(slabs)))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)       # caching allocator: stream-ordered, no hipMalloc per call
+        with torch.cuda.device(dev):
+            rc = _lib.pvm_pose_metrics_batched(pp.data_ptr(), pg.data_ptr(), md.data_ptr(), Km.data_ptr(),
+                                               None if sym is None else sym.data_ptr(), metrics.data_ptr(),
+                                               None if idx is None else idx.data_ptr(), ws.data_ptr(), b, n,
+                                               int(Km.dim() == 3), int(slabs), torch.cuda.current_stream().cuda_stream)
+        if rc != 0:
+            raise RuntimeError("pvm_pose_metrics_batched failed (%d)" % rc)
+    out = {k: metrics[:, i] for i, k in enumerate(COLUMNS)}
+    if return_idx:
+        out["adds_idx"] = idx
+    return out
+
+
+_MASK_DTYPES = None
+
+
+def _mask_arg(m, what):
+    """A [b,H,W] mask as (tensor, batch stride in elements, element size); only the batch dimension may be strided."""
+    import torch
+    global _MASK_DTYPES
+    if _MASK_DTYPES is None:
+        _MASK_DTYPES = {torch.int64: 8, torch.int32: 4, torch.uint8: 1, torch.bool: 1}
+    _need_cuda(m, what)
+    if m.dtype not in _MASK_DTYPES:
+        raise TypeError("mask_iou: %s has dtype %s, supported are int64, int32, uint8 and bool" % (what, m.dtype))
+    assert m.dim() == 3, m.shape
+    b, h, w = m.shape
+    if b and h and w and not (m.stride(2) == 1 and m.stride(1) == w and (b == 1 or m.stride(0) >= h * w)):
+        m = m.contiguous()
+    return m, (m.stride(0) if b > 1 else h * w), _MASK_DTYPES[m.dtype]
+
+
+def mask_counts(mask_pred, mask_gt):
+    """``(mask_pred & mask_gt).sum()`` and ``(mask_pred | mask_gt).sum()`` per image: two [b] int64 CUDA tensors."""
+    import torch
+    mp, sp, ep = _mask_arg(mask_pred, "mask_pred")
+    mg, sg, eg = _mask_arg(mask_gt, "mask_gt")
+    assert mp.shape == mg.shape, (mp.shape, mg.shape)
+    b, h, w = mp.shape
+    dev = mp.device
+    inter = torch.empty(b, dtype=torch.int64, device=dev)
+    union = torch.empty(b, dtype=torch.int64, device=dev)
+    if b:
+        with torch.cuda.device(dev):
+            rc = _lib.pvm_mask_iou_batched(mp.data_ptr(), mg.data_ptr(), sp, sg, ep, eg, inter.data_ptr(), union.data_ptr(),
+                                           b, h, w, torch.cuda.current_stream().cuda_stream)
+        if rc != 0:
+            raise RuntimeError("pvm_mask_iou_batched failed (%d)" % rc)
+    return inter, union
+
+
+def mask_iou(mask_pred, mask_gt):
+    """linemod/pvnet.py:96-99 for a batch: [b] float64 ``inter / union`` on the device (0 / 0 is NaN, as numpy gives)."""
+    import torch
+    inter, union = mask_counts(mask_pred, mask_gt)
+    return inter.to(torch.float64) / union.to(torch.float64)
+
+
+class PoseEvaluator:
+    """The comparisons and the bookkeeping of the reference's ``Evaluator`` (linemod/pvnet.py:59-100, :207-227) on the
+    device.  ``evaluate`` adds the hits of a batch to int64 counters without a synchronisation; ``summarize`` is the one
+    place that reads back.  ``last`` holds the per-image values and hits of the latest ``evaluate`` as device tensors."""
+
+    def __init__(self, model, diameter, symmetric=False, percentage=0.1, proj_threshold=5.0, iou_threshold=0.7,
+                 device="cuda"):
+        import torch
+        self.model = torch.as_tensor(model).to(device=device, dtype=torch.float32).contiguous()
+        if self.model.device.type != "cuda":
+            raise RuntimeError("clean_pvnet_amd.metrics: PoseEvaluator needs a CUDA device; there is no CPU fallback")
+        self.diameter = float(diameter)
+        self.symmetric = bool(symmetric)
+        self.percentage = float(percentage)
+        self.proj_threshold = float(proj_threshold)
+        self.iou_threshold = float(iou_threshold)
+        # proj2d, add, cmd5 hits, images; mask hits, images with a mask
+        self._counts = torch.zeros(6, dtype=torch.int64, device=self.model.device)
+        self.last = None
+
+    def evaluate(self, output, pose_gt, K, mask_gt=None):
+        """``output['pose']`` [b,3,4] against ``pose_gt`` [b,3,4] with the camera ``K`` ([3,3] or [b,3,3]), and
+        ``output['mask']`` against ``mask_gt`` [b,H,W] when one is given.  Everything is a CUDA tensor."""
+        import torch
+        m = pose_metrics(output["pose"], pose_gt, self.model, K, symmetric=self.symmetric)
+        dist = m["adds"] if self.symmetric else m["add"]
+        hits = {"add": dist < self.diameter * self.percentage,                       # a comparison with NaN is a miss
+                "proj2d": m["proj2d"] < self.proj_threshold,
+                "cmd5": (m["trans_cm"] < 5) & (m["ang_deg"] < 5)}
+        b = dist.shape[0]
+        n_img = torch.full((), b, dtype=torch.int64, device=dist.device)
+        zero = torch.zeros((), dtype=torch.int64, device=dist.device)
+        ap_hits, n_mask = zero, zero
+        if mask_gt is not None:
+            m["iou"] = mask_iou(output["mask"], mask_gt)
+            hits["ap"] = m["iou"] > self.iou_threshold
+            ap_hits, n_mask = hits["ap"].sum(), n_img
+        self._counts += torch.stack([hits["proj2d"].sum(), hits["add"].sum(), hits["cmd5"].sum(), n_img, ap_hits, n_mask])
+        self.last = {"values": m, "hits": hits}
+        return hits
+
+    def summarize(self):
+        """``Evaluator.summarize`` (:207-227): the hit rates since the last call, then the counters start again.  The mean
+        of no images is NaN, as ``np.mean([])``."""
+        c = [int(v) for v in self._counts.cpu().tolist()]
+        self._counts.zero_()
+        rate = lambda hits, n: hits / n if n else float("nan")                       # noqa: E731
+        return {"proj2d": rate(c[0], c[3]), "add": rate(c[1], c[3]), "cmd5": rate(c[2], c[3]), "ap": rate(c[4], c[5])}
