@@ -7,6 +7,7 @@
   libpvnet_pose.so   batched pose with its start: P3P / DLT + the same refinement (include/pvnet_pose.h)
   libpvnet_metrics.so  batched pose scores: ADD, ADD-S with its search, 2D projection, 5 cm 5 degrees, mask IoU
                      (include/pvnet_metrics.h)
+  libpvnet_vsd.so    batched depth rasteriser and Visible Surface Discrepancy (include/pvnet_vsd.h)
 
 Both land next to this file so they travel with the source tree (a JIT cache
 under ~/.cache would not).  hipcc cross-compiles for gfx950 without a GPU.
@@ -27,6 +28,7 @@ NNLIB = os.path.join(HERE, "libpvnet_nn.so")
 PNPLIB = os.path.join(HERE, "libpvnet_pnp.so")
 POSELIB = os.path.join(HERE, "libpvnet_pose.so")
 METRICSLIB = os.path.join(HERE, "libpvnet_metrics.so")
+VSDLIB = os.path.join(HERE, "libpvnet_vsd.so")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
 # -ffp-contract=off is part of the numerical contract (bit-exact inlier counts), not a tuning flag.
@@ -87,6 +89,18 @@ def build_metrics(force=False, verbose=False):
     return METRICSLIB
 
 
+def build_vsd(force=False, verbose=False):
+    """libpvnet_vsd.so: the batched depth rasteriser and VSD (include/pvnet_vsd.h), hipcc, no torch.  The flags of
+    build_metrics: the device equals the numpy twin bit for bit only with -ffp-contract=off."""
+    src = os.path.join(CSRC, "pvnet_vsd.hip")
+    hdr = os.path.join(INCLUDE, "pvnet_vsd.h")
+    if not force and _newer(VSDLIB, src, hdr):
+        return VSDLIB
+    hipcc = shutil.which("hipcc") or os.path.join(ROCM, "bin", "hipcc")
+    _run([hipcc, *HIPCC_FLAGS, "-I" + INCLUDE, "-o", VSDLIB, src], verbose)
+    return VSDLIB
+
+
 def build_pnp(force=False, verbose=False):
     """libpvnet_pnp.so: the batched uncertainty-PnP refinement (include/pvnet_pnp.h), hipcc, no torch.  binary64
     throughout and not part of the bit-exactness contract: default fp-contract."""
@@ -135,7 +149,7 @@ def build_ext(force=False, verbose=False):
 
 def build_all(force=False, verbose=False):
     return (build_lib(force, verbose), build_ext(force, verbose), build_nn(force, verbose), build_pnp(force, verbose),
-            build_pose(force, verbose), build_metrics(force, verbose))
+            build_pose(force, verbose), build_metrics(force, verbose), build_vsd(force, verbose))
 
 
 if __name__ == "__main__":

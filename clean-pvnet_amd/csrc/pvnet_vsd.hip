@@ -1,0 +1,548 @@
+// pvnet_vsd.hip -- a batched depth rasteriser and the Visible Surface Discrepancy of a whole batch on the device, native HIP
+// for gfx950 (include/pvnet_vsd.h has both arithmetic contracts and the reference lines each pass replaces).
+//
+//   k_vertices    grid (vertex tiles, P): eye-space coordinates in binary64 and the snapped image coordinates of every
+//                 (pose, vertex), once -- not once per triangle corner.
+//   k_raster      grid (tiles of 256 triangles, P).  A lane sets up one triangle (near clip, orientation, bounding box);
+//                 then the work is shared by its size: a piece whose bounding box holds at most kSmall samples is swept by
+//                 its own lane, every other piece by the whole wave -- 64 blocks of 8x8 samples are tested against the
+//                 three edges at a time (one block per lane), the blocks that survive are sampled one sample per lane.
+//                 A large flat triangle therefore keeps 64 lanes busy instead of leaving 63 waiting.  Depth: an unsigned
+//                 atomicMin on the float bits.
+//   k_resolve     the untouched samples (0xffffffff from the memset on the stream) become 0, the background.
+//   k_vsd         grid (pixel chunks, pairs): distance images, visibility masks and costs of one (prediction, ground truth)
+//                 pair, integer counts reduced per block and added with integer atomics; the 'tlinear' costs as one
+//                 tree-reduced sum per tile of 256 pixels.
+//   k_vsd_finish  a thread per pair: the tile sums in ascending order and the error.
+//
+// Index bounds: vertex i < N (grid tail and the face check 0 <= index < N before any vertex is read), triangle f < F, pose
+// p < P by the grid; every sample a kernel touches satisfies 0 <= x < W and 0 <= y < H because a piece's bounding box is
+// clamped to the image rectangle before it is swept; pixel index < H*W and tile < ntiles in k_vsd.
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cmath>
+#include <cstdint>
+
+#include "pvnet_vsd.h"
+
+#pragma clang fp contract(off)
+
+#define PVS_EXPORT extern "C" __attribute__((visibility("default")))
+
+namespace {
+
+constexpr int kBlock = 256;          // threads per block everywhere; also the tile of the fixed-order sums
+constexpr int kSmall = 32;           // a piece with at most this many samples in its bounding box is swept by its own lane
+constexpr int kBadCoord = INT_MIN;   // snapped coordinate of a vertex that has none (outside the near plane, or too large)
+constexpr double kSnapLimit = 268435456.0;   // 2^28
+constexpr int kTilesPerBlock = 4;    // k_vsd: tiles of 256 pixels a block walks
+constexpr unsigned kEmpty = 0xffffffffu;
+
+struct Vtx {                         // 32 bytes, one per (pose, vertex)
+    double X, Y, Z;
+    int U, V;
+};
+
+struct Cam {
+    double fx, s, cx, fy, cy;
+};
+
+struct Piece {                       // a clipped, oriented (positive area) triangle in snapped coordinates, with its samples
+    int ax, ay, bx, by, cx, cy;
+    int xmin, ymin, w, h;            // w == 0: no piece
+};
+
+int ceil_div(int a, int b) { return (a + b - 1) / b; }
+
+__device__ bool pose_finite(const double *P)
+{
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) ok = ok && isfinite(P[i]);
+    return ok;
+}
+
+__device__ Cam load_cam(const double *K)
+{
+    Cam c;
+    c.fx = K[0];
+    c.s = K[1];
+    c.cx = K[2];
+    c.fy = K[4];
+    c.cy = K[5];
+    return c;
+}
+
+// u = (fx*X + s*Y)/Z + cx, v = (fy*Y)/Z + cy, snapped to 8 sub-pixel bits; kBadCoord when out of range or not a number
+__device__ void project_snap(const Cam &c, double X, double Y, double Z, int *U, int *V)
+{
+    const double u = (c.fx * X + c.s * Y) / Z + c.cx;
+    const double v = (c.fy * Y) / Z + c.cy;
+    const double Ud = floor(256.0 * u + 0.5), Vd = floor(256.0 * v + 0.5);
+    const bool ok = fabs(Ud) <= kSnapLimit && fabs(Vd) <= kSnapLimit;      // false for NaN
+    *U = ok ? (int)Ud : kBadCoord;
+    *V = ok ? (int)Vd : kBadCoord;
+}
+
+__global__ __launch_bounds__(kBlock) void k_vertices(const float *__restrict__ pts, const double *__restrict__ pose,
+                                                     const double *__restrict__ K, Vtx *__restrict__ vtx, int N, int K_batched,
+                                                     double near)
+{
+    const int p = blockIdx.y;
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= N) return;
+    const double *T = pose + (size_t)p * 12;
+    const Cam c = load_cam(K + (K_batched ? (size_t)p * 9 : 0));
+    const double x = (double)pts[i * 3], y = (double)pts[i * 3 + 1], z = (double)pts[i * 3 + 2];
+    Vtx o;
+    o.X = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
+    o.Y = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
+    o.Z = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
+    o.U = o.V = kBadCoord;
+    if (o.Z >= near) project_snap(c, o.X, o.Y, o.Z, &o.U, &o.V);
+    vtx[(size_t)p * N + i] = o;
+}
+
+// The vertex where the edge from the inside vertex p to the outside vertex q meets Z = near, projected and snapped.
+__device__ void clip_snap(const Cam &c, const Vtx &p, const Vtx &q, double near, int *U, int *V)
+{
+    const double t = (near - p.Z) / (q.Z - p.Z);
+    const double X = p.X + t * (q.X - p.X);
+    const double Y = p.Y + t * (q.Y - p.Y);
+    project_snap(c, X, Y, near, U, V);
+}
+
+__device__ Piece make_piece(int U0, int V0, int U1, int V1, int U2, int V2, int W, int H)
+{
+    Piece t;
+    t.w = t.h = 0;
+    t.ax = t.ay = t.bx = t.by = t.cx = t.cy = t.xmin = t.ymin = 0;
+    if (U0 == kBadCoord || U1 == kBadCoord || U2 == kBadCoord) return t;
+    const long long area2 = (long long)(U1 - U0) * (V2 - V0) - (long long)(V1 - V0) * (U2 - U0);
+    if (area2 == 0) return t;
+    if (area2 < 0) {
+        int k = U1; U1 = U2; U2 = k;
+        k = V1; V1 = V2; V2 = k;
+    }
+    // samples (256x + 128, 256y + 128) inside the vertices' box: x >= (Umin - 128)/256, x <= (Umax - 128)/256
+    int xmin = (min(U0, min(U1, U2)) - 128 + 255) >> 8, xmax = (max(U0, max(U1, U2)) - 128) >> 8;
+    int ymin = (min(V0, min(V1, V2)) - 128 + 255) >> 8, ymax = (max(V0, max(V1, V2)) - 128) >> 8;
+    xmin = max(xmin, 0);
+    ymin = max(ymin, 0);
+    xmax = min(xmax, W - 1);
+    ymax = min(ymax, H - 1);
+    if (xmin > xmax || ymin > ymax) return t;
+    t.ax = U0; t.ay = V0; t.bx = U1; t.by = V1; t.cx = U2; t.cy = V2;
+    t.xmin = xmin; t.ymin = ymin; t.w = xmax - xmin + 1; t.h = ymax - ymin + 1;
+    return t;
+}
+
+// E = dx*(py - ay) - dy*(px - ax) > 0, or = 0 on an edge that owns its line.  |dx|, |dy| <= 2^29 and |py - ay|, |px - ax| <
+// 2^29: every product fits 59 bits.
+__device__ bool edge_in(int ax, int ay, int bx, int by, int px, int py)
+{
+    const int dx = bx - ax, dy = by - ay;
+    const long long E = (long long)dx * (py - ay) - (long long)dy * (px - ax);
+    const bool owns = dy > 0 || (dy == 0 && dx > 0);
+    return E > 0 || (E == 0 && owns);
+}
+
+__device__ bool covered(const Piece &t, int x, int y)
+{
+    const int px = 256 * x + 128, py = 256 * y + 128;
+    return edge_in(t.ax, t.ay, t.bx, t.by, px, py) && edge_in(t.bx, t.by, t.cx, t.cy, px, py) &&
+           edge_in(t.cx, t.cy, t.ax, t.ay, px, py);
+}
+
+// The largest value an edge function takes on the samples x0..x1, y0..y1 is negative: no sample of the block is inside.
+__device__ bool edge_rejects(int ax, int ay, int bx, int by, int x0, int y0, int x1, int y1)
+{
+    const int dx = bx - ax, dy = by - ay;
+    const int py = 256 * (dx > 0 ? y1 : y0) + 128, px = 256 * (dy > 0 ? x0 : x1) + 128;
+    return (long long)dx * (py - ay) - (long long)dy * (px - ax) < 0;
+}
+
+__device__ bool block_rejected(const Piece &t, int x0, int y0, int x1, int y1)
+{
+    return edge_rejects(t.ax, t.ay, t.bx, t.by, x0, y0, x1, y1) || edge_rejects(t.bx, t.by, t.cx, t.cy, x0, y0, x1, y1) ||
+           edge_rejects(t.cx, t.cy, t.ax, t.ay, x0, y0, x1, y1);
+}
+
+struct Plane {
+    double n0, n1, n2, num;
+};
+
+__device__ void shade(unsigned *__restrict__ img, int W, int x, int y, const Plane &pl, const Cam &c, double near, double far)
+{
+    const double dy = (((double)y + 0.5) - c.cy) / c.fy;
+    const double dx = ((((double)x + 0.5) - c.cx) - c.s * dy) / c.fx;
+    const double den = (pl.n0 * dx + pl.n1 * dy) + pl.n2;
+    if (den == 0.0) return;
+    const double Z = pl.num / den;
+    if (Z >= near && Z <= far) atomicMin(img + (size_t)y * W + x, __float_as_uint((float)Z));
+}
+
+__device__ int rl(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
+
+__device__ double rl(double v, int lane)
+{
+    return __hiloint2double(rl(__double2hiint(v), lane), rl(__double2loint(v), lane));
+}
+
+__device__ Piece rl(const Piece &t, int lane)
+{
+    Piece o;
+    o.ax = rl(t.ax, lane); o.ay = rl(t.ay, lane); o.bx = rl(t.bx, lane); o.by = rl(t.by, lane);
+    o.cx = rl(t.cx, lane); o.cy = rl(t.cy, lane);
+    o.xmin = rl(t.xmin, lane); o.ymin = rl(t.ymin, lane); o.w = rl(t.w, lane); o.h = rl(t.h, lane);
+    return o;
+}
+
+// One piece per lane (w == 0: none).  Small pieces by their own lane, the others by the whole wave.
+__device__ void sweep(const Piece &mine, const Plane &pl, unsigned *__restrict__ img, int W, const Cam &c, double near,
+                      double far)
+{
+    const int lane = threadIdx.x & 63;
+    const int cnt = mine.w * mine.h;                       // <= 2^28 by PVS_MAX_SIDE
+    const bool small = cnt <= kSmall;
+    if (small) {
+        int x = mine.xmin, y = mine.ymin;
+        for (int i = 0; i < cnt; ++i) {
+            if (covered(mine, x, y)) shade(img, W, x, y, pl, c, near, far);
+            if (++x == mine.xmin + mine.w) {
+                x = mine.xmin;
+                ++y;
+            }
+        }
+    }
+    unsigned long long big = __ballot(!small);
+    while (big) {
+        const int src = __ffsll((long long)big) - 1;
+        big &= big - 1;
+        const Piece t = rl(mine, src);
+        Plane q;
+        q.n0 = rl(pl.n0, src); q.n1 = rl(pl.n1, src); q.n2 = rl(pl.n2, src); q.num = rl(pl.num, src);
+        const int xmax = t.xmin + t.w - 1, ymax = t.ymin + t.h - 1;
+        const int bx0 = t.xmin >> 3, by0 = t.ymin >> 3;
+        const int nbx = (xmax >> 3) - bx0 + 1, nby = (ymax >> 3) - by0 + 1;
+        const int nblocks = nbx * nby;
+        for (int base = 0; base < nblocks; base += 64) {
+            const int bi = base + lane;
+            const int by = bi / nbx, bx = bi - by * nbx;
+            bool live = bi < nblocks;
+            if (live) {
+                const int x0 = max((bx0 + bx) << 3, t.xmin), y0 = max((by0 + by) << 3, t.ymin);
+                const int x1 = min(((bx0 + bx) << 3) + 7, xmax), y1 = min(((by0 + by) << 3) + 7, ymax);
+                live = !block_rejected(t, x0, y0, x1, y1);
+            }
+            unsigned long long todo = __ballot(live);
+            while (todo) {
+                const int j = __ffsll((long long)todo) - 1;
+                todo &= todo - 1;
+                const int x = ((bx0 + rl(bx, j)) << 3) + (lane & 7), y = ((by0 + rl(by, j)) << 3) + (lane >> 3);
+                if (x >= t.xmin && x <= xmax && y >= t.ymin && y <= ymax && covered(t, x, y))
+                    shade(img, W, x, y, q, c, near, far);
+            }
+        }
+    }
+}
+
+__device__ void rotate_left(Vtx &a, Vtx &b, Vtx &c, int r)
+{
+    if (r == 1) {
+        const Vtx k = a; a = b; b = c; c = k;
+    } else if (r == 2) {
+        const Vtx k = c; c = b; b = a; a = k;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_raster(const int32_t *__restrict__ faces, const Vtx *__restrict__ vtx,
+                                                   const double *__restrict__ pose, const double *__restrict__ K,
+                                                   unsigned *__restrict__ depth, int N, int F, int K_batched, int W, int H,
+                                                   double near, double far)
+{
+    const int p = blockIdx.y;
+    if (!pose_finite(pose + (size_t)p * 12)) return;       // block-uniform: an all-zero image
+    const Cam c = load_cam(K + (K_batched ? (size_t)p * 9 : 0));
+    const int f = blockIdx.x * kBlock + threadIdx.x;
+    Piece pc0 = make_piece(kBadCoord, 0, 0, 0, 0, 0, W, H), pc1 = pc0;
+    Plane pl = {0.0, 0.0, 0.0, 0.0};
+    if (f < F) {
+        const int i0 = faces[f * 3], i1 = faces[f * 3 + 1], i2 = faces[f * 3 + 2];
+        if (i0 >= 0 && i0 < N && i1 >= 0 && i1 < N && i2 >= 0 && i2 < N) {
+            const Vtx *vp = vtx + (size_t)p * N;
+            Vtx v0 = vp[i0], v1 = vp[i1], v2 = vp[i2];
+            const int m = (v0.Z >= near ? 1 : 0) | (v1.Z >= near ? 2 : 0) | (v2.Z >= near ? 4 : 0);
+            if (m) {
+                const double a0 = v1.X - v0.X, a1 = v1.Y - v0.Y, a2 = v1.Z - v0.Z;
+                const double b0 = v2.X - v0.X, b1 = v2.Y - v0.Y, b2 = v2.Z - v0.Z;
+                pl.n0 = a1 * b2 - a2 * b1;
+                pl.n1 = a2 * b0 - a0 * b2;
+                pl.n2 = a0 * b1 - a1 * b0;
+                pl.num = (pl.n0 * v0.X + pl.n1 * v0.Y) + pl.n2 * v0.Z;
+                if (m == 7) {
+                    pc0 = make_piece(v0.U, v0.V, v1.U, v1.V, v2.U, v2.V, W, H);
+                } else if (m == 1 || m == 2 || m == 4) {           // one vertex inside: (a, ab, ac)
+                    rotate_left(v0, v1, v2, m == 1 ? 0 : m == 2 ? 1 : 2);
+                    int Ub, Vb, Uc, Vc;
+                    clip_snap(c, v0, v1, near, &Ub, &Vb);
+                    clip_snap(c, v0, v2, near, &Uc, &Vc);
+                    pc0 = make_piece(v0.U, v0.V, Ub, Vb, Uc, Vc, W, H);
+                } else {                                            // one vertex outside, c: (a, b, bc) and (a, bc, ac)
+                    rotate_left(v0, v1, v2, m == 3 ? 0 : m == 6 ? 1 : 2);
+                    int Ub, Vb, Ua, Va;
+                    clip_snap(c, v1, v2, near, &Ub, &Vb);
+                    clip_snap(c, v0, v2, near, &Ua, &Va);
+                    pc0 = make_piece(v0.U, v0.V, v1.U, v1.V, Ub, Vb, W, H);
+                    pc1 = make_piece(v0.U, v0.V, Ub, Vb, Ua, Va, W, H);
+                }
+            }
+        }
+    }
+    unsigned *img = depth + (size_t)p * H * W;
+    sweep(pc0, pl, img, W, c, near, far);
+    if (__any(pc1.w != 0)) sweep(pc1, pl, img, W, c, near, far);
+}
+
+__global__ __launch_bounds__(kBlock) void k_resolve(unsigned *__restrict__ depth, size_t total)
+{
+    const size_t n4 = total / 4, stride = (size_t)gridDim.x * kBlock;
+    uint4 *d4 = (uint4 *)depth;
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += stride) {
+        uint4 v = d4[i];
+        if (v.x == kEmpty || v.y == kEmpty || v.z == kEmpty || v.w == kEmpty) {
+            v.x = v.x == kEmpty ? 0u : v.x;
+            v.y = v.y == kEmpty ? 0u : v.y;
+            v.z = v.z == kEmpty ? 0u : v.z;
+            v.w = v.w == kEmpty ? 0u : v.w;
+            d4[i] = v;
+        }
+    }
+    const size_t i = n4 * 4 + (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i < total && depth[i] == kEmpty) depth[i] = 0u;
+}
+
+// ------------------------------------------------------------------------------------------------------------------- VSD
+template <int KIND>
+__device__ double load_test(const void *p, size_t i, double scale)
+{
+    if (KIND == PVS_TEST_U16) return (double)((const uint16_t *)p)[i] * scale;
+    if (KIND == PVS_TEST_F32) return (double)((const float *)p)[i];
+    return ((const double *)p)[i];
+}
+
+// Xs = ((x - cx)*depth)*(1/fx), Ys alike, sqrt((Xs*Xs + Ys*Ys) + depth*depth)
+__device__ double dist_of(double xc, double yc, double ifx, double ify, double depth)
+{
+    const double Xs = (xc * depth) * ifx, Ys = (yc * depth) * ify;
+    return sqrt((Xs * Xs + Ys * Ys) + depth * depth);
+}
+
+__device__ bool visible(double dist_test, double dist_model, float delta)
+{
+    const bool valid = dist_test > 0.0 && dist_model > 0.0;
+    const float d_diff = (float)dist_model - (float)dist_test;
+    return d_diff <= delta && valid;
+}
+
+// Sum of the 256 values of a block in a fixed order: slot j += slot j + s for s = 128, 64, ..., 1.
+__device__ double block_sum(double v, double *sh)
+{
+    const int tid = threadIdx.x;
+    __syncthreads();
+    sh[tid] = v;
+    __syncthreads();
+#pragma unroll
+    for (int s = kBlock / 2; s > 0; s >>= 1) {
+        if (tid < s) sh[tid] += sh[tid + s];
+        __syncthreads();
+    }
+    return sh[0];
+}
+
+__device__ unsigned wave_sum(unsigned v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+    return v;
+}
+
+template <int KIND, bool TLINEAR>
+__global__ __launch_bounds__(kBlock) void k_vsd(const float *__restrict__ depth_est, const float *__restrict__ depth_gt,
+                                                const void *__restrict__ depth_test, double depth_scale,
+                                                const double *__restrict__ K, int K_batched, double delta, double tau,
+                                                unsigned long long *__restrict__ counts, double *__restrict__ tiles, int p, int g,
+                                                int W, int HW, int ntiles)
+{
+    __shared__ double sh[kBlock];
+    __shared__ unsigned shc[3][kBlock / 64];
+    const int pair = blockIdx.y, tid = threadIdx.x;
+    const int i = pair / (p * g), a = (pair / g) % p, b = pair % g;
+    const float *est = depth_est + ((size_t)i * p + a) * HW, *gt = depth_gt + ((size_t)i * g + b) * HW;
+    const size_t test0 = (size_t)i * HW;
+    const double *Kc = K + (K_batched ? (size_t)i * 9 : 0);
+    const double cx = Kc[2], cy = Kc[5], ifx = 1.0 / Kc[0], ify = 1.0 / Kc[4], itau = 1.0 / tau;
+    const float fdelta = (float)delta;
+    unsigned n_union = 0, n_inter = 0, n_cost = 0;
+    for (int k = 0; k < kTilesPerBlock; ++k) {
+        const int tile = blockIdx.x * kTilesPerBlock + k;
+        if (tile >= ntiles) break;                          // block-uniform
+        const int pix = tile * kBlock + tid;
+        double cost = 0.0;
+        if (pix < HW) {
+            const float dg = gt[pix], de = est[pix];
+            if (dg != 0.0f || de != 0.0f) {                 // both renders empty: neither mask can hold the pixel
+                const int y = pix / W, x = pix - y * W;
+                const double xc = (double)x - cx, yc = (double)y - cy;
+                const double dist_t = dist_of(xc, yc, ifx, ify, load_test<KIND>(depth_test, test0 + pix, depth_scale));
+                const double dist_g = dist_of(xc, yc, ifx, ify, (double)dg), dist_e = dist_of(xc, yc, ifx, ify, (double)de);
+                const bool vg = visible(dist_t, dist_g, fdelta);
+                const bool ve = visible(dist_t, dist_e, fdelta) || (vg && dist_e > 0.0);
+                n_union += (vg || ve) ? 1u : 0u;
+                if (vg && ve) {
+                    ++n_inter;
+                    const double c = fabs(dist_g - dist_e);
+                    n_cost += c >= tau ? 1u : 0u;
+                    const double cl = c * itau;
+                    cost = cl > 1.0 ? 1.0 : cl;
+                }
+            }
+        }
+        if (TLINEAR) {
+            const double s = block_sum(cost, sh);
+            if (tid == 0) tiles[(size_t)pair * ntiles + tile] = s;
+        }
+    }
+    n_union = wave_sum(n_union);
+    n_inter = wave_sum(n_inter);
+    n_cost = wave_sum(n_cost);
+    if ((tid & 63) == 0) {
+        shc[0][tid >> 6] = n_union;
+        shc[1][tid >> 6] = n_inter;
+        shc[2][tid >> 6] = n_cost;
+    }
+    __syncthreads();
+    if (tid < 3) {
+        unsigned s = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / 64; ++w) s += shc[tid][w];
+        if (s) atomicAdd(counts + (size_t)pair * 3 + tid, (unsigned long long)s);
+    }
+}
+
+__global__ void k_vsd_finish(const long long *__restrict__ counts, const double *__restrict__ tiles, double *__restrict__ e,
+                             int pairs, int ntiles, int tlinear)
+{
+    const int pair = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pair >= pairs) return;
+    const long long n_union = counts[(size_t)pair * 3 + PVS_UNION], n_inter = counts[(size_t)pair * 3 + PVS_INTER];
+    double r = 1.0;
+    if (n_union > 0) {
+        if (tlinear) {
+            double s = 0.0;
+            for (int t = 0; t < ntiles; ++t) s += tiles[(size_t)pair * ntiles + t];
+            r = (s + (double)(n_union - n_inter)) / (double)n_union;
+        } else {
+            r = (double)(counts[(size_t)pair * 3 + PVS_COST] + (n_union - n_inter)) / (double)n_union;
+        }
+    }
+    e[pair] = r;
+}
+
+template <int KIND>
+void launch_vsd(bool tlinear, dim3 grid, hipStream_t st, const float *est, const float *gt, const void *test, double scale,
+                const double *K, int K_batched, double delta, double tau, unsigned long long *counts, double *tiles, int p, int g,
+                int W, int HW, int ntiles)
+{
+    if (tlinear)
+        hipLaunchKernelGGL((k_vsd<KIND, true>), grid, dim3(kBlock), 0, st, est, gt, test, scale, K, K_batched, delta, tau, counts,
+                           tiles, p, g, W, HW, ntiles);
+    else
+        hipLaunchKernelGGL((k_vsd<KIND, false>), grid, dim3(kBlock), 0, st, est, gt, test, scale, K, K_batched, delta, tau, counts,
+                           tiles, p, g, W, HW, ntiles);
+}
+
+bool side_ok(int v) { return v > 0 && v <= PVS_MAX_SIDE; }
+
+}  // namespace
+
+PVS_EXPORT size_t pvs_render_workspace_bytes(int P, int N)
+{
+    if (P <= 0 || N <= 0) return 0;
+    return (size_t)P * N * sizeof(Vtx);
+}
+
+PVS_EXPORT int pvs_render_depth_batched(const float *d_pts, const int32_t *d_faces, const double *d_pose, const double *d_K,
+                                        float *d_depth, void *d_workspace, int P, int N, int F, int K_batched, int W, int H,
+                                        double near, double far, void *stream)
+{
+    if (P < 0 || P > 65535 || N <= 0 || F < 0 || !side_ok(W) || !side_ok(H)) return -1;
+    if (N > INT_MAX / 3 || F > INT_MAX / 3) return -1;
+    if (!(near > 0.0) || !(far >= near)) return -1;         // also refuses NaN
+    if (P == 0) return 0;
+    if (!d_pts || !d_pose || !d_K || !d_depth || !d_workspace || (F > 0 && !d_faces)) return -1;
+    if (((uintptr_t)d_workspace & 15) != 0 || ((uintptr_t)d_depth & 15) != 0) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t total = (size_t)P * H * W;
+    hipError_t e = hipMemsetAsync(d_depth, 0xff, total * sizeof(float), st);
+    if (e != hipSuccess) return (int)e;
+    Vtx *vtx = (Vtx *)d_workspace;
+    if (F > 0) {
+        hipLaunchKernelGGL(k_vertices, dim3(ceil_div(N, kBlock), P), dim3(kBlock), 0, st, d_pts, d_pose, d_K, vtx, N, K_batched,
+                           near);
+        hipLaunchKernelGGL(k_raster, dim3(ceil_div(F, kBlock), P), dim3(kBlock), 0, st, d_faces, vtx, d_pose, d_K,
+                           (unsigned *)d_depth, N, F, K_batched, W, H, near, far);
+    }
+    size_t blocks = (total / 4 + kBlock - 1) / kBlock;
+    blocks = blocks < 1 ? 1 : blocks > 2048 ? 2048 : blocks;
+    hipLaunchKernelGGL(k_resolve, dim3((unsigned)blocks), dim3(kBlock), 0, st, (unsigned *)d_depth, total);
+    return (int)hipGetLastError();
+}
+
+PVS_EXPORT size_t pvs_vsd_workspace_bytes(int n, int p, int g, int H, int W, int cost_type)
+{
+    if (n <= 0 || p <= 0 || g <= 0 || H <= 0 || W <= 0 || cost_type != PVS_COST_TLINEAR) return 0;
+    const size_t ntiles = ((size_t)H * W + kBlock - 1) / kBlock;
+    return (size_t)n * p * g * ntiles * sizeof(double);
+}
+
+PVS_EXPORT int pvs_vsd_batched(const float *d_depth_est, const float *d_depth_gt, const void *d_depth_test, int test_kind,
+                               double depth_scale, const double *d_K, int K_batched, double delta, double tau, int cost_type,
+                               long long *d_counts, double *d_e, void *d_workspace, int n, int p, int g, int H, int W,
+                               void *stream)
+{
+    if (n < 0 || p < 0 || g < 0 || !side_ok(W) || !side_ok(H)) return -1;
+    if (cost_type != PVS_COST_STEP && cost_type != PVS_COST_TLINEAR) return -1;
+    if (test_kind < PVS_TEST_U16 || test_kind > PVS_TEST_F64) return -1;
+    const long long pairs = (long long)n * p * g;
+    if (pairs > 65535) return -1;
+    if (pairs == 0) return 0;
+    if (!d_depth_est || !d_depth_gt || !d_depth_test || !d_K || !d_counts || !d_e) return -1;
+    const bool tlinear = cost_type == PVS_COST_TLINEAR;
+    if (tlinear && (!d_workspace || ((uintptr_t)d_workspace & 15) != 0)) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    const int HW = H * W, ntiles = ceil_div(HW, kBlock);
+    hipError_t err = hipMemsetAsync(d_counts, 0, (size_t)pairs * 3 * sizeof(long long), st);
+    if (err != hipSuccess) return (int)err;
+    const dim3 grid(ceil_div(ntiles, kTilesPerBlock), (unsigned)pairs);
+    unsigned long long *counts = (unsigned long long *)d_counts;
+    double *tiles = (double *)d_workspace;
+    switch (test_kind) {
+    case PVS_TEST_U16:
+        launch_vsd<PVS_TEST_U16>(tlinear, grid, st, d_depth_est, d_depth_gt, d_depth_test, depth_scale, d_K, K_batched, delta, tau,
+                                 counts, tiles, p, g, W, HW, ntiles);
+        break;
+    case PVS_TEST_F32:
+        launch_vsd<PVS_TEST_F32>(tlinear, grid, st, d_depth_est, d_depth_gt, d_depth_test, depth_scale, d_K, K_batched, delta, tau,
+                                 counts, tiles, p, g, W, HW, ntiles);
+        break;
+    default:
+        launch_vsd<PVS_TEST_F64>(tlinear, grid, st, d_depth_est, d_depth_gt, d_depth_test, depth_scale, d_K, K_batched, delta, tau,
+                                 counts, tiles, p, g, W, HW, ntiles);
+        break;
+    }
+    hipLaunchKernelGGL(k_vsd_finish, dim3(ceil_div((int)pairs, 64)), dim3(64), 0, st, (const long long *)d_counts, tiles, d_e,
+                       (int)pairs, ntiles, tlinear ? 1 : 0);
+    return (int)hipGetLastError();
+}
