@@ -1,15 +1,8 @@
-"""In-tree build of the native parts (gfx950 only).
+"""In-tree build of the native parts (gfx950 only): the HIP libraries of the ``HIP_LIBS`` table below -- each
+``csrc/pvnet_<name>.hip`` with its C ABI in ``include/pvnet_<name>.h`` becomes ``libpvnet_<name>.so``, hipcc, no torch -- and
+``ransac_voting.so``, the pybind11/torch shim over the C ABI of ``libpvnet_vote.so`` (host compiler only).
 
-  libpvnet_vote.so   HIP kernels + C ABI (include/pvnet_vote.h), hipcc, no torch
-  ransac_voting.so   pybind11/torch shim over that C ABI, host compiler only
-  libpvnet_nn.so     ADD-S nearest-neighbour search (include/pvnet_nn.h)
-  libpvnet_pnp.so    batched uncertainty-PnP refinement (include/pvnet_pnp.h)
-  libpvnet_pose.so   batched pose with its start: P3P / DLT + the same refinement (include/pvnet_pose.h)
-  libpvnet_metrics.so  batched pose scores: ADD, ADD-S with its search, 2D projection, 5 cm 5 degrees, mask IoU
-                     (include/pvnet_metrics.h)
-  libpvnet_vsd.so    batched depth rasteriser and Visible Surface Discrepancy (include/pvnet_vsd.h)
-
-Both land next to this file so they travel with the source tree (a JIT cache
+All land next to this file so they travel with the source tree (a JIT cache
 under ~/.cache would not).  hipcc cross-compiles for gfx950 without a GPU.
 """
 import os
@@ -22,13 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 INCLUDE = os.path.join(ROOT, "include")
 CSRC = os.path.join(HERE, "csrc")
-LIB = os.path.join(HERE, "libpvnet_vote.so")
 EXT = os.path.join(HERE, "ransac_voting.so")
-NNLIB = os.path.join(HERE, "libpvnet_nn.so")
-PNPLIB = os.path.join(HERE, "libpvnet_pnp.so")
-POSELIB = os.path.join(HERE, "libpvnet_pose.so")
-METRICSLIB = os.path.join(HERE, "libpvnet_metrics.so")
-VSDLIB = os.path.join(HERE, "libpvnet_vsd.so")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
 # -ffp-contract=off is part of the numerical contract (bit-exact inlier counts), not a tuning flag.
@@ -40,6 +27,19 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
                "-mllvm", "-amdgpu-mfma-vgpr-form", "-fPIC", "-shared", "-fvisibility=hidden", "-Wall",
                "-Wno-unused-function"]
+# pnp and pose are binary64 throughout and not part of the bit-exactness contract: default fp-contract
+PNP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-Wall"]
+
+# The HIP libraries: name -> (flags, include directories) of csrc/pvnet_<name>.hip.  metrics and vsd take HIPCC_FLAGS for
+# -ffp-contract=off: the ADD-S indices, the stated operation order and the bit-for-bit numpy twins need it.
+HIP_LIBS = {
+    "vote": (HIPCC_FLAGS, [INCLUDE, CSRC]),   # the voting kernels, one translation unit in parts (csrc/*.hpp)
+    "nn": (HIPCC_FLAGS, [INCLUDE]),           # the ADD-S nearest-neighbour search
+    "pnp": (PNP_FLAGS, [INCLUDE]),            # the batched uncertainty-PnP refinement
+    "pose": (PNP_FLAGS, [INCLUDE]),           # the batched pose with its start: P3P / DLT + the refinement of pnp (csrc/pnp_lm.hpp)
+    "metrics": (HIPCC_FLAGS, [INCLUDE]),      # the batched pose scores: ADD, ADD-S with its search, 2D projection, 5 cm 5 degrees, mask IoU
+    "vsd": (HIPCC_FLAGS, [INCLUDE]),          # the batched depth rasteriser and the Visible Surface Discrepancy
+}
 
 
 def _newer(target, *sources):
@@ -55,80 +55,36 @@ def _run(cmd, verbose):
     subprocess.check_call(cmd)
 
 
-def build_lib(force=False, verbose=False):
-    src = os.path.join(CSRC, "pvnet_vote.hip")
-    hdr = os.path.join(INCLUDE, "pvnet_vote.h")
-    parts = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".hpp")]
-    if not force and _newer(LIB, src, hdr, *parts):
-        return LIB
-    hipcc = shutil.which("hipcc") or os.path.join(ROCM, "bin", "hipcc")
-    _run([hipcc, *HIPCC_FLAGS, "-I" + INCLUDE, "-I" + CSRC, "-o", LIB, src], verbose)
-    return LIB
+def lib_path(name):
+    return os.path.join(HERE, "libpvnet_%s.so" % name)
 
 
-def build_nn(force=False, verbose=False):
-    """libpvnet_nn.so: the ADD-S nearest-neighbour search (include/pvnet_nn.h), hipcc, no torch."""
-    src = os.path.join(CSRC, "pvnet_nn.hip")
-    hdr = os.path.join(INCLUDE, "pvnet_nn.h")
-    if not force and _newer(NNLIB, src, hdr):
-        return NNLIB
-    hipcc = shutil.which("hipcc") or os.path.join(ROCM, "bin", "hipcc")
-    _run([hipcc, *HIPCC_FLAGS, "-I" + INCLUDE, "-o", NNLIB, src], verbose)
-    return NNLIB
+def hip_sources(name):
+    """What ``libpvnet_<name>.so`` is rebuilt after: its .hip, its ABI header and every csrc/*.hpp (more than any one library
+    includes, so that no header edit leaves a stale build)."""
+    return [os.path.join(CSRC, "pvnet_%s.hip" % name), os.path.join(INCLUDE, "pvnet_%s.h" % name),
+            *(os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".hpp"))]
 
 
-def build_metrics(force=False, verbose=False):
-    """libpvnet_metrics.so: the batched pose scores (include/pvnet_metrics.h), hipcc, no torch.  The flags of build_nn: the
-    ADD-S indices and the stated operation order need -ffp-contract=off."""
-    src = os.path.join(CSRC, "pvnet_metrics.hip")
-    hdr = os.path.join(INCLUDE, "pvnet_metrics.h")
-    if not force and _newer(METRICSLIB, src, hdr):
-        return METRICSLIB
-    hipcc = shutil.which("hipcc") or os.path.join(ROCM, "bin", "hipcc")
-    _run([hipcc, *HIPCC_FLAGS, "-I" + INCLUDE, "-o", METRICSLIB, src], verbose)
-    return METRICSLIB
-
-
-def build_vsd(force=False, verbose=False):
-    """libpvnet_vsd.so: the batched depth rasteriser and VSD (include/pvnet_vsd.h), hipcc, no torch.  The flags of
-    build_metrics: the device equals the numpy twin bit for bit only with -ffp-contract=off."""
-    src = os.path.join(CSRC, "pvnet_vsd.hip")
-    hdr = os.path.join(INCLUDE, "pvnet_vsd.h")
-    if not force and _newer(VSDLIB, src, hdr):
-        return VSDLIB
-    hipcc = shutil.which("hipcc") or os.path.join(ROCM, "bin", "hipcc")
-    _run([hipcc, *HIPCC_FLAGS, "-I" + INCLUDE, "-o", VSDLIB, src], verbose)
-    return VSDLIB
-
-
-def build_pnp(force=False, verbose=False):
-    """libpvnet_pnp.so: the batched uncertainty-PnP refinement (include/pvnet_pnp.h), hipcc, no torch.  binary64
-    throughout and not part of the bit-exactness contract: default fp-contract."""
-    return _build_pnp_lib("pvnet_pnp", PNPLIB, force, verbose)
-
-
-def build_pose(force=False, verbose=False):
-    """libpvnet_pose.so: the batched pose with its start on the device (include/pvnet_pose.h), the refinement shared with
-    libpvnet_pnp.so through csrc/pnp_lm.hpp; hipcc, no torch, flags as build_pnp."""
-    return _build_pnp_lib("pvnet_pose", POSELIB, force, verbose)
-
-
-def _build_pnp_lib(name, target, force, verbose):
-    src = os.path.join(CSRC, name + ".hip")
-    hdr = os.path.join(INCLUDE, name + ".h")
-    if not force and _newer(target, src, hdr, os.path.join(CSRC, "pnp_lm.hpp")):
+def build_hip(name, force=False, verbose=False):
+    flags, inc = HIP_LIBS[name]
+    target, src = lib_path(name), hip_sources(name)
+    if not force and _newer(target, *src):
         return target
     hipcc = shutil.which("hipcc") or os.path.join(ROCM, "bin", "hipcc")
-    _run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-Wall",
-          "-I" + INCLUDE, "-o", target, src], verbose)
+    _run([hipcc, *flags, *("-I" + d for d in inc), "-o", target, src[0]], verbose)
     return target
+
+
+def build_lib(force=False, verbose=False):
+    return build_hip("vote", force, verbose)
 
 
 def build_ext(force=False, verbose=False):
     src = os.path.join(CSRC, "ransac_voting_ext.cpp")
     hdr = os.path.join(INCLUDE, "pvnet_vote.h")
-    build_lib(verbose=verbose)
-    if not force and _newer(EXT, src, hdr, LIB):
+    lib = build_lib(verbose=verbose)
+    if not force and _newer(EXT, src, hdr, lib):
         return EXT
     import torch
     from torch.utils import cpp_extension as ce
@@ -148,8 +104,7 @@ def build_ext(force=False, verbose=False):
 
 
 def build_all(force=False, verbose=False):
-    return (build_lib(force, verbose), build_ext(force, verbose), build_nn(force, verbose), build_pnp(force, verbose),
-            build_pose(force, verbose), build_metrics(force, verbose), build_vsd(force, verbose))
+    return (*(build_hip(name, force, verbose) for name in HIP_LIBS), build_ext(force, verbose))
 
 
 if __name__ == "__main__":

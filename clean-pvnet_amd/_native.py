@@ -1,0 +1,51 @@
+"""The one loader and the one calling convention of the ctypes-bound native libraries (``libpvnet_nn.so``,
+``libpvnet_pnp.so``, ``libpvnet_pose.so``, ``libpvnet_metrics.so``, ``libpvnet_vsd.so``; ``_build.py`` has the table).
+
+Every device entry point of these libraries takes the stream as its last argument and returns 0 on success: ``call`` is that
+convention, ``load`` binds a library with its signatures, ``need_cuda`` / ``workspace`` / ``ptr`` are what the wrappers
+share around a call.  torch is imported where it is used, so a host-pointer wrapper (``nn_utils``) loads without it.
+There is no CPU fallback anywhere behind this module.
+"""
+import ctypes
+import os
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+PTR, INT, LONGLONG, DOUBLE, SIZE = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_double, ctypes.c_size_t
+
+
+def load(module, libname, signatures):
+    """``CDLL`` of ``libname`` next to this file for ``clean_pvnet_amd.<module>``, with ``restype`` / ``argtypes`` set from
+    ``signatures``: {symbol: (restype, argtypes)}."""
+    try:
+        lib = ctypes.CDLL(os.path.join(HERE, libname))
+    except OSError as e:
+        raise ImportError("clean_pvnet_amd.%s: %s is not built (run `python __graft_entry__.py`); "
+                          "there is no CPU fallback. Original error: %s" % (module, libname, e)) from e
+    for symbol, (restype, argtypes) in signatures.items():
+        fn = getattr(lib, symbol)
+        fn.restype, fn.argtypes = restype, argtypes
+    return lib
+
+
+def need_cuda(t, what, module):
+    import torch
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+        raise RuntimeError("clean_pvnet_amd.%s: %s must be a CUDA tensor; there is no CPU fallback" % (module, what))
+
+
+def call(lib, symbol, dev, *args):
+    """``lib.<symbol>(*args, stream)`` on the current stream of ``dev``; a non-zero return is a RuntimeError."""
+    import torch
+    with torch.cuda.device(dev):
+        rc = getattr(lib, symbol)(*args, torch.cuda.current_stream().cuda_stream)
+    if rc != 0:
+        raise RuntimeError("%s failed (%d)" % (symbol, rc))
+
+
+def workspace(nbytes, dev):
+    import torch
+    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)   # caching allocator: stream-ordered, no hipMalloc per call
+
+
+def ptr(t):
+    return None if t is None else t.data_ptr()

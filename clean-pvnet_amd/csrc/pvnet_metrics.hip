@@ -22,11 +22,10 @@
 
 #pragma clang fp contract(off)
 
-#define PVM_EXPORT extern "C" __attribute__((visibility("default")))
-
 namespace {
 
-constexpr int kBlock = 256;        // threads per block everywhere; also the tile of the fixed-order sums
+#include "eval_common.hpp"
+
 constexpr int kQ = 4;              // queries per lane in the search
 constexpr int kQTile = kBlock * kQ;
 constexpr int kRefTile = 1024;     // predicted points staged in LDS per step (16 KB)
@@ -37,8 +36,6 @@ constexpr int kMaskPerThread = 8;
 struct Layout {
     size_t part, pred4, targ4, keys, total;
 };
-
-int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 int auto_slabs(int B, int N)
 {
@@ -67,29 +64,6 @@ Layout layout(int B, int N, int S)
     l.keys = l.targ4 + (size_t)B * N * sizeof(float4);
     l.total = l.keys + (size_t)B * S * N * sizeof(unsigned long long);
     return l;
-}
-
-// Sum of the 256 values of a block in a fixed order: slot j += slot j + s for s = 128, 64, ..., 1.
-__device__ double block_sum(double v, double *sh)
-{
-    const int tid = threadIdx.x;
-    __syncthreads();
-    sh[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = kBlock / 2; s > 0; s >>= 1) {
-        if (tid < s) sh[tid] += sh[tid + s];
-        __syncthreads();
-    }
-    return sh[0];
-}
-
-__device__ bool pose_finite(const double *P)
-{
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) ok = ok && isfinite(P[i]);
-    return ok;
 }
 
 // x[i] = ((m0*R[i,0] + m1*R[i,1]) + m2*R[i,2]) + t[i]
@@ -319,15 +293,15 @@ __global__ __launch_bounds__(kBlock) void k_mask_iou(const void *__restrict__ mp
 
 }  // namespace
 
-PVM_EXPORT int pvm_adds_slabs(int B, int N) { return auto_slabs(B, N); }
+PVE_EXPORT int pvm_adds_slabs(int B, int N) { return auto_slabs(B, N); }
 
-PVM_EXPORT size_t pvm_workspace_bytes(int B, int N, int slabs)
+PVE_EXPORT size_t pvm_workspace_bytes(int B, int N, int slabs)
 {
     if (B <= 0 || N <= 0) return 0;
     return layout(B, N, pick_slabs(B, N, slabs)).total;
 }
 
-PVM_EXPORT int pvm_pose_metrics_batched(const double *d_pose_pred, const double *d_pose_gt, const float *d_model,
+PVE_EXPORT int pvm_pose_metrics_batched(const double *d_pose_pred, const double *d_pose_gt, const float *d_model,
                                         const double *d_K, const uint8_t *d_symmetric, double *d_metrics, int32_t *d_adds_idx,
                                         void *d_workspace, int B, int N, int K_batched, int slabs, void *stream)
 {
@@ -359,7 +333,7 @@ PVM_EXPORT int pvm_pose_metrics_batched(const double *d_pose_pred, const double 
     return (int)hipGetLastError();
 }
 
-PVM_EXPORT int pvm_mask_iou_batched(const void *d_mask_pred, const void *d_mask_gt, long long pred_stride_b,
+PVE_EXPORT int pvm_mask_iou_batched(const void *d_mask_pred, const void *d_mask_gt, long long pred_stride_b,
                                     long long gt_stride_b, int pred_elem_size, int gt_elem_size, long long *d_inter,
                                     long long *d_union, int B, int H, int W, void *stream)
 {

@@ -28,11 +28,10 @@
 
 #pragma clang fp contract(off)
 
-#define PVS_EXPORT extern "C" __attribute__((visibility("default")))
-
 namespace {
 
-constexpr int kBlock = 256;          // threads per block everywhere; also the tile of the fixed-order sums
+#include "eval_common.hpp"
+
 constexpr int kSmall = 32;           // a piece with at most this many samples in its bounding box is swept by its own lane
 constexpr int kBadCoord = INT_MIN;   // snapped coordinate of a vertex that has none (outside the near plane, or too large)
 constexpr double kSnapLimit = 268435456.0;   // 2^28
@@ -52,16 +51,6 @@ struct Piece {                       // a clipped, oriented (positive area) tria
     int ax, ay, bx, by, cx, cy;
     int xmin, ymin, w, h;            // w == 0: no piece
 };
-
-int ceil_div(int a, int b) { return (a + b - 1) / b; }
-
-__device__ bool pose_finite(const double *P)
-{
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) ok = ok && isfinite(P[i]);
-    return ok;
-}
 
 __device__ Cam load_cam(const double *K)
 {
@@ -346,21 +335,6 @@ __device__ bool visible(double dist_test, double dist_model, float delta)
     return d_diff <= delta && valid;
 }
 
-// Sum of the 256 values of a block in a fixed order: slot j += slot j + s for s = 128, 64, ..., 1.
-__device__ double block_sum(double v, double *sh)
-{
-    const int tid = threadIdx.x;
-    __syncthreads();
-    sh[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = kBlock / 2; s > 0; s >>= 1) {
-        if (tid < s) sh[tid] += sh[tid + s];
-        __syncthreads();
-    }
-    return sh[0];
-}
-
 __device__ unsigned wave_sum(unsigned v)
 {
 #pragma unroll
@@ -467,13 +441,13 @@ bool side_ok(int v) { return v > 0 && v <= PVS_MAX_SIDE; }
 
 }  // namespace
 
-PVS_EXPORT size_t pvs_render_workspace_bytes(int P, int N)
+PVE_EXPORT size_t pvs_render_workspace_bytes(int P, int N)
 {
     if (P <= 0 || N <= 0) return 0;
     return (size_t)P * N * sizeof(Vtx);
 }
 
-PVS_EXPORT int pvs_render_depth_batched(const float *d_pts, const int32_t *d_faces, const double *d_pose, const double *d_K,
+PVE_EXPORT int pvs_render_depth_batched(const float *d_pts, const int32_t *d_faces, const double *d_pose, const double *d_K,
                                         float *d_depth, void *d_workspace, int P, int N, int F, int K_batched, int W, int H,
                                         double near, double far, void *stream)
 {
@@ -500,14 +474,14 @@ PVS_EXPORT int pvs_render_depth_batched(const float *d_pts, const int32_t *d_fac
     return (int)hipGetLastError();
 }
 
-PVS_EXPORT size_t pvs_vsd_workspace_bytes(int n, int p, int g, int H, int W, int cost_type)
+PVE_EXPORT size_t pvs_vsd_workspace_bytes(int n, int p, int g, int H, int W, int cost_type)
 {
     if (n <= 0 || p <= 0 || g <= 0 || H <= 0 || W <= 0 || cost_type != PVS_COST_TLINEAR) return 0;
     const size_t ntiles = ((size_t)H * W + kBlock - 1) / kBlock;
     return (size_t)n * p * g * ntiles * sizeof(double);
 }
 
-PVS_EXPORT int pvs_vsd_batched(const float *d_depth_est, const float *d_depth_gt, const void *d_depth_test, int test_kind,
+PVE_EXPORT int pvs_vsd_batched(const float *d_depth_est, const float *d_depth_gt, const void *d_depth_test, int test_kind,
                                double depth_scale, const double *d_K, int K_batched, double delta, double tau, int cost_type,
                                long long *d_counts, double *d_e, void *d_workspace, int n, int p, int g, int H, int W,
                                void *stream)

@@ -8,32 +8,17 @@ its nearest-neighbour search, the mean 2D projection distance, the translation a
 call on the current stream, reading ``output['pose']`` where ``pose.solve_pose`` left it; ``PoseEvaluator`` turns them into
 the reference's hit counts on the device and reads back once, in ``summarize()``.  There is no CPU fallback.
 """
-import ctypes
-import os
+from . import _native
+from ._native import INT, LONGLONG, PTR, SIZE
 
-_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libpvnet_metrics.so")
-try:
-    _lib = ctypes.CDLL(_LIB)
-except OSError as e:
-    raise ImportError("clean_pvnet_amd.metrics: libpvnet_metrics.so is not built (run `python __graft_entry__.py`); "
-                      "there is no CPU fallback. Original error: %s" % (e,)) from e
-_lib.pvm_adds_slabs.restype = ctypes.c_int
-_lib.pvm_adds_slabs.argtypes = [ctypes.c_int, ctypes.c_int]
-_lib.pvm_workspace_bytes.restype = ctypes.c_size_t
-_lib.pvm_workspace_bytes.argtypes = [ctypes.c_int] * 3
-_lib.pvm_pose_metrics_batched.restype = ctypes.c_int
-_lib.pvm_pose_metrics_batched.argtypes = [ctypes.c_void_p] * 8 + [ctypes.c_int] * 4 + [ctypes.c_void_p]
-_lib.pvm_mask_iou_batched.restype = ctypes.c_int
-_lib.pvm_mask_iou_batched.argtypes = ([ctypes.c_void_p] * 2 + [ctypes.c_longlong] * 2 + [ctypes.c_int] * 2 +
-                                      [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3 + [ctypes.c_void_p])
+_lib = _native.load("metrics", "libpvnet_metrics.so", {
+    "pvm_adds_slabs": (INT, [INT] * 2),
+    "pvm_workspace_bytes": (SIZE, [INT] * 3),
+    "pvm_pose_metrics_batched": (INT, [PTR] * 8 + [INT] * 4 + [PTR]),
+    "pvm_mask_iou_batched": (INT, [PTR] * 2 + [LONGLONG] * 2 + [INT] * 2 + [PTR] * 2 + [INT] * 3 + [PTR]),
+})
 
 COLUMNS = ("add", "adds", "proj2d", "trans_cm", "ang_deg")          # PVM_ADD ... PVM_ANG_DEG
-
-
-def _need_cuda(t, what):
-    import torch
-    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-        raise RuntimeError("clean_pvnet_amd.metrics: %s must be a CUDA tensor; there is no CPU fallback" % what)
 
 
 def adds_slabs(b, n):
@@ -55,7 +40,7 @@ def pose_metrics(pose_pred, pose_gt, model, K, *, symmetric=False, return_idx=Fa
     """
     import torch
     for t, what in ((pose_pred, "pose_pred"), (pose_gt, "pose_gt"), (model, "model"), (K, "K")):
-        _need_cuda(t, what)
+        _native.need_cuda(t, what, "metrics")
     dev = pose_pred.device
     pp = pose_pred.to(dtype=torch.float64).contiguous()
     pg = pose_gt.to(device=dev, dtype=torch.float64).contiguous()
@@ -67,7 +52,7 @@ def pose_metrics(pose_pred, pose_gt, model, K, *, symmetric=False, return_idx=Fa
     assert Km.shape in ((3, 3), (b, 3, 3)), Km.shape
     n = md.shape[0]
     if isinstance(symmetric, torch.Tensor):
-        _need_cuda(symmetric, "symmetric")
+        _native.need_cuda(symmetric, "symmetric", "metrics")
         assert symmetric.shape == (b,), symmetric.shape
         sym = (symmetric != 0).to(torch.uint8).contiguous()
     else:
@@ -75,15 +60,9 @@ def pose_metrics(pose_pred, pose_gt, model, K, *, symmetric=False, return_idx=Fa
     metrics = torch.empty(b, 5, dtype=torch.float64, device=dev)
     idx = torch.empty(b, n, dtype=torch.int32, device=dev) if return_idx else None
     if b:
-        nbytes = int(_lib.pvm_workspace_bytes(b, n, int(slabs)))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)       # caching allocator: stream-ordered, no hipMalloc per call
-        with torch.cuda.device(dev):
-            rc = _lib.pvm_pose_metrics_batched(pp.data_ptr(), pg.data_ptr(), md.data_ptr(), Km.data_ptr(),
-                                               None if sym is None else sym.data_ptr(), metrics.data_ptr(),
-                                               None if idx is None else idx.data_ptr(), ws.data_ptr(), b, n,
-                                               int(Km.dim() == 3), int(slabs), torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            raise RuntimeError("pvm_pose_metrics_batched failed (%d)" % rc)
+        ws = _native.workspace(_lib.pvm_workspace_bytes(b, n, int(slabs)), dev)
+        _native.call(_lib, "pvm_pose_metrics_batched", dev, pp.data_ptr(), pg.data_ptr(), md.data_ptr(), Km.data_ptr(),
+                     _native.ptr(sym), metrics.data_ptr(), _native.ptr(idx), ws.data_ptr(), b, n, int(Km.dim() == 3), int(slabs))
     out = {k: metrics[:, i] for i, k in enumerate(COLUMNS)}
     if return_idx:
         out["adds_idx"] = idx
@@ -99,7 +78,7 @@ def _mask_arg(m, what):
     global _MASK_DTYPES
     if _MASK_DTYPES is None:
         _MASK_DTYPES = {torch.int64: 8, torch.int32: 4, torch.uint8: 1, torch.bool: 1}
-    _need_cuda(m, what)
+    _native.need_cuda(m, what, "metrics")
     if m.dtype not in _MASK_DTYPES:
         raise TypeError("mask_iou: %s has dtype %s, supported are int64, int32, uint8 and bool" % (what, m.dtype))
     assert m.dim() == 3, m.shape
@@ -120,11 +99,8 @@ def mask_counts(mask_pred, mask_gt):
     inter = torch.empty(b, dtype=torch.int64, device=dev)
     union = torch.empty(b, dtype=torch.int64, device=dev)
     if b:
-        with torch.cuda.device(dev):
-            rc = _lib.pvm_mask_iou_batched(mp.data_ptr(), mg.data_ptr(), sp, sg, ep, eg, inter.data_ptr(), union.data_ptr(),
-                                           b, h, w, torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            raise RuntimeError("pvm_mask_iou_batched failed (%d)" % rc)
+        _native.call(_lib, "pvm_mask_iou_batched", dev, mp.data_ptr(), mg.data_ptr(), sp, sg, ep, eg, inter.data_ptr(),
+                     union.data_ptr(), b, h, w)
     return inter, union
 
 

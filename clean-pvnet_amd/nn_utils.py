@@ -4,20 +4,11 @@ The reference binds ``findNearestPointIdxLauncher`` of its CUDA library through 
 needed here: the same C symbol, exported by ``libpvnet_nn.so`` (HIP, gfx950), is bound with ctypes.  Same function name,
 arguments (numpy arrays on the host) and return value as the reference; there is no CPU fallback.
 """
-import ctypes
-import os
-
 import numpy as np
 
-_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libpvnet_nn.so")
-try:
-    _lib = ctypes.CDLL(_LIB)
-except OSError as e:
-    raise ImportError("clean_pvnet_amd.nn_utils: libpvnet_nn.so is not built (run `python __graft_entry__.py`); "
-                      "there is no CPU fallback. Original error: %s" % (e,)) from e
-_lib.findNearestPointIdxLauncher.restype = None
-_lib.findNearestPointIdxLauncher.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                             ctypes.c_int, ctypes.c_int, ctypes.c_int]
+from ._native import INT, PTR, load
+
+_lib = load("nn_utils", "libpvnet_nn.so", {"findNearestPointIdxLauncher": (None, [PTR] * 3 + [INT] * 5)})
 
 
 def find_nearest_point_idx(ref_pts, que_pts):

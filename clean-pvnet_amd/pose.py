@@ -11,22 +11,15 @@ Here both run for the batch in one launch on the current stream, reading ``outpu
 A planar object model (OpenCV would take a homography start there) and fewer than six keypoints for the DLT have no start:
 those images come back as NaN with their status.  There is no CPU fallback.
 """
-import ctypes
-import os
-
 import numpy as np
 
-_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libpvnet_pose.so")
-try:
-    _lib = ctypes.CDLL(_LIB)
-except OSError as e:
-    raise ImportError("clean_pvnet_amd.pose: libpvnet_pose.so is not built (run `python __graft_entry__.py`); "
-                      "there is no CPU fallback. Original error: %s" % (e,)) from e
-_lib.pvp_initial_pose_batched.restype = ctypes.c_int
-_lib.pvp_initial_pose_batched.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 4 + [ctypes.c_void_p]
-_lib.pvp_pose_batched.restype = ctypes.c_int
-_lib.pvp_pose_batched.argtypes = ([ctypes.c_void_p] * 4 + [ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_int] * 5 +
-                                  [ctypes.c_double, ctypes.c_void_p])
+from . import _native
+from ._native import DOUBLE, INT, PTR
+
+_lib = _native.load("pose", "libpvnet_pose.so", {
+    "pvp_initial_pose_batched": (INT, [PTR] * 4 + [INT] + [PTR] * 2 + [INT] * 4 + [PTR]),
+    "pvp_pose_batched": (INT, [PTR] * 4 + [INT] + [PTR] * 5 + [INT] * 5 + [DOUBLE, PTR]),
+})
 
 METHODS = {"p3p": 0, "dlt": 1}                    # PVP_START_P3P, PVP_START_DLT
 # d_status codes (PVP_STATUS_*): >= 0 a start was found, < 0 the image's outputs are NaN
@@ -48,10 +41,6 @@ def _inputs(points_2d, points_3d, camera_matrix, weights_2d):
     return dev, p2, p3, Km, w2, b, pn
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 def initial_pose_batched(points_2d, points_3d, camera_matrix, weights_2d=None, method="p3p"):
     """The start alone, for a batch, on the device (one launch on the current stream, nothing read back).
     :param points_2d:      [b,pn,2] CUDA tensor, any float dtype
@@ -71,12 +60,8 @@ def initial_pose_batched(points_2d, points_3d, camera_matrix, weights_2d=None, m
     status = torch.empty(b, dtype=torch.int32, device=dev)
     if b == 0:
         return rt, status
-    with torch.cuda.device(dev):
-        rc = _lib.pvp_initial_pose_batched(p2.data_ptr(), p3.data_ptr(), _ptr(w2), Km.data_ptr(), METHODS[method], rt.data_ptr(),
-                                           status.data_ptr(), b, pn, int(p3.dim() == 3), int(Km.dim() == 3),
-                                           torch.cuda.current_stream().cuda_stream)
-    if rc != 0:
-        raise RuntimeError("pvp_initial_pose_batched failed (%d)" % rc)
+    _native.call(_lib, "pvp_initial_pose_batched", dev, p2.data_ptr(), p3.data_ptr(), _native.ptr(w2), Km.data_ptr(),
+                 METHODS[method], rt.data_ptr(), status.data_ptr(), b, pn, int(p3.dim() == 3), int(Km.dim() == 3))
     return rt, status
 
 
@@ -96,13 +81,10 @@ def pose_batched(points_2d, points_3d, camera_matrix, weights_2d=None, method="d
     out["status"] = torch.empty(b, dtype=torch.int32, device=dev)
     if b == 0:
         return out
-    with torch.cuda.device(dev):
-        rc = _lib.pvp_pose_batched(p2.data_ptr(), p3.data_ptr(), _ptr(w2), Km.data_ptr(), METHODS[method], out["rt"].data_ptr(),
-                                   out["Rt"].data_ptr(), out["init_rt"].data_ptr(), out["status"].data_ptr(),
-                                   out["info"].data_ptr(), b, pn, int(p3.dim() == 3), int(Km.dim() == 3), int(max_iterations),
-                                   float(function_tolerance), torch.cuda.current_stream().cuda_stream)
-    if rc != 0:
-        raise RuntimeError("pvp_pose_batched failed (%d)" % rc)
+    _native.call(_lib, "pvp_pose_batched", dev, p2.data_ptr(), p3.data_ptr(), _native.ptr(w2), Km.data_ptr(), METHODS[method],
+                 out["rt"].data_ptr(), out["Rt"].data_ptr(), out["init_rt"].data_ptr(), out["status"].data_ptr(),
+                 out["info"].data_ptr(), b, pn, int(p3.dim() == 3), int(Km.dim() == 3), int(max_iterations),
+                 float(function_tolerance))
     return out
 
 

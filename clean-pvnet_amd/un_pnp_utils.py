@@ -13,22 +13,15 @@ start is a DLT over all keypoints (>= 6, not coplanar -- PVNet's 8 surface point
 start inside the same basin; the refinement converges to the same minimum (tests/test_pnp.py).  ``uncertainty_pnp_batched``
 without ``init_rt`` computes that start on the device (``pose.py``, the same selection and solvers in HIP).
 """
-import ctypes
-import os
-
 import numpy as np
 
-_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libpvnet_pnp.so")
-try:
-    _lib = ctypes.CDLL(_LIB)
-except OSError as e:
-    raise ImportError("clean_pvnet_amd.un_pnp_utils: libpvnet_pnp.so is not built (run `python __graft_entry__.py`); "
-                      "there is no CPU fallback. Original error: %s" % (e,)) from e
-_dp = ctypes.POINTER(ctypes.c_double)
-_lib.uncertainty_pnp.restype = None
-_lib.uncertainty_pnp.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_int]
-_lib.pvp_uncertainty_pnp_batched.restype = ctypes.c_int
-_lib.pvp_uncertainty_pnp_batched.argtypes = [ctypes.c_void_p] * 7 + [ctypes.c_int] * 5 + [ctypes.c_double, ctypes.c_void_p]
+from . import _native
+from ._native import DOUBLE, INT, PTR
+
+_lib = _native.load("un_pnp_utils", "libpvnet_pnp.so", {
+    "uncertainty_pnp": (None, [PTR] * 6 + [INT]),
+    "pvp_uncertainty_pnp_batched": (INT, [PTR] * 7 + [INT] * 5 + [DOUBLE, PTR]),
+})
 
 
 def rodrigues(w):
@@ -287,11 +280,7 @@ def uncertainty_pnp_batched(points_2d, weights_2d, points_3d, camera_matrix, ini
     info = torch.empty(b, 4, dtype=torch.float64, device=dev) if return_info else None
     if b == 0:
         return (out, info) if return_info else out
-    with torch.cuda.device(dev):
-        rc = _lib.pvp_uncertainty_pnp_batched(p2.data_ptr(), p3.data_ptr(), w2.data_ptr(), Km.data_ptr(), rt0.data_ptr(),
-                                              out.data_ptr(), info.data_ptr() if return_info else None, b, pn,
-                                              1 if p3.dim() == 3 else 0, 1 if Km.dim() == 3 else 0, int(max_iterations),
-                                              float(function_tolerance), torch.cuda.current_stream().cuda_stream)
-    if rc != 0:
-        raise RuntimeError("pvp_uncertainty_pnp_batched failed (%d)" % rc)
+    _native.call(_lib, "pvp_uncertainty_pnp_batched", dev, p2.data_ptr(), p3.data_ptr(), w2.data_ptr(), Km.data_ptr(),
+                 rt0.data_ptr(), out.data_ptr(), _native.ptr(info), b, pn, 1 if p3.dim() == 3 else 0, 1 if Km.dim() == 3 else 0,
+                 int(max_iterations), float(function_tolerance))
     return (out, info) if return_info else out

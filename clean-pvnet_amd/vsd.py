@@ -10,40 +10,19 @@ image, and ``VsdEvaluator`` applies the reference's any-pair rule and counts the
 before ``summarize()``.  Every call runs on the current stream in a workspace from the caching allocator.  There is no CPU
 fallback.
 """
-import ctypes
-import os
+from . import _native
+from ._native import DOUBLE, INT, PTR, SIZE
 
-_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libpvnet_vsd.so")
-try:
-    _lib = ctypes.CDLL(_LIB)
-except OSError as e:
-    raise ImportError("clean_pvnet_amd.vsd: libpvnet_vsd.so is not built (run `python __graft_entry__.py`); "
-                      "there is no CPU fallback. Original error: %s" % (e,)) from e
-_lib.pvs_render_workspace_bytes.restype = ctypes.c_size_t
-_lib.pvs_render_workspace_bytes.argtypes = [ctypes.c_int] * 2
-_lib.pvs_render_depth_batched.restype = ctypes.c_int
-_lib.pvs_render_depth_batched.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_int] * 6 + [ctypes.c_double] * 2 + [ctypes.c_void_p]
-_lib.pvs_vsd_workspace_bytes.restype = ctypes.c_size_t
-_lib.pvs_vsd_workspace_bytes.argtypes = [ctypes.c_int] * 6
-_lib.pvs_vsd_batched.restype = ctypes.c_int
-_lib.pvs_vsd_batched.argtypes = ([ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_int,
-                                                          ctypes.c_double, ctypes.c_double, ctypes.c_int] +
-                                 [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_void_p])
+_lib = _native.load("vsd", "libpvnet_vsd.so", {
+    "pvs_render_workspace_bytes": (SIZE, [INT] * 2),
+    "pvs_render_depth_batched": (INT, [PTR] * 6 + [INT] * 6 + [DOUBLE] * 2 + [PTR]),
+    "pvs_vsd_workspace_bytes": (SIZE, [INT] * 6),
+    "pvs_vsd_batched": (INT, [PTR] * 3 + [INT, DOUBLE, PTR, INT, DOUBLE, DOUBLE, INT] + [PTR] * 3 + [INT] * 5 + [PTR]),
+})
 
 COSTS = {"step": 0, "tlinear": 1}                                    # PVS_COST_*
 COUNTS = ("union", "inter", "cost")                                  # PVS_UNION, PVS_INTER, PVS_COST
 MAX_SIDE = 16384                                                     # PVS_MAX_SIDE
-
-
-def _need_cuda(t, what):
-    import torch
-    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-        raise RuntimeError("clean_pvnet_amd.vsd: %s must be a CUDA tensor; there is no CPU fallback" % what)
-
-
-def _workspace(nbytes, dev):
-    import torch
-    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)   # caching allocator: stream-ordered
 
 
 def _check_size(size):
@@ -66,7 +45,7 @@ def render_depth(pts, faces, pose, K, size, near=100., far=10000.):
     """
     import torch
     for t, what in ((pts, "pts"), (faces, "faces"), (pose, "pose"), (K, "K")):
-        _need_cuda(t, what)
+        _native.need_cuda(t, what, "vsd")
     W, H = _check_size(size)
     if not (float(near) > 0.0 and float(far) >= float(near)):
         raise ValueError("0 < near <= far is required, got near=%r far=%r" % (near, far))
@@ -82,14 +61,10 @@ def render_depth(pts, faces, pose, K, size, near=100., far=10000.):
     assert Km.shape in ((3, 3), (P, 3, 3)), Km.shape
     depth = torch.empty(P, H, W, dtype=torch.float32, device=dev)
     if P:
-        ws = _workspace(_lib.pvs_render_workspace_bytes(P, md.shape[0]), dev)
-        with torch.cuda.device(dev):
-            rc = _lib.pvs_render_depth_batched(md.data_ptr(), fc.data_ptr() if fc.shape[0] else None, ps.data_ptr(),
-                                               Km.data_ptr(), depth.data_ptr(), ws.data_ptr(), P, md.shape[0], fc.shape[0],
-                                               int(Km.dim() == 3), W, H, float(near), float(far),
-                                               torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            raise RuntimeError("pvs_render_depth_batched failed (%d)" % rc)
+        ws = _native.workspace(_lib.pvs_render_workspace_bytes(P, md.shape[0]), dev)
+        _native.call(_lib, "pvs_render_depth_batched", dev, md.data_ptr(), fc.data_ptr() if fc.shape[0] else None, ps.data_ptr(),
+                     Km.data_ptr(), depth.data_ptr(), ws.data_ptr(), P, md.shape[0], fc.shape[0], int(Km.dim() == 3), W, H,
+                     float(near), float(far))
     return depth
 
 
@@ -102,7 +77,7 @@ def _test_image(depth_test, depth_scale):
     global _TEST_KINDS
     if _TEST_KINDS is None:
         _TEST_KINDS = {torch.uint16: 0, torch.float32: 1, torch.float64: 2}
-    _need_cuda(depth_test, "depth_test")
+    _native.need_cuda(depth_test, "depth_test", "vsd")
     if depth_test.dtype not in _TEST_KINDS:
         raise TypeError("vsd: depth_test has dtype %s, supported are uint16, float32 and float64" % depth_test.dtype)
     kind = _TEST_KINDS[depth_test.dtype]
@@ -131,7 +106,7 @@ def vsd(pose_est, pose_gt, depth_test, K, pts, faces, *, delta=15., tau=20., cos
     """
     import torch
     for t, what in ((pose_est, "pose_est"), (pose_gt, "pose_gt"), (K, "K"), (pts, "pts"), (faces, "faces")):
-        _need_cuda(t, what)
+        _native.need_cuda(t, what, "vsd")
     if cost not in COSTS:
         raise ValueError("vsd: cost must be 'step' or 'tlinear', got %r" % (cost,))
     dt, kind = _test_image(depth_test, depth_scale)
@@ -145,7 +120,7 @@ def vsd(pose_est, pose_gt, depth_test, K, pts, faces, *, delta=15., tau=20., cos
     Km = K.to(device=dev, dtype=torch.float64).contiguous()
     assert Km.shape in ((3, 3), (n, 3, 3)), Km.shape
     if gt_valid is not None:
-        _need_cuda(gt_valid, "gt_valid")
+        _native.need_cuda(gt_valid, "gt_valid", "vsd")
         assert gt_valid.shape == (n, g), gt_valid.shape
     # one render per pose: the n*p predictions, then the n*g ground truths
     poses = torch.cat([pose_est.to(torch.float64).reshape(n * p, 3, 4), pose_gt.to(device=dev, dtype=torch.float64).reshape(n * g, 3, 4)])
@@ -159,14 +134,10 @@ def vsd(pose_est, pose_gt, depth_test, K, pts, faces, *, delta=15., tau=20., cos
     counts = torch.empty(n, p, g, 3, dtype=torch.int64, device=dev)
     e = torch.empty(n, p, g, dtype=torch.float64, device=dev)
     if n * p * g:
-        ws = _workspace(_lib.pvs_vsd_workspace_bytes(n, p, g, H, W, COSTS[cost]), dev)
-        with torch.cuda.device(dev):
-            rc = _lib.pvs_vsd_batched(depth_est.data_ptr(), depth_gt.data_ptr(), dt.data_ptr(), kind, float(depth_scale),
-                                      Km.data_ptr(), int(Km.dim() == 3), float(delta), float(tau), COSTS[cost],
-                                      counts.data_ptr(), e.data_ptr(), ws.data_ptr(), n, p, g, H, W,
-                                      torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            raise RuntimeError("pvs_vsd_batched failed (%d)" % rc)
+        ws = _native.workspace(_lib.pvs_vsd_workspace_bytes(n, p, g, H, W, COSTS[cost]), dev)
+        _native.call(_lib, "pvs_vsd_batched", dev, depth_est.data_ptr(), depth_gt.data_ptr(), dt.data_ptr(), kind,
+                     float(depth_scale), Km.data_ptr(), int(Km.dim() == 3), float(delta), float(tau), COSTS[cost],
+                     counts.data_ptr(), e.data_ptr(), ws.data_ptr(), n, p, g, H, W)
     if gt_valid is not None:
         e = torch.where((gt_valid != 0)[:, None, :], e, torch.full_like(e, float("nan")))
     if return_images:

@@ -29,3 +29,21 @@ def _register_clean_pvnet_amd():
         del sys.modules["clean_pvnet_amd"]
         raise
     return mod
+
+
+def load_build():
+    """``clean-pvnet_amd/_build.py`` as a module (its directory name is not importable)."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("_pvnet_vote_build", os.path.join(root, "clean-pvnet_amd", "_build.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def build_in_place(*names):
+    """What the ``setup.py build_ext --inplace`` entry points under ``lib/csrc/`` run: the named rows of the build table
+    (``"ext"`` is the host shim ``ransac_voting.so``), in place, next to the package."""
+    b = load_build()
+    for name in names:
+        path = b.build_ext(verbose=True) if name == "ext" else b.build_hip(name, verbose=True)
+        print("built", os.path.relpath(path, b.ROOT))

@@ -434,3 +434,63 @@ def test_stage_hint_thresholds_and_no_data_without_a_gpu():
     mean, t = ctypes.c_float(7.0), ctypes.c_float(7.0)
     L.pvv_stage_hint_query(ctypes.byref(mean), ctypes.byref(t), None, None)
     assert t.value == -1.0
+
+
+def _load_file(name, *path):
+    from importlib import util
+    spec = util.spec_from_file_location(name, os.path.join(*path))
+    mod = util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_native_loader_refuses_a_library_that_is_not_built():
+    """_native.load is the one place a ctypes-bound library is opened: a missing one is an ImportError that names the module
+    and the library, says how to build it and that nothing stands in for it.  The module itself needs no torch."""
+    native = _load_file("_native_alone", ROOT, "clean-pvnet_amd", "_native.py")
+    with pytest.raises(ImportError) as ei:
+        native.load("nowhere", "libpvnet_nowhere.so", {})
+    msg = str(ei.value)
+    assert "clean_pvnet_amd.nowhere: libpvnet_nowhere.so is not built" in msg
+    assert "`python __graft_entry__.py`" in msg and "no CPU fallback" in msg
+    with pytest.raises(RuntimeError, match="x must be a CUDA tensor; there is no CPU fallback"):
+        native.need_cuda(torch.zeros(1), "x", "nowhere")
+
+
+def test_build_table_headers_and_sources_name_the_same_libraries():
+    import glob
+    import re
+    import lib
+    b = lib.load_build()
+    names = lambda pattern, rx: {re.fullmatch(rx, os.path.basename(p)).group(1) for p in glob.glob(pattern)}   # noqa: E731
+    assert set(b.HIP_LIBS) == names(os.path.join(b.INCLUDE, "pvnet_*.h"), r"pvnet_(\w+)\.h")
+    assert set(b.HIP_LIBS) == names(os.path.join(b.CSRC, "pvnet_*.hip"), r"pvnet_(\w+)\.hip")
+    for name, (flags, inc) in b.HIP_LIBS.items():
+        assert b.hip_sources(name)[0].endswith("pvnet_%s.hip" % name) and all(os.path.exists(s) for s in b.hip_sources(name))
+        assert ("-I" + b.CSRC in ["-I" + d for d in inc]) == (name == "vote")
+        assert ("-ffp-contract=off" in flags) == (name not in ("pnp", "pose"))
+
+
+def test_a_shared_header_edit_makes_every_library_that_may_include_it_stale(tmp_path):
+    """Every HIP library depends on all of csrc/*.hpp: a newer eval_common.hpp rebuilds metrics and vsd (a copy of the
+    sources with set mtimes; nothing is compiled and the tree is not touched)."""
+    import shutil
+    pkg = tmp_path / "clean-pvnet_amd"
+    shutil.copytree(os.path.join(ROOT, "clean-pvnet_amd", "csrc"), pkg / "csrc")
+    shutil.copytree(os.path.join(ROOT, "include"), tmp_path / "include")
+    shutil.copy(os.path.join(ROOT, "clean-pvnet_amd", "_build.py"), pkg / "_build.py")
+    b = _load_file("_build_copy", str(pkg), "_build.py")
+    assert b.CSRC == str(pkg / "csrc")
+    t0 = 1.7e9
+    for name in b.HIP_LIBS:
+        for s in b.hip_sources(name):
+            os.utime(s, (t0, t0))
+        open(b.lib_path(name), "wb").close()
+        os.utime(b.lib_path(name), (t0 + 10, t0 + 10))
+    assert all(b._newer(b.lib_path(name), *b.hip_sources(name)) for name in b.HIP_LIBS)
+    os.utime(os.path.join(b.CSRC, "eval_common.hpp"), (t0 + 20, t0 + 20))
+    for name in ("metrics", "vsd"):
+        assert not b._newer(b.lib_path(name), *b.hip_sources(name)), name
+    os.utime(os.path.join(b.CSRC, "eval_common.hpp"), (t0, t0))
+    os.utime(os.path.join(b.INCLUDE, "pvnet_nn.h"), (t0 + 20, t0 + 20))           # an ABI header is its own library's alone
+    assert [name for name in b.HIP_LIBS if not b._newer(b.lib_path(name), *b.hip_sources(name))] == ["nn"]

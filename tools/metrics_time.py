@@ -29,6 +29,7 @@ import torch  # noqa: E402
 import lib  # noqa: E402
 
 lib._register_clean_pvnet_amd()
+from _timing import alternate, summary  # noqa: E402
 from clean_pvnet_amd import metrics  # noqa: E402
 from lib.csrc.nn.nn_utils import find_nearest_point_idx  # noqa: E402
 
@@ -105,22 +106,10 @@ def main():
             forms = {"nn": lambda: nn_form(nn, ref32, que32, idx, B, N)}
         elif a.only:
             forms = {a.only: forms[a.only]}
-        ms = {k: [] for k in forms}
-        for i in range(a.warmup + a.rounds):
-            for name, f in forms.items():                                                  # alternated, same inputs
-                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                torch.cuda.synchronize()
-                s.record()
-                f()
-                e.record()
-                torch.cuda.synchronize()
-                if i >= a.warmup:
-                    ms[name].append(s.elapsed_time(e))
+        ms = alternate(forms, a.rounds, a.warmup)
         res = {"B": B, "N": N, "rounds": a.rounds, "slabs": a.slabs or metrics.adds_slabs(B, N)}
         for name, v in ms.items():
-            v = np.asarray(v)
-            res[name + "_ms"] = {"median": round(float(np.median(v)), 4), "min": round(float(v.min()), 4),
-                                 "max": round(float(v.max()), 4)}
+            res[name + "_ms"] = summary(v, 4)
         if "device" in ms:                                     # a whole-call rate (four launches), not the search kernel's
             res["device_call_evals_per_s"] = float("%.4g" % (B * N * N / (np.median(ms["device"]) * 1e-3)))
         print(json.dumps(res), flush=True)

@@ -27,6 +27,7 @@ import torch  # noqa: E402
 import lib  # noqa: E402
 
 lib._register_clean_pvnet_amd()
+from _timing import alternate, summary  # noqa: E402
 from clean_pvnet_amd.decode import decode_keypoint  # noqa: E402
 from clean_pvnet_amd.pose import solve_pose  # noqa: E402
 from clean_pvnet_amd.un_pnp_utils import initial_pose_dlt, initial_pose_p3p, uncertainty_pnp_batched  # noqa: E402
@@ -96,22 +97,10 @@ def main():
         forms = {"device": lambda i: device_form(x, Pt, Kt, i), "host": lambda i: host_form(x, Pt, Kt, P, i)}
         if a.only:
             forms = {a.only: forms[a.only]}
-        ms = {k: [] for k in forms}
-        for i in range(a.warmup + a.rounds):
-            for name, f in forms.items():                                                  # alternated, same inputs
-                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                torch.cuda.synchronize()
-                s.record()
-                f(i)
-                e.record()
-                torch.cuda.synchronize()
-                if i >= a.warmup:
-                    ms[name].append(s.elapsed_time(e))
+        ms = alternate(forms, a.rounds, a.warmup)
         res = {"B": B, "rounds": a.rounds}
         for name, v in ms.items():
-            v = np.asarray(v)
-            res[name + "_ms"] = {"median": round(float(np.median(v)), 3), "min": round(float(v.min()), 3),
-                                 "max": round(float(v.max()), 3)}
+            res[name + "_ms"] = summary(v, 3)
         print(json.dumps(res), flush=True)
 
 

@@ -31,6 +31,7 @@ import torch  # noqa: E402
 import lib  # noqa: E402
 
 lib._register_clean_pvnet_amd()
+from _timing import alternate, summary  # noqa: E402
 from clean_pvnet_amd import vsd as V  # noqa: E402
 from tests import vsd_twin as twin  # noqa: E402
 
@@ -90,26 +91,13 @@ def main():
                  "host": lambda: host_form(t, K, raw, n, p, g, a.cost)}
         if a.only:
             forms = {a.only: forms[a.only]}
-        ms = {k: [] for k in forms}
-        for i in range(a.warmup + a.rounds):
-            for name, f in forms.items():                                                  # alternated, same inputs
-                if name == "host" and i >= a.warmup + a.host_rounds:                       # seconds per round at 16x2x2
-                    continue
-                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                torch.cuda.synchronize()
-                s.record()
-                f()
-                e.record()
-                torch.cuda.synchronize()
-                if i >= a.warmup:
-                    ms[name].append(s.elapsed_time(e))
+        # the host form only in the first host_rounds timed rounds: seconds per round at 16x2x2
+        ms = alternate(forms, a.rounds, a.warmup, skip=lambda name, i: name == "host" and i >= a.warmup + a.host_rounds)
         res = {"n": n, "p": p, "g": g, "size": list(SIZE), "triangles": int(t["faces"].shape[0]), "renders": n * (p + g),
                "pairs": n * p * g, "cost": a.cost, "rounds": a.rounds, "warmup": a.warmup,
                "host_rounds": min(a.host_rounds, a.rounds)}
         for name, v in ms.items():
-            v = np.asarray(v)
-            res[name + "_ms"] = {"median": round(float(np.median(v)), 4), "min": round(float(v.min()), 4),
-                                 "max": round(float(v.max()), 4)}
+            res[name + "_ms"] = summary(v, 4)
         print(json.dumps(res), flush=True)
         lines.append(res)
     if a.out:
