@@ -39,6 +39,7 @@ HIP_LIBS = {
     "pose": (PNP_FLAGS, [INCLUDE]),           # the batched pose with its start: P3P / DLT + the refinement of pnp (csrc/pnp_lm.hpp)
     "metrics": (HIPCC_FLAGS, [INCLUDE]),      # the batched pose scores: ADD, ADD-S with its search, 2D projection, 5 cm 5 degrees, mask IoU
     "vsd": (HIPCC_FLAGS, [INCLUDE]),          # the batched depth rasteriser and the Visible Surface Discrepancy
+    "icp": (HIPCC_FLAGS, [INCLUDE]),          # the batched ICP pose refinement: clouds, samples, the search and the fit
 }
 
 

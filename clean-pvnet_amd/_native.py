@@ -1,5 +1,6 @@
 """The one loader and the one calling convention of the ctypes-bound native libraries (``libpvnet_nn.so``,
-``libpvnet_pnp.so``, ``libpvnet_pose.so``, ``libpvnet_metrics.so``, ``libpvnet_vsd.so``; ``_build.py`` has the table).
+``libpvnet_pnp.so``, ``libpvnet_pose.so``, ``libpvnet_metrics.so``, ``libpvnet_vsd.so``, ``libpvnet_icp.so``; ``_build.py`` has the
+table).
 
 Every device entry point of these libraries takes the stream as its last argument and returns 0 on success: ``call`` is that
 convention, ``load`` binds a library with its signatures, ``need_cuda`` / ``workspace`` / ``ptr`` are what the wrappers
