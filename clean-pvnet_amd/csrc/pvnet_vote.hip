@@ -1423,3 +1423,6 @@ PVV_EXPORT int pvv_count_inliers(const float *d_direct, const float *d_coords, c
     a.thresh = inlier_thresh;
     return launch_count(a, st);
 }
+
+// ---- detector decode, crops and the way back (ABI v8, additive) --------------------------
+#include "crop.hpp"

@@ -32,7 +32,9 @@ extern "C" {
 #define PVV_E_ARG (-1)       /* bad shape / size / NULL pointer              */
 #define PVV_E_WORKSPACE (-2) /* workspace smaller than pvv_workspace_bytes() */
 
-/* ABI version of this header; pvv_abi_version() must return the same. */
+/* ABI version of this header; pvv_abi_version() must return the same.  (The detector decode, the crops and the way back --
+ * pvv_ct_*, pvv_crop_boxes, pvv_uncrop_* at the end of this header -- were added under v8: nothing that existed changed, so
+ * the version did not; a host asks for them with dlsym.) */
 #define PVV_ABI_VERSION 8
 
 int pvv_abi_version(void);
@@ -359,6 +361,54 @@ int pvv_stage_hint_query(float *mean_ratio, float *threshold, const pvv_problem 
 int pvv_rerun_count_kernel(const pvv_problem *p, void *d_workspace,
                            size_t workspace_bytes, int zero_counts,
                            void *stream);
+
+/* ------------------------------------------------------------------------
+ * Detector decode, crops and the way back (ABI v8, additive): what the detector -> crop -> PVNet caller of the reference
+ * does on the host around the voting layer.  Citations:
+ *   D = lib/utils/ct/ct_decode.py     U = lib/utils/data_utils.py     R = lib/networks/ct_pvnet/res.py
+ *   T = lib/utils/tless/tless_test_utils.py                           E = lib/evaluators/tless_test/pvnet.py
+ * All arithmetic is in the stated order without fused multiply-add; tests/crop_twin.py is the same in numpy, bit for bit.
+ * Parity of the two warps with cv2.warpAffine is unpinned (no OpenCV where this was built): the contract is the product's own.
+ * ---------------------------------------------------------------------- */
+#define PVV_CT_MAX_K 256
+#define PVV_CROP_WORKSPACE_PER_BOX 96 /* bytes of 8-byte aligned device scratch pvv_crop_boxes needs per box */
+
+/* Replaces decode_ct_hm with ae = None (D:52-75: nms D:6-12, the two-level topk D:33-49, the rows D:60-69) followed, when
+ * `clip` is set, by clip_to_image with the heat map's own H, W (U:373-377 as called in lib/networks/ct/dla.py:20-26).
+ *   d_ct_hm     [B,C,H,W] f32, after the sigmoid: finite, >= 0           d_wh  [B,2,H,W] f32
+ *   d_ct        [B,K,2] f32 (x, y)      d_detection [B,K,6] f32 (x0, y0, x1, y1, value, class)      d_count [B] i32
+ * A peak is a pixel not smaller than any of its 8 neighbours inside its class plane; a candidate is a peak > 0; the rows are the
+ * K candidates of an image by descending value, the lower c*H*W + y*W + x first among equals; d_count = min(K, candidates) and
+ * the rows from there on are zeros (the reference's depend on torch.topk's tie order among zeros).  1 <= K <= PVV_CT_MAX_K,
+ * K <= H*W, C*H*W < 2^31.  Three launches whatever the data; the workspace is 256-byte aligned. */
+size_t pvv_ct_workspace_bytes(int B, int C, int H, int W, int K);
+int pvv_ct_decode(const float *d_ct_hm, const float *d_wh, int B, int C, int H, int W, int K, int clip, void *d_workspace,
+                  size_t workspace_bytes, float *d_ct, float *d_detection, int32_t *d_count, void *stream);
+
+/* Replaces _crop / pvnet_transform (R:14-32, T:57-79) for N boxes: centre and scale (R:16-17), the closed form of
+ * get_affine_transform(center, scale, 0, [ow, oh]) (U:123-156), an 8-bit bilinear warp in fixed point with constant border 0
+ * in place of cv2.warpAffine(INTER_LINEAR) (R:23), the box blanking of the test loader when has_box_ratio (magnify_box,
+ * T:49-54, 65-69) and the normalisation to planar float32 (R:25-27).
+ *   d_img [B,H,W,3] u8     d_boxes [N,4] f64 (x0,y0,x1,y1) in image pixels     d_image_index [N] i32
+ *   h_mean, h_std: HOST arrays of 3 floats
+ *   d_inp [N,3,oh,ow] f32  d_center [N,2] f32  d_scale [N] f32  d_trans [N,2,3] f64 (image -> crop)  d_valid [N] u8
+ * A box with a non-finite entry, a float32 scale <= 0 or an image index outside [0, B) is invalid: valid 0, centre, scale
+ * and trans zero, the crop normalised zeros. */
+int pvv_crop_boxes(const uint8_t *d_img, int B, int H, int W, const double *d_boxes, const int32_t *d_image_index, int N, int ow,
+                   int oh, double scale_ratio, int has_box_ratio, double box_ratio, const float *h_mean, const float *h_std,
+                   void *d_workspace, size_t workspace_bytes, float *d_inp, float *d_center, float *d_scale, double *d_trans,
+                   uint8_t *d_valid, void *stream);
+
+/* Replaces affine_transform(kpt_2d, get_affine_transform(..., inv=1)) (E:233-234): d_trans [N,2,3] f64 as pvv_crop_boxes wrote
+ * it is inverted (the operation order of OpenCV's invertAffineTransform; a zero map inverts to zeros) and applied in binary64.
+ *   d_kpt_2d [N,K,2] f32, or f64 when kpt_is_f64        d_out [N,K,2] f64 */
+int pvv_uncrop_keypoints(const void *d_kpt_2d, int kpt_is_f64, const double *d_trans, int N, int K, double *d_out, void *stream);
+
+/* Replaces cv2.warpAffine(seg, trans_inv, (Wc, Hc), INTER_NEAREST) (E:243-245): d_trans (canvas -> crop) is the
+ * destination -> source map, nearest neighbour in fixed point with 10 fractional bits, 0 outside the crop.
+ *   d_mask [N,h,w] of mask_elem_size 1 or 8 bytes (the low byte is read)        d_out [N,Hc,Wc] u8 */
+int pvv_uncrop_mask(const void *d_mask, int mask_elem_size, int h, int w, const double *d_trans, int N, int Hc, int Wc,
+                    uint8_t *d_out, void *stream);
 
 #ifdef __cplusplus
 }

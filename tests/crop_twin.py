@@ -1,0 +1,248 @@
+"""numpy twins of the four contracts of ``clean_pvnet_amd.crop`` (include/pvnet_vote.h, the last section): every operation in
+the order the kernels of clean-pvnet_amd/csrc/crop.hpp perform it, one IEEE rounding each, so that the device must give the
+same bits.  Plus ``bilinear_f64``, a plain binary64 bilinear sampler that the fixed-point warp is held against, the inputs the
+CPU and the GPU tests share, and the regeneration of the heat maps of tests/golden/crop_*.npz from their seeds."""
+import numpy as np
+
+MAX_K = 256
+I32_MIN, I32_MAX = -2147483648, 2147483647
+
+
+# ------------------------------------------------------------------------------------------------------------ decode_ct_hm
+def peaks(hm):
+    """[C,H,W] bool: not smaller than any of the 8 neighbours inside the plane, and > 0."""
+    C, H, W = hm.shape
+    pad = np.full((C, H + 2, W + 2), -np.inf, np.float32)
+    pad[:, 1:-1, 1:-1] = hm
+    keep = hm > 0
+    for dy in range(3):
+        for dx in range(3):
+            keep &= hm >= pad[:, dy:dy + H, dx:dx + W]
+    return keep
+
+
+def keys(hm):
+    """The sorted (descending) unique 64-bit keys of an image's candidates: value bits << 32 | ~flat index."""
+    flat = np.flatnonzero(peaks(hm).ravel()).astype(np.uint64)
+    bits = hm.ravel()[flat.astype(np.int64)].view(np.uint32).astype(np.uint64)
+    k = (bits << np.uint64(32)) | (~flat & np.uint64(0xffffffff))
+    return np.sort(k)[::-1]
+
+
+def decode_ct_hm(ct_hm, wh, K=100, clip=True):
+    ct_hm, wh = np.ascontiguousarray(ct_hm, np.float32), np.ascontiguousarray(wh, np.float32)
+    B, C, H, W = ct_hm.shape
+    if not 1 <= K <= MAX_K or K > H * W:
+        raise ValueError("K must lie in [1, min(%d, H*W = %d)], got %d" % (MAX_K, H * W, K))
+    ct, det, count = np.zeros((B, K, 2), np.float32), np.zeros((B, K, 6), np.float32), np.zeros(B, np.int32)
+    two = np.float32(2)
+    for b in range(B):
+        k = keys(ct_hm[b])[:K]
+        n = len(k)
+        count[b] = n
+        flat = (~k & np.uint64(0xffffffff)).astype(np.int64)
+        value = (k >> np.uint64(32)).astype(np.uint32).view(np.float32)
+        cls, rem = flat // (H * W), flat % (H * W)
+        y, x = rem // W, rem % W
+        w, h = wh[b, 0, y, x], wh[b, 1, y, x]
+        xf, yf = x.astype(np.float32), y.astype(np.float32)
+        row = np.stack([xf - w / two, yf - h / two, xf + w / two, yf + h / two, value, cls.astype(np.float32)], 1).astype(np.float32)
+        if clip:
+            row[:, 0] = np.where(row[:, 0] < 0, np.float32(0), row[:, 0])
+            row[:, 1] = np.where(row[:, 1] < 0, np.float32(0), row[:, 1])
+            row[:, 2] = np.where(row[:, 2] > np.float32(W - 1), np.float32(W - 1), row[:, 2])
+            row[:, 3] = np.where(row[:, 3] > np.float32(H - 1), np.float32(H - 1), row[:, 3])
+        det[b, :n] = row
+        ct[b, :n] = np.stack([xf, yf], 1)
+    return ct, det, count
+
+
+def heat_maps(seed, shape):
+    """The seeded inputs of a fixture: ct_hm [B,C,H,W] in [0, 1) and wh [B,2,H,W] in [0, 16) -- no transcendental function, so
+    every machine draws the same bits."""
+    rng = np.random.default_rng(int(seed))
+    B, C, H, W = (int(v) for v in shape)
+    hm = rng.random((B, C, H, W), dtype=np.float32)
+    wh = rng.random((B, 2, H, W), dtype=np.float32) * np.float32(16)
+    return hm, wh
+
+
+def regenerate(c):
+    """(ct_hm, wh) of a fixture: stored, or drawn again from its seed."""
+    if "ct_hm" in c:
+        return c["ct_hm"], c["wh"]
+    return heat_maps(c["seed"], c["shape"])
+
+
+# ------------------------------------------------------------------------------------------------------------ the affine maps
+def sat_rint(v):
+    """rint (half to even), saturated to int32, as int64."""
+    return np.clip(np.rint(np.asarray(v, np.float64)), I32_MIN, I32_MAX).astype(np.int64)
+
+
+def invert_affine(M):
+    """[2,3] -> [2,3] in the operation order of OpenCV's invertAffineTransform; a singular map gives zeros."""
+    M = np.asarray(M, np.float64).ravel()
+    D = M[0] * M[4] - M[1] * M[3]
+    D = np.float64(1.) / D if D != 0 else np.float64(0.)
+    A11, A22, m1, m3 = M[4] * D, M[0] * D, M[1] * (-D), M[3] * (-D)
+    b1 = -A11 * M[2] - m1 * M[5]
+    b2 = -m3 * M[2] - A22 * M[5]
+    return np.array([[A11, m1, b1], [m3, A22, b2]], np.float64)
+
+
+def box_transform(box, out_size, scale_ratio):
+    """(center [2] f32, scale f32, trans [2,3] f64, valid) of one box (x0, y0, x1, y1)."""
+    ow, oh = out_size
+    x0, y0, x1, y1 = (np.float64(v) for v in box)
+    with np.errstate(all="ignore"):
+        cx, cy, bw, bh = (x0 + x1) / np.float64(2), (y0 + y1) / np.float64(2), x1 - x0, y1 - y0
+        s = (bh if bh > bw else bw) * np.float64(scale_ratio)
+        cxf, cyf, sf = np.float32(cx), np.float32(cy), np.float32(s)
+    valid = bool(np.isfinite([x0, y0, x1, y1]).all() and np.isfinite([cxf, cyf, sf]).all() and sf > 0)
+    if not valid:
+        return np.zeros(2, np.float32), np.float32(0), np.zeros((2, 3)), False
+    a = np.float64(ow) / np.float64(sf)
+    trans = np.array([[a, 0., ow * 0.5 - a * np.float64(cxf)], [0., a, oh * 0.5 - a * np.float64(cyf)]], np.float64)
+    return np.array([cxf, cyf], np.float32), sf, trans, True
+
+
+def blank_rect(box, trans, out_size, box_ratio):
+    """The inclusive rectangle (x0, y0, x1, y1) magnify_box keeps (tless_test_utils.py:49-54, 65-69)."""
+    ow, oh = out_size
+    a, t0, t1 = trans[0, 0], trans[0, 2], trans[1, 2]
+    x0, y0, x1, y1 = (np.float64(v) for v in box)
+    px0, py0, px1, py1 = x0 * a + t0, y0 * a + t1, x1 * a + t0, y1 * a + t1
+    mx, my = (px0 + px1) / np.float64(2), (py0 + py1) / np.float64(2)
+    r = np.float64(box_ratio)
+    c = sat_rint([(px0 - mx) * r + mx, (py0 - my) * r + my, (px1 - mx) * r + mx, (py1 - my) * r + my])
+    return (int(np.clip(c[0], 0, ow - 1)), int(np.clip(c[1], 0, oh - 1)), int(np.clip(c[2], 0, ow - 1)), int(np.clip(c[3], 0, oh - 1)))
+
+
+def _tap(img, sy, sx):
+    H, W = img.shape[:2]
+    ok = (sy >= 0) & (sy < H) & (sx >= 0) & (sx < W)
+    v = img[np.clip(sy, 0, H - 1), np.clip(sx, 0, W - 1)].astype(np.int64)
+    return np.where(ok[..., None], v, 0)
+
+
+def warp_u8(img, trans, out_size):
+    """[H,W,3] uint8 -> [oh,ow,3] uint8: the 8-bit bilinear warp in fixed point, constant border 0."""
+    ow, oh = out_size
+    I = invert_affine(trans)
+    y, x = np.arange(oh, dtype=np.float64)[:, None], np.arange(ow, dtype=np.float64)[None, :]
+    X0, Y0 = sat_rint((I[0, 1] * y + I[0, 2]) * 1024.) + 16, sat_rint((I[1, 1] * y + I[1, 2]) * 1024.) + 16
+    X, Y = (X0 + sat_rint(I[0, 0] * x * 1024.)) >> 5, (Y0 + sat_rint(I[1, 0] * x * 1024.)) >> 5
+    sx, sy, a, b = X >> 5, Y >> 5, (X & 31)[..., None], (Y & 31)[..., None]
+    acc = (_tap(img, sy, sx) * ((32 - a) * (32 - b) * 32) + _tap(img, sy, sx + 1) * (a * (32 - b) * 32)
+           + _tap(img, sy + 1, sx) * ((32 - a) * b * 32) + _tap(img, sy + 1, sx + 1) * (a * b * 32) + 16384) >> 15
+    return acc.astype(np.uint8)
+
+
+def normalise(u8, mean, std):
+    """[oh,ow,3] uint8 -> [3,oh,ow] float32."""
+    m, s = np.asarray(mean, np.float32), np.asarray(std, np.float32)
+    return np.ascontiguousarray(((u8.astype(np.float32) / np.float32(255) - m) / s).transpose(2, 0, 1))
+
+
+def crop_boxes(img, boxes, image_index, out_size, *, scale_ratio, box_ratio=None, mean, std):
+    img, boxes = np.asarray(img), np.asarray(boxes)
+    N, (ow, oh) = len(boxes), out_size
+    out = {"inp": np.zeros((N, 3, oh, ow), np.float32), "center": np.zeros((N, 2), np.float32), "scale": np.zeros(N, np.float32),
+           "trans": np.zeros((N, 2, 3)), "valid": np.zeros(N, bool), "u8": np.zeros((N, oh, ow, 3), np.uint8)}
+    for n in range(N):
+        center, scale, trans, valid = box_transform(boxes[n], out_size, scale_ratio)
+        if valid and 0 <= int(image_index[n]) < len(img):
+            out["center"][n], out["scale"][n], out["trans"][n], out["valid"][n] = center, scale, trans, True
+            u8 = warp_u8(img[int(image_index[n])], trans, out_size)
+            if box_ratio is not None:
+                x0, y0, x1, y1 = blank_rect(boxes[n], trans, out_size, box_ratio)
+                kept = np.zeros_like(u8)
+                kept[y0:y1 + 1, x0:x1 + 1] = u8[y0:y1 + 1, x0:x1 + 1]
+                u8 = kept
+            out["u8"][n] = u8
+        out["inp"][n] = normalise(out["u8"][n], mean, std)
+    return out
+
+
+def uncrop_keypoints(kpt_2d, trans):
+    kpt = np.asarray(kpt_2d).astype(np.float64)
+    out = np.zeros(kpt.shape, np.float64)
+    for n in range(len(kpt)):
+        I = invert_affine(trans[n])
+        x, y = kpt[n, :, 0], kpt[n, :, 1]
+        out[n, :, 0] = I[0, 0] * x + I[0, 1] * y + I[0, 2]
+        out[n, :, 1] = I[1, 0] * x + I[1, 1] * y + I[1, 2]
+    return out
+
+
+def uncrop_mask(mask, trans, canvas_size):
+    mask = np.asarray(mask)
+    Wc, Hc = canvas_size
+    N, h, w = mask.shape
+    out = np.zeros((N, Hc, Wc), np.uint8)
+    y, x = np.arange(Hc, dtype=np.float64)[:, None], np.arange(Wc, dtype=np.float64)[None, :]
+    for n in range(N):
+        T = np.asarray(trans[n], np.float64)
+        X = (sat_rint((T[0, 1] * y + T[0, 2]) * 1024.) + 512 + sat_rint(T[0, 0] * x * 1024.)) >> 10
+        Y = (sat_rint((T[1, 1] * y + T[1, 2]) * 1024.) + 512 + sat_rint(T[1, 0] * x * 1024.)) >> 10
+        ok = (X >= 0) & (X < w) & (Y >= 0) & (Y < h)
+        out[n] = np.where(ok, mask[n][np.clip(Y, 0, h - 1), np.clip(X, 0, w - 1)].astype(np.uint8), 0)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------ the sanity sampler
+def bilinear_f64(img, trans, out_size):
+    """[oh,ow,3] float64: plain bilinear interpolation at the exact inverse-mapped position, zero outside the image."""
+    ow, oh = out_size
+    a, t0, t1 = trans[0, 0], trans[0, 2], trans[1, 2]
+    y, x = np.arange(oh, dtype=np.float64)[:, None], np.arange(ow, dtype=np.float64)[None, :]
+    u, v = (x - t0) / a + 0 * y, (y - t1) / a + 0 * x
+    u0, v0 = np.floor(u).astype(np.int64), np.floor(v).astype(np.int64)
+    fu, fv = (u - u0)[..., None], (v - v0)[..., None]
+    f = lambda sy, sx: _tap(img, sy, sx).astype(np.float64)                      # noqa: E731
+    return (f(v0, u0) * (1 - fu) * (1 - fv) + f(v0, u0 + 1) * fu * (1 - fv) + f(v0 + 1, u0) * (1 - fu) * fv + f(v0 + 1, u0 + 1) * fu * fv)
+
+
+def neighbour_difference(img):
+    """The largest difference between horizontally or vertically adjacent pixels, the zero border included."""
+    p = np.pad(np.asarray(img, np.int64), ((1, 1), (1, 1), (0, 0)))
+    return int(max(np.abs(np.diff(p, axis=0)).max(), np.abs(np.diff(p, axis=1)).max()))
+
+
+# ------------------------------------------------------------------------------------------------------------ shared inputs
+MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+SCALE_RATIO, BOX_RATIO = 1.2, 1.2
+# inside; over the top-left corner; over the bottom-right; a sub-pixel box that 32 x 32 magnifies ~3 x; the whole image
+BOXES = np.array([[20.0, 14.0, 50.0, 40.0], [-9.5, -6.25, 18.0, 12.5], [55.0, 38.0, 80.0, 60.0], [30.25, 20.5, 38.75, 29.25],
+                  [0.0, 0.0, 72.0, 54.0]])
+
+
+def image(seed, H=54, W=72):
+    """A smooth ramp with seeded noise and a few hard edges, uint8 [H,W,3]."""
+    rng = np.random.default_rng(seed)
+    y, x = np.mgrid[0:H, 0:W]
+    base = np.stack([(x * 3 + y) % 256, (x + y * 4) % 256, (x * 2 + y * 2) % 256], 2)
+    img = (base + rng.integers(0, 24, (H, W, 3))) % 256
+    img[10:20, 30:44] = 255
+    img[12:18, 33:40] = 0
+    return img.astype(np.uint8)
+
+
+def tie_case():
+    """(ct_hm, wh, K): two classes share the largest value (the lower flat index, class 0, comes first), and a two-pixel plateau
+    inside the top K (its left pixel first)."""
+    hm, wh = np.zeros((1, 2, 8, 8), np.float32), heat_maps(3, (1, 2, 8, 8))[1]
+    hm[0, 1, 5, 5] = hm[0, 0, 2, 2] = 0.9
+    hm[0, 0, 6, 4] = hm[0, 0, 6, 5] = 0.7
+    hm[0, 1, 1, 1] = 0.5
+    hm[0, 0, 0, 7] = 0.25
+    return hm, wh, 5
+
+
+def short_case():
+    """(ct_hm, wh, K): B=3, the first image has 3 candidates (fewer than K), the second none, the third is random."""
+    hm, wh = heat_maps(4, (3, 2, 9, 11))
+    hm[:2] = 0
+    hm[0, 0, 0, 0], hm[0, 1, 8, 10], hm[0, 1, 4, 5] = 0.3, 0.2, 0.1
+    return hm, wh, 6
