@@ -1,4 +1,4 @@
-"""The one loader and the one calling convention of the ctypes-bound native libraries (``libpvnet_vote.so`` for ``crop``, ``libpvnet_nn.so``,
+"""The one loader and the one calling convention of the ctypes-bound native libraries (``libpvnet_vote.so`` for ``crop`` and ``dcn``, ``libpvnet_nn.so``,
 ``libpvnet_pnp.so``, ``libpvnet_pose.so``, ``libpvnet_metrics.so``, ``libpvnet_vsd.so``, ``libpvnet_icp.so``; ``_build.py`` has the
 table).
 

@@ -1426,3 +1426,6 @@ PVV_EXPORT int pvv_count_inliers(const float *d_direct, const float *d_coords, c
 
 // ---- detector decode, crops and the way back (ABI v8, additive) --------------------------
 #include "crop.hpp"
+
+// ---- DCNv2 modulated deformable convolution, forward (ABI v8, additive) -------------------
+#include "dcn.hpp"

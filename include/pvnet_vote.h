@@ -410,6 +410,46 @@ int pvv_uncrop_keypoints(const void *d_kpt_2d, int kpt_is_f64, const double *d_t
 int pvv_uncrop_mask(const void *d_mask, int mask_elem_size, int h, int w, const double *d_trans, int N, int Hc, int Wc,
                     uint8_t *d_out, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Modulated deformable convolution (DCNv2), forward only (ABI v8, additive): the op every DeformConv of the detector
+ * (lib/networks/ct/dla_dcn.py:346-358) runs through lib/networks/dcn_v2.py.  Citations:
+ *   I = lib/csrc/dcn_v2/src/cuda/dcn_v2_im2col_cuda.cu        C = lib/csrc/dcn_v2/src/cuda/dcn_v2_cuda.cu
+ * Replaces dcn_v2_cuda_forward (C:86-163: the bias broadcast C:97-125, modulated_deformable_im2col_cuda C:133-141 and the
+ * batched SGEMM C:143-160) with the column element of I:25-54, 143-189.  Everything is float32:
+ *   d_input [B,C,H,W]   d_weight [M,C,kh,kw]   d_bias [M] or NULL (zeros)   d_out [B,M,Ho,Wo]
+ *   d_offset: image b at d_offset + b * offset_image_stride, [2*dg*kh*kw, Ho, Wo] contiguous
+ *   d_mask:   image b at d_mask   + b * mask_image_stride,   [dg*kh*kw, Ho, Wo] contiguous    (strides in elements, so both
+ *             may be views of one tensor)
+ *   Ho = (H + 2*pad_h - (dil_h*(kh-1)+1)) / stride_h + 1 in integer division, Wo alike; dg >= 1 divides C.
+ *
+ * Columns, in this order and without fused multiply-add.  For output pixel (y, x), channel c of deformable group
+ * g = c / (C/dg) and tap (i, j), t = i*kw + j:
+ *   h = float(y*stride_h - pad_h + i*dil_h) + offset[b, g*2*kh*kw + 2t, y, x]          (I:155, 177)
+ *   w = float(x*stride_w - pad_w + j*dil_w) + offset[b, g*2*kh*kw + 2t + 1, y, x]      (I:156, 178)
+ *   not (h > -1 && w > -1 && h < H && w < W)  =>  val = 0   (a NaN offset too)         (I:176, 180)
+ *   otherwise h0 = floor(h), lh = h - h0, hh = 1 - lh, and w0, lw, hw alike; v1..v4 = input[b, c] at (h0, w0), (h0, w0+1),
+ *   (h0+1, w0), (h0+1, w0+1), each 0 unless its row and column pass h0 >= 0, w0 >= 0, h0+1 <= H-1, w0+1 <= W-1;
+ *   val = (((hh*hw)*v1 + (hh*lw)*v2) + (lh*hw)*v3) + (lh*lw)*v4                        (I:28-52)
+ *   col[k, p] = val * mask[b, g*kh*kw + t, y, x],   k = c*kh*kw + t,   p = y*Wo + x    (I:189)
+ * Output: out[b, o, p] = the float32 fmaf chain over k in ascending order from the bias,
+ *   acc = bias[o];   for k = 0 .. C*kh*kw - 1:  acc = fmaf(weight[o, k], col[k, p], acc)
+ * one rounding per step, no split over k, no second accumulator.  Zero terms (0 * 0) may be added to fill an instruction;
+ * they change at most the sign of a zero, so results compare as bit patterns with -0 mapped to +0.  The reference sums the
+ * same terms in its BLAS's unspecified order.  tests/dcn_twin.py is this contract in numpy, bit for bit.
+ * ---------------------------------------------------------------------- */
+
+/* One fused launch; no column tensor is written.  Per-image element counts must stay below 2^31, B <= 65535. */
+int pvv_dcn_forward(const float *d_input, const float *d_weight, const float *d_bias, const float *d_offset,
+                    long long offset_image_stride, const float *d_mask, long long mask_image_stride, int B, int C, int H, int W,
+                    int M, int kh, int kw, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
+                    int deformable_groups, float *d_out, void *stream);
+
+/* The columns alone, for tests: d_col [B, C*kh*kw, Ho*Wo] (fewer than 2^31 elements), one thread per element through the same
+ * device function as pvv_dcn_forward. */
+int pvv_dcn_columns(const float *d_input, const float *d_offset, long long offset_image_stride, const float *d_mask,
+                    long long mask_image_stride, int B, int C, int H, int W, int kh, int kw, int stride_h, int stride_w, int pad_h,
+                    int pad_w, int dil_h, int dil_w, int deformable_groups, float *d_col, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
