@@ -1429,3 +1429,6 @@ PVV_EXPORT int pvv_count_inliers(const float *d_direct, const float *d_coords, c
 
 // ---- DCNv2 modulated deformable convolution, forward (ABI v8, additive) -------------------
 #include "dcn.hpp"
+
+// ---- model metadata: farthest point sampling, bounds, diameter (ABI v8, additive) ----------
+#include "model.hpp"

@@ -450,6 +450,65 @@ int pvv_dcn_columns(const float *d_input, const float *d_offset, long long offse
                     long long mask_image_stride, int B, int C, int H, int W, int kh, int kw, int stride_h, int stride_w, int pad_h,
                     int pad_w, int dil_h, int dil_w, int deformable_groups, float *d_col, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Model metadata (ABI v8, additive): from a mesh's vertices to what every later stage consumes -- the farthest-point
+ * keypoints (`fps_3d`), the bounding box (`corner_3d`, `center_3d`) and the diameter.  Citations:
+ *   F = lib/csrc/fps/src/farthest_point_sampling.cpp    M = lib/utils/vsd/misc.py:139-154 (calc_pts_diameter)
+ *   H = tools/handle_custom_dataset.py:19-40 (sample_fps_points, get_model_corners), :94 (the centre)
+ * A batch is padded: d_points [B,N,3], cloud b has n_b = d_n[b] points (int32 on the device, each in [1, N]; NULL: every cloud
+ * has N).  The padding is never read.  Device pointers, caller-owned workspace (256-byte aligned, at least what the query
+ * beside each entry point returns), the stream last; nothing is kept between calls.
+ * Limits, refused with PVV_E_ARG beyond them: 1 <= N <= PVV_MODEL_MAX_N, 1 <= B <= PVV_MODEL_MAX_B,
+ * B * T <= 2^22 with T = ceil(N / PVV_MODEL_TILE) (the grids are (T, B)); the diameter also B * T * T <= 2^22 (its grid is
+ * (T, T, B)); 1 <= sn <= 2^20 and B * sn < 2^31.
+ *
+ * FPS (F:40-105, 122-160; float32 throughout, in this order, no fused multiply-add):
+ *   d2(p, q)    = ((p.x-q.x)*(p.x-q.x) + (p.y-q.y)*(p.y-q.y)) + (p.z-q.z)*(p.z-q.z)
+ *   min_dist[i] = FLT_MAX;  chosen[i] = false
+ *   pick()      = the lowest i with chosen[i] false and min_dist[i] maximal if that maximum is > 0, otherwise 0    (F:56-73)
+ *   d_start == NULL (F:122-160): c = (hi + lo) * 0.5f per coordinate, hi / lo the coordinate-wise max / min of the cloud;
+ *                                min_dist[i] = min(d2(p_i, c), FLT_MAX);  cur = pick()
+ *   otherwise (F:76-105):        cur = d_start[b] (int32 on the device, in [0, n_b)), in place of F:93-94's rand() % pn
+ *   repeat sn times:  chosen[cur] = true;  idx[k] = cur
+ *                     if k < sn-1:  for every i not chosen: d = d2(p_i, p_cur); if d < min_dist[i]: min_dist[i] = d
+ *                                   cur = pick()
+ * "otherwise 0" is F:61-62: once every unchosen point coincides with a chosen one, index 0 repeats, chosen before or not, so
+ * sn > n_b is legal.  Inputs are finite; with a non-finite coordinate the indices of that cloud are unspecified but stay in
+ * [0, n_b).  PVV_FPS_ONE_BLOCK (N <= PVV_FPS_ONE_BLOCK_MAX) runs the sn rounds in one launch of one workgroup per cloud;
+ * PVV_FPS_TILED runs one launch per round over (T, B) workgroups; both give the same indices.  PVV_FPS_AUTO takes ONE_BLOCK
+ * where it applies.  No workgroup waits for another in either.
+ *
+ * Diameter (M:139-154): coordinates taken to binary64 exactly (float32 widened), d2 = (dx*dx + dy*dy) + dz*dz in binary64
+ * without fused multiply-add, the result the correctly rounded sqrt of the maximum of d2 over all pairs, a point with itself
+ * included (one point, or all equal: 0.0).  A maximum is exact in any order; for float64 input this is calc_pts_diameter's value
+ * bit for bit.  Bounds (H:27-29): plain minima and maxima, in the type of the points.  tests/model_twin.py is this contract in numpy.
+ * ---------------------------------------------------------------------- */
+#define PVV_FPS_AUTO 0
+#define PVV_FPS_ONE_BLOCK 1
+#define PVV_FPS_TILED 2
+#define PVV_FPS_ONE_BLOCK_MAX 8192 /* the largest N PVV_FPS_ONE_BLOCK takes */
+#define PVV_MODEL_TILE 1024        /* points per workgroup of the tiled kernels */
+#define PVV_MODEL_MAX_N (1 << 20)
+#define PVV_MODEL_MAX_B 65535
+
+/* Host-only.  Bytes pvv_fps needs for these sizes and this path; 0 with pvv_last_error set when they are refused. */
+size_t pvv_fps_workspace_bytes(int B, int N, int sn, int path);
+
+/* d_idx [B,sn] int32.  d_start == NULL: the centre start (farthest_point_sampling_init_center, F:186-204). */
+int pvv_fps(const float *d_points, const int *d_n, const int *d_start, int B, int N, int sn, int path, void *workspace,
+            size_t workspace_bytes, int *d_idx, void *stream);
+
+/* Host-only.  Bytes pvv_model_bounds and pvv_model_diameter need; 0 with pvv_last_error set when the sizes are refused. */
+size_t pvv_model_workspace_bytes(int B, int N);
+
+/* d_points [B,N,3] float32, or float64 when is_f64; d_lo, d_hi [B,3] of the same type. */
+int pvv_model_bounds(const void *d_points, int is_f64, const int *d_n, int B, int N, void *workspace, size_t workspace_bytes,
+                     void *d_lo, void *d_hi, void *stream);
+
+/* d_out [B] float64. */
+int pvv_model_diameter(const void *d_points, int is_f64, const int *d_n, int B, int N, void *workspace, size_t workspace_bytes,
+                       double *d_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
