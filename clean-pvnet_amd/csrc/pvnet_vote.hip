@@ -1432,3 +1432,6 @@ PVV_EXPORT int pvv_count_inliers(const float *d_direct, const float *d_coords, c
 
 // ---- model metadata: farthest point sampling, bounds, diameter (ABI v8, additive) ----------
 #include "model.hpp"
+
+// ---- training: vote targets and the PVNet loss, forward and backward (ABI v8, additive) -----
+#include "train.hpp"

@@ -1,0 +1,201 @@
+"""PVNet's vote targets and training loss on the device (``libpvnet_vote.so``, the last section of include/pvnet_vote.h).
+
+The reference builds the target field on a CPU core per sample (``compute_vertex``, lib/utils/pvnet/pvnet_data_utils.py:30-44,
+called at lib/datasets/*/pvnet.py:53: 22 MB per 480x640 image at K = 9, then copied to the device) and computes the loss in
+torch ops with autograd (``NetworkWrapper.forward``, lib/train/trainers/pvnet.py:25-34).  Here ``compute_vertex`` is one
+launch for a batch, and ``pvnet_loss`` is fused: the forward pass reads the network output once, the backward pass reads it
+once and writes the gradient once, and with ``kpt_2d`` the target field never exists -- it is recomputed per pixel from the
+mask and the keypoints.  The target equals the reference's bit for bit, the vote loss's gradient equals torch's CPU autograd
+bit for bit, every sum is binary64 in a fixed order (tests/train_twin.py is the contract in numpy, tests/golden/train_*.npz
+the reference's own results).  CUDA float32 tensors, the current stream, nothing read back, no CPU fallback.
+"""
+import ctypes
+
+import torch
+from torch import nn
+from torch.autograd.function import once_differentiable
+
+from . import _native
+from ._native import INT, LONGLONG, PTR, SIZE
+
+MAX_K, MAX_C = 64, 16                # PVV_TRAIN_MAX_K, PVV_TRAIN_MAX_C
+MASK_KINDS = {torch.uint8: 0, torch.bool: 0, torch.int32: 1, torch.int64: 2}     # PVV_MASK_U8, PVV_MASK_I32, PVV_MASK_I64
+
+_INPUTS = [PTR, LONGLONG, PTR, LONGLONG, PTR, INT, PTR, INT, PTR, LONGLONG] + [INT] * 5
+_lib = _native.load("train", "libpvnet_vote.so", {
+    "pvv_last_error": (ctypes.c_char_p, []),
+    "pvv_vertex_target": (INT, [PTR, INT, PTR, INT, INT, INT, INT, INT, PTR, PTR]),
+    "pvv_pvnet_loss_workspace_bytes": (SIZE, [INT] * 3),
+    "pvv_pvnet_loss_forward": (INT, _INPUTS + [PTR, SIZE, PTR, PTR, PTR]),
+    "pvv_pvnet_loss_backward": (INT, _INPUTS + [PTR, PTR, PTR, PTR, PTR]),
+})
+
+
+def _call(symbol, dev, *args):
+    try:
+        _native.call(_lib, symbol, dev, *args)
+    except RuntimeError as e:
+        raise RuntimeError("clean_pvnet_amd.train: %s: %s" % (e, _lib.pvv_last_error().decode())) from None
+
+
+def _check(named, mask, kpt_2d):
+    """Device, then dtype, of every tensor; shapes come after."""
+    for what, t in named + [("mask", mask)] + ([("kpt_2d", kpt_2d)] if kpt_2d is not None else []):
+        _native.need_cuda(t, what, "train")
+    for what, t in named:
+        if t.dtype != torch.float32:
+            raise RuntimeError("clean_pvnet_amd.train: %s must be float32, got %s" % (what, t.dtype))
+    if mask.dtype not in MASK_KINDS:
+        raise RuntimeError("clean_pvnet_amd.train: mask must be uint8, bool, int32 or int64, got %s" % mask.dtype)
+    if kpt_2d is not None and kpt_2d.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError("clean_pvnet_amd.train: kpt_2d must be float32 or float64, got %s" % kpt_2d.dtype)
+
+
+def _mask_kpt_shapes(mask, kpt_2d):
+    if mask.dim() != 3:
+        raise ValueError("clean_pvnet_amd.train: mask must be [B, H, W], got %s" % (tuple(mask.shape),))
+    B, H, W = mask.shape
+    if kpt_2d is not None and (kpt_2d.dim() != 3 or kpt_2d.shape[0] != B or kpt_2d.shape[2] != 2):
+        raise ValueError("clean_pvnet_amd.train: kpt_2d must be [B = %d, K, 2], got %s" % (B, tuple(kpt_2d.shape)))
+    return B, H, W
+
+
+def _per_image(t, what, channels, H, W):
+    """``t`` [B, channels, H, W] as (tensor, element stride between images): a view whose images are contiguous -- a channel
+    slice of the network's output -- is taken as it is, by its stride."""
+    image = channels * H * W
+    if not t[:1].is_contiguous() or (t.shape[0] > 1 and t.stride(0) < image):
+        t = t.contiguous()
+    return t, (t.stride(0) if t.shape[0] > 1 else image)
+
+
+def compute_vertex(mask, kpt_2d):
+    """The reference's ``compute_vertex`` (pvnet_data_utils.py:30-44) for a batch, as its loader stores it (``transpose(2, 0, 1)``).
+    :param mask:    [B,H,W] uint8, bool, int32 or int64 CUDA tensor; the pixels with ``mask == 1`` get a target
+    :param kpt_2d:  [B,K,2] float32 or float64, (x, y)
+    :return:        [B,2K,H,W] float32: channel 2k the x and 2k+1 the y component of the unit vector to keypoint k, +0 elsewhere
+    ``mask`` [H,W] with ``kpt_2d`` [K,2] gives [2K,H,W]."""
+    _check([], mask, kpt_2d)
+    single = mask.dim() == 2 and kpt_2d.dim() == 2
+    m, kp = (mask[None], kpt_2d[None]) if single else (mask, kpt_2d)
+    B, H, W = _mask_kpt_shapes(m, kp)
+    K = kp.shape[1]
+    m, kp = m.contiguous(), kp.detach().contiguous()
+    out = torch.empty(B, 2 * K, H, W, dtype=torch.float32, device=m.device)
+    if out.numel() == 0:
+        return out[0] if single else out
+    _call("pvv_vertex_target", m.device, m.data_ptr(), MASK_KINDS[m.dtype], kp.data_ptr(), int(kp.dtype == torch.float64), B, K, H, W,
+          out.data_ptr())
+    return out[0] if single else out
+
+
+def _problem(vertex_pred, seg_pred, mask, kpt_2d, vertex):
+    """The checked arguments of both entry points: (tensors kept alive, the leading ctypes arguments, sizes)."""
+    if (kpt_2d is None) == (vertex is None):
+        raise ValueError("clean_pvnet_amd.train: exactly one of kpt_2d and vertex must be given")
+    named = [("vertex_pred", vertex_pred), ("seg_pred", seg_pred)] + ([("vertex", vertex)] if vertex is not None else [])
+    _check(named, mask, kpt_2d)
+    for what, t in [("vertex", vertex), ("kpt_2d", kpt_2d)]:
+        if t is not None and t.requires_grad:
+            raise RuntimeError("clean_pvnet_amd.train: %s requires grad; gradients go to vertex_pred and seg_pred only" % what)
+    B, H, W = _mask_kpt_shapes(mask, kpt_2d)
+    if vertex_pred.dim() != 4 or vertex_pred.shape[0] != B or tuple(vertex_pred.shape[2:]) != (H, W) or vertex_pred.shape[1] % 2:
+        raise ValueError("clean_pvnet_amd.train: vertex_pred must be [B = %d, 2K, %d, %d], got %s" % (B, H, W, tuple(vertex_pred.shape)))
+    K = vertex_pred.shape[1] // 2
+    if seg_pred.dim() != 4 or seg_pred.shape[0] != B or tuple(seg_pred.shape[2:]) != (H, W):
+        raise ValueError("clean_pvnet_amd.train: seg_pred must be [B = %d, C, %d, %d], got %s" % (B, H, W, tuple(seg_pred.shape)))
+    C = seg_pred.shape[1]
+    if kpt_2d is not None and kpt_2d.shape[1] != K:
+        raise ValueError("clean_pvnet_amd.train: kpt_2d has %d keypoints, vertex_pred %d" % (kpt_2d.shape[1], K))
+    if vertex is not None and tuple(vertex.shape) != (B, 2 * K, H, W):
+        raise ValueError("clean_pvnet_amd.train: vertex must be [%d, %d, %d, %d], got %s" % (B, 2 * K, H, W, tuple(vertex.shape)))
+    if not 1 <= K <= MAX_K or not 1 <= C <= MAX_C:
+        raise ValueError("clean_pvnet_amd.train: K must lie in [1, %d] and C in [1, %d], got K = %d, C = %d" % (MAX_K, MAX_C, K, C))
+    if B == 0 or H * W == 0:
+        raise ValueError("clean_pvnet_amd.train: an empty batch has no loss")
+    vp, vp_stride = _per_image(vertex_pred.detach(), "vertex_pred", 2 * K, H, W)
+    sp, sp_stride = _per_image(seg_pred.detach(), "seg_pred", C, H, W)
+    tg, tg_stride = (None, 0) if vertex is None else _per_image(vertex, "vertex", 2 * K, H, W)
+    m = mask.contiguous()
+    kp = None if kpt_2d is None else kpt_2d.contiguous()
+    args = (vp.data_ptr(), vp_stride, sp.data_ptr(), sp_stride, m.data_ptr(), MASK_KINDS[m.dtype], _native.ptr(kp),
+            int(kp is not None and kp.dtype == torch.float64), _native.ptr(tg), tg_stride, B, K, C, H, W)
+    return (vp, sp, m, kp, tg), args, (B, K, C, H, W)
+
+
+class _PVNetLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, vertex_pred, seg_pred, mask, kpt_2d, vertex):
+        keep, args, (B, K, C, H, W) = _problem(vertex_pred, seg_pred, mask, kpt_2d, vertex)
+        dev = vertex_pred.device
+        nbytes = _lib.pvv_pvnet_loss_workspace_bytes(B, H, W)
+        if nbytes == 0:
+            raise ValueError("clean_pvnet_amd.train: %s" % _lib.pvv_last_error().decode())
+        ws = _native.workspace(nbytes, dev)
+        losses = torch.empty(2, dtype=torch.float32, device=dev)
+        state = torch.empty(2, dtype=torch.int64, device=dev)
+        _call("pvv_pvnet_loss_forward", dev, *args, ws.data_ptr(), nbytes, losses.data_ptr(), state.data_ptr())
+        ctx.keep, ctx.args, ctx.sizes, ctx.state = keep, args, (B, K, C, H, W), state
+        return losses[0], losses[1]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, go_vote, go_seg):
+        B, K, C, H, W = ctx.sizes
+        dev = ctx.state.device
+        zero = None
+        if go_vote is None or go_seg is None:                      # an unused loss: its upstream gradient counts as zero
+            zero = torch.zeros((), dtype=torch.float32, device=dev)
+        go = torch.stack([zero if go_vote is None else go_vote.to(torch.float32), zero if go_seg is None else go_seg.to(torch.float32)])
+        grad_vertex = torch.empty(B, 2 * K, H, W, dtype=torch.float32, device=dev)
+        grad_seg = torch.empty(B, C, H, W, dtype=torch.float32, device=dev)
+        _call("pvv_pvnet_loss_backward", dev, *ctx.args, ctx.state.data_ptr(), go.data_ptr(), grad_vertex.data_ptr(), grad_seg.data_ptr())
+        return grad_vertex, grad_seg, None, None, None
+
+
+def pvnet_loss(vertex_pred, seg_pred, mask, *, kpt_2d=None, vertex=None):
+    """The two losses of the reference's ``NetworkWrapper.forward`` (lib/train/trainers/pvnet.py:25-34), fused.
+    :param vertex_pred: [B,2K,H,W] float32 CUDA tensor, ``output['vertex']``; a channel slice of a larger tensor is read in place
+    :param seg_pred:    [B,C,H,W] float32, ``output['seg']``; likewise
+    :param mask:        [B,H,W] uint8, bool, int32 or int64: the vote weight and the segmentation label
+    :param kpt_2d:      [B,K,2] float32 or float64 -- the target is recomputed per pixel, no field exists -- or
+    :param vertex:      [B,2K,H,W] float32, ``batch['vertex']``; exactly one of the two
+    :return:            (vote_loss, seg_loss), 0-dim float32 tensors on the device
+    Gradients go to ``vertex_pred`` and ``seg_pred`` only, once (no double backward).  A label outside [0, C) makes both
+    losses and both gradients NaN instead of faulting; the contract is in include/pvnet_vote.h."""
+    return _PVNetLoss.apply(vertex_pred, seg_pred, mask, kpt_2d, vertex)
+
+
+class PVNetLoss(nn.Module):
+    """``pvnet_loss`` as a module: ``forward(vertex_pred, seg_pred, mask, kpt_2d=None, vertex=None) -> (vote_loss, seg_loss)``."""
+
+    def forward(self, vertex_pred, seg_pred, mask, kpt_2d=None, vertex=None):
+        return pvnet_loss(vertex_pred, seg_pred, mask, kpt_2d=kpt_2d, vertex=vertex)
+
+
+class NetworkWrapper(nn.Module):
+    """The reference's ``NetworkWrapper`` (lib/train/trainers/pvnet.py:6-39) over the fused loss: the same ``forward(batch)``
+    contract and the same keys.  The target is ``batch['vertex']`` when the loader still ships it, otherwise it is
+    recomputed from ``batch['kpt_2d']`` [B,K,2]."""
+
+    def __init__(self, net):
+        super().__init__()
+        self.net = net
+        self.crit = PVNetLoss()
+
+    def forward(self, batch):
+        output = self.net(batch['inp'])
+
+        if 'pose_test' in batch['meta'].keys():
+            loss = torch.tensor(0).to(batch['inp'].device)
+            return output, loss, {}, {}
+
+        if 'vertex' in batch:
+            vote_loss, seg_loss = self.crit(output['vertex'], output['seg'], batch['mask'], vertex=batch['vertex'])
+        else:
+            vote_loss, seg_loss = self.crit(output['vertex'], output['seg'], batch['mask'], kpt_2d=batch['kpt_2d'])
+        loss = vote_loss + seg_loss
+        scalar_stats = {'vote_loss': vote_loss, 'seg_loss': seg_loss, 'loss': loss}
+        image_stats = {}
+
+        return output, loss, scalar_stats, image_stats

@@ -509,6 +509,91 @@ int pvv_model_bounds(const void *d_points, int is_f64, const int *d_n, int B, in
 int pvv_model_diameter(const void *d_points, int is_f64, const int *d_n, int B, int N, void *workspace, size_t workspace_bytes,
                        double *d_out, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Training: vote targets and the PVNet loss (ABI v8, additive).  Citations:
+ *   D = lib/utils/pvnet/pvnet_data_utils.py:30-44 (compute_vertex, called per sample at lib/datasets/<dataset>/pvnet.py:53)
+ *   T = lib/train/trainers/pvnet.py:25-34 (NetworkWrapper.forward: the vote loss and the cross entropy)
+ *   N = lib/networks/pvnet/resnet18.py:93-94 (seg and vertex are channel slices of one [B, C+2K, H, W] tensor)
+ * Device pointers, caller-owned workspace (256-byte aligned), the caller's stream last; nothing is read back, nothing
+ * synchronises, nothing is allocated and nothing is kept between calls.
+ *   mask        [B,H,W] of PVV_MASK_U8 (uint8, or bool: one byte, 0 or 1), PVV_MASK_I32 or PVV_MASK_I64
+ *   kpt_2d      [B,K,2] (x, y), float32 or binary64 (kpt_is_f64); float32 is widened exactly
+ *   vertex_pred [B,2K,H,W] and seg_pred [B,C,H,W] float32, each image contiguous, images `*_image_stride` elements apart
+ *               (N: channel slices are passed as they lie, without a copy); target likewise, channel 2k = x, 2k+1 = y
+ *   Exactly one of kpt_2d and target is given (the other NULL): with kpt_2d the target is recomputed per pixel, the field
+ *   never exists.  Both forms are the same kernels.
+ * Limits, refused with PVV_E_ARG beyond them: 1 <= B <= 65535, 1 <= K <= PVV_TRAIN_MAX_K, 1 <= C <= PVV_TRAIN_MAX_C,
+ * H*W, 2K*H*W and C*H*W < 2^31, B*H*W < 2^53.
+ *
+ * The arithmetic contract (no fused multiply-add anywhere; tests/train_twin.py is this contract in numpy):
+ *
+ * Target (D:33-41), binary64, for a pixel (x, y) with mask == 1 and keypoint (kx, ky):
+ *   dx = kx - x;  dy = ky - y;  n = sqrt(dx*dx + dy*dy);  if n < 1e-3: n += 1e-3;  target = float32(dx/n), float32(dy/n)
+ * every other pixel: +0.
+ *
+ * Vote loss (T:25-27), per element in float32:  w = float(mask);  d = pred*w - target*w;  z = |d|;
+ *   element = z < 1 ? (0.5f*z)*z : z - 0.5f          (torch's smooth_l1_loss, beta = 1; a non-finite pred gives a non-finite
+ *   loss as in the reference: no pixel is skipped).
+ *
+ * Sums: binary64, in one order that no launch parameter changes.
+ *   pixel  = its elements (vote) in ascending channel, each widened; its one term (seg)
+ *   lane   = PVV_TRAIN_LANE_PIXELS consecutive pixels of the flattened plane, ascending
+ *   tile   = PVV_TRAIN_TILE pixels = 256 lanes: slot j += slot j+s for s = 128, 64, ..., 1; pixels past H*W count as +0
+ *   image  = slot j (of PVV_TRAIN_IMAGE_SLOTS) = the tiles t = j, j+256, ... ascending, then the same slot order
+ *   batch  = ascending b
+ * The mask sum M is an integer (the sum of the mask values), converted once: wsum = float32(M).
+ *   vote_loss = float32(float32(float32(S) / wsum) / float32(2K));  M = 0 gives 0/0 = NaN as in the reference.
+ *
+ * Vote gradient, float32, go_vote the upstream gradient:  s = (go_vote / float32(2K)) / wsum;
+ *   g = (d < -1 ? -s : d > 1 ? s : s*d) * w
+ *
+ * Seg loss (T:31-32, CrossEntropyLoss with mean reduction), binary64 from the float32 logits z_c of a pixel:
+ *   m = max_c z_c (z > m ? z : m from z_0 on);  e_c = exp(z_c - m);  s = sum_c e_c ascending;
+ *   term = (m - z_label) + log(s)                     (both parts >= 0: nothing cancels)
+ *   seg_loss = float32(sum / (B*H*W)), the sum in the order above.
+ * Seg gradient, N = B*H*W, go_seg widened:
+ *   c != label: float32(((go_seg * e_c) / s) / N);   c == label: float32(((-go_seg * r) / s) / N),
+ *   r = the sum of e_c over c != label, ascending -- never p - 1.
+ *
+ * Labels: label = mask value.  A label outside [0, C) is counted in out_state and selects no logit; if the count is not
+ * zero both losses and every gradient element are NaN (the reference asserts on the device here): no fault, no
+ * synchronisation, no silently wrong value.
+ *
+ * out_state: two int64 on the device, {M, the count of labels outside [0, C)}; the backward pass reads it.
+ * ---------------------------------------------------------------------- */
+#define PVV_MASK_U8 0
+#define PVV_MASK_I32 1
+#define PVV_MASK_I64 2
+#define PVV_TRAIN_MAX_K 64
+#define PVV_TRAIN_MAX_C 16
+#define PVV_TRAIN_LANE_PIXELS 4
+#define PVV_TRAIN_TILE 1024
+#define PVV_TRAIN_IMAGE_SLOTS 256
+
+/* D:30-44 for a batch: d_out [B,2K,H,W] float32, what batch['vertex'] holds after the loader's transpose(2, 0, 1)
+ * (lib/datasets/<dataset>/pvnet.py:53).  One launch. */
+int pvv_vertex_target(const void *d_mask, int mask_kind, const void *d_kpt_2d, int kpt_is_f64, int B, int K, int H, int W,
+                      float *d_out, void *stream);
+
+/* Host-only.  Bytes pvv_pvnet_loss_forward needs; 0 with pvv_last_error set when the sizes are refused. */
+size_t pvv_pvnet_loss_workspace_bytes(int B, int H, int W);
+
+/* T:25-34.  d_out_losses [2] float32 = {vote_loss, seg_loss}; d_out_state as above (8-byte aligned).  Three launches: the
+ * tiles, the images, the batch. */
+int pvv_pvnet_loss_forward(const float *d_vertex_pred, long long vp_image_stride, const float *d_seg_pred,
+                           long long sp_image_stride, const void *d_mask, int mask_kind, const void *d_kpt_2d, int kpt_is_f64,
+                           const float *d_target, long long tg_image_stride, int B, int K, int C, int H, int W, void *workspace,
+                           size_t workspace_bytes, float *d_out_losses, void *d_out_state, void *stream);
+
+/* What autograd derives from T:25-34, in one launch: d_grad_vertex [B,2K,H,W] and d_grad_seg [B,C,H,W], contiguous float32,
+ * from the inputs of the forward call, its d_out_state and d_grad_losses [2] float32 on the device = {go_vote, go_seg}.
+ * d and the softmax are recomputed, not saved. */
+int pvv_pvnet_loss_backward(const float *d_vertex_pred, long long vp_image_stride, const float *d_seg_pred,
+                            long long sp_image_stride, const void *d_mask, int mask_kind, const void *d_kpt_2d, int kpt_is_f64,
+                            const float *d_target, long long tg_image_stride, int B, int K, int C, int H, int W,
+                            const void *d_out_state, const float *d_grad_losses, float *d_grad_vertex, float *d_grad_seg,
+                            void *stream);
+
 #ifdef __cplusplus
 }
 #endif
