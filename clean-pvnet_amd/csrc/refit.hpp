@@ -125,7 +125,7 @@ __global__ __launch_bounds__(kBlock) void k_select_refit(
 // Merge the partial normal equations, solve the 2x2 systems (P:193, closed form in binary64) and apply the
 // singular-matrix policy across the keypoints of an image (b_inv, P:97-109).  One block per image.
 // Also reports the image's mean winner ratio (winner count / tn over its keypoints; -1: image skipped) to hint[b] and its
-// tn to hint[hint_stride + b] -- host-visible memory the NEXT calls read to decide whether staged counting pays (stage_hint_allows, pvnet_vote.hip);
+// tn to hint[hint_stride + b] -- host-visible memory the NEXT calls read to decide whether staged counting pays (stage_hint_allows, host_stage.hpp);
 // hint may be null.
 __global__ __launch_bounds__(64) void k_finalize_v3(const int *__restrict__ tn_arr, const double *__restrict__ sums,
                                                     float2 *__restrict__ out, int K, int policy, int nsplit,

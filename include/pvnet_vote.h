@@ -336,7 +336,7 @@ int pvv_stream_read_probe(const void *d_buf, size_t bytes, uint32_t *d_sink, voi
  * inlier ratio, which nobody knows before the call -- but consecutive calls see similar data, and every v3 call ends with
  * the exact winner counts.  The library therefore keeps, per device, the mean winner ratio (winner count / tn) of every
  * image of the last completed v3 calls in a small pinned array the GPU writes, and PVV_COUNT_AUTO stages a call only if
- * that mean reaches a threshold that depends on the problem's size (pvnet_vote.hip, stage_hint_threshold; DESIGN.md
+ * that mean reaches a threshold that depends on the problem's size (host_stage.hpp, stage_hint_threshold; DESIGN.md
  * 4.6-4.7).  The same array carries every image's tn, so the size that decides is the call's real work -- K * hn * sum(tn)
  * evaluations as the last call of this shape reported them (dense detector crops stage at a batch size where sparse full
  * frames do not; "shape" = H, W, K, hn: the batch size may change from call to call, the sums are scaled to it) -- and

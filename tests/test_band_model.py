@@ -1,7 +1,7 @@
 """CPU model of the guard bands: numpy emulations of the two fast inlier tests on adversarial
 samples concentrated around the threshold.  Claim checked: whenever the fast path says "outside the band"
 (|t| - beta*a > eps) its decision sign(t) equals the exact binary32 decision of ransac_voting_kernel.cu:100-125.
-The constants are computed exactly as clean-pvnet_amd/csrc/pvnet_vote.hip does (fast_consts / bf16_consts)."""
+The constants are computed exactly as clean-pvnet_amd/csrc/host_count.hpp does (fast_consts / bf16_consts)."""
 import numpy as np
 import pytest
 

@@ -2,7 +2,7 @@
 """AUTO's regret on STRUCTURED errors: time(AUTO) / min(time(FULL), time(STAGED)) per case.
 
 AUTO picks between the full count pass and the staged one from the winners' inlier ratios the LAST calls of the shape left
-in the stage hint, against a break-even table that was measured on uniform random-direction outliers (pvnet_vote.hip:
+in the stage hint, against a break-even table that was measured on uniform random-direction outliers (host_stage.hpp:
 stage_hint_threshold).  Real fields fail differently: a contiguous part of the object voting for a wrong point, keypoints
 of very different quality within one image, dense detector crops with both.  Per case: whole calls (HIP events around
 groups of calls, rotating batches, the hint warmed by the case's own calls first), the three modes interleaved in one
