@@ -461,3 +461,6 @@ PVV_EXPORT int pvv_count_inliers(const float *d_direct, const float *d_coords, c
 
 // ---- training: vote targets and the PVNet loss, forward and backward (ABI v8, additive) -----
 #include "train.hpp"
+
+// ---- detector training: heat-map targets and the detector loss, forward and backward (ABI v8, additive) -----
+#include "ct_train.hpp"

@@ -510,6 +510,97 @@ int pvv_model_diameter(const void *d_points, int is_f64, const int *d_n, int B, 
                        double *d_out, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Detector training: heat-map targets and the detector loss (ABI v8, additive).  Citations:
+ *   P = lib/datasets/tless_train/ct.py:46-66 (prepare_detection, called per object at :86-95)
+ *   G = lib/utils/data_utils.py:10-65 (gaussian_radius :10-33, gaussian2D :36-47, draw_umich_gaussian :50-65)
+ *   K = lib/datasets/collate_batch.py:6-32 (ct_collator)
+ *   T = lib/train/trainers/ct.py:14-31 (NetworkWrapper.forward)
+ *   L = lib/utils/net_utils.py:9-49 (sigmoid, _neg_loss, FocalLoss), :195-246 (_tranpose_and_gather_feat, IndL1Loss1d)
+ * Device pointers, caller-owned workspace (256-byte aligned), the caller's stream last; nothing is read back, nothing
+ * synchronises, nothing is allocated and nothing is kept between calls.  No fused multiply-add anywhere;
+ * tests/ct_train_twin.py is this contract in numpy.
+ * Limits, refused with PVV_E_ARG beyond them: 1 <= B <= 65535, 1 <= N <= PVV_CT_TRAIN_MAX_N, C, H, W >= 1, C*H*W and 2*H*W < 2^31.
+ *
+ * Targets (P, G, K), binary64, the reference's operations in its order.  boxes [B,N,4] = (x_min, y_min, x_max, y_max) on the
+ * output map, PVV_BOX_F32 / PVV_BOX_I32 / PVV_BOX_I64, widened exactly; cls [B,N] and num [B] int32 or int64.  Object n of
+ * image b exists when n < num[b] (num is clamped to [0, N]).  For an object:
+ *   w = x_max - x_min;  h = y_max - y_min
+ *   cx = rint(float32((x_min + x_max) / 2)), cy alike: half to even, as np.round of a float32                        (P:51-52)
+ *   R = gaussian_radius((ceil(h), ceil(w))) (G:10-33, min_overlap = 0.7), every step as written there:
+ *     s = ceil(h) + ceil(w);  a = ceil(w) * ceil(h)
+ *     r1 = (s + sqrt(s*s - 4*((a * (1 - 0.7)) / (1 + 0.7)))) / 2
+ *     r2 = (2*s + sqrt((2*s)*(2*s) - 16*(((1 - 0.7) * ceil(w)) * ceil(h)))) / 2
+ *     b3 = (-2*0.7) * s;  d3 = b3*b3 - (4*(4*0.7)) * (((0.7 - 1) * ceil(w)) * ceil(h))
+ *     r3 = d3 < 0 ? min(r1, r2) : (b3 + sqrt(d3)) / 2;   R = min(r1, r2, r3);   r = max(0, int(R))                    (P:55-56)
+ *   sigma = (2r + 1) / 6;  value(dx, dy) = float32(exp(-((dx*dx) / (sigma*sigma) + (dy*dy) / (sigma*sigma)) / 2))     (G:41-45, 52)
+ *   for |dx| <= r, |dy| <= r inside the map (G:58-62); the class plane takes the maximum over its objects (G:64), +0 elsewhere.
+ *   The centre is exp(-0) = 1 exactly.  The rule of G:46 (values below eps * max become 0) is not applied: it never fires.
+ *   wh = (float32(w), float32(h));  ct_ind = cy*W + cx;  ct_cls = cls;  ct_01 = 1                                    (P:59-60, K:18-29)
+ * An object is dropped -- it draws nothing and takes no row -- when w <= 0 or h <= 0 (ct.py:91-92 drops the equalities; a
+ * negative size makes the reference raise), when a coordinate is not finite or not below 2^24 in magnitude, when cls lies
+ * outside [0, C) or (cx, cy) outside the map (the reference's behaviour there is an indexing accident).  The survivors are
+ * packed to the front in their order; rows from ct_num[b] on are zeros.  K pads to the batch's largest ct_num; here the
+ * width is N (zero-weight rows change neither loss).
+ *
+ * Loss (T, L).  hm_pred [B,C,H,W] logits, wh_pred [B,2,H,W], ct_hm [B,C,H,W]: float32, each image contiguous, images
+ * `*_image_stride` elements apart (channel slices of one network output are read in place).  wh [B,N,2] float32, ct_ind [B,N]
+ * int32 or int64, ct_01 [B,N] float32, contiguous.
+ * Focal loss (L:9-11, 21-38), per element in binary64 from the float32 logit z and target g:
+ *   s = 1 / (1 + exp(-z));   p = min(max(s, lo), hi),  lo = float32(1e-4), hi = float32(1 - 1e-4) = 0.99989998...
+ *   g == 1:  pos = log(p) * ((1-p)*(1-p))            g < 1:  neg = (log(1-p) * (p*p)) * (((1-g)*(1-g)) * ((1-g)*(1-g)))
+ *   num_pos = the count of g == 1, an integer;  P, Q = the sums of pos, neg
+ *   ct_loss = float32(num_pos == 0 ? -Q : -(P + Q) / num_pos)
+ * Sums: binary64, in the order of the Training section below over the flattened [C*H*W] image: a lane owns
+ * PVV_TRAIN_LANE_PIXELS consecutive elements, a tile is PVV_TRAIN_TILE elements, PVV_TRAIN_IMAGE_SLOTS slots per image,
+ * then ascending b.  Reruns give the same bits.
+ * Focal gradient, k = num_pos == 0 ? -go_ct : -go_ct / num_pos (go_ct widened):
+ *   g == 1:  dp = ((1-p)*(1-p)) / p - (2*(1-p)) * log(p)
+ *   g < 1:   dp = ((2*p) * log(1-p) - (p*p) / (1-p)) * (((1-g)*(1-g)) * ((1-g)*(1-g)))
+ *   grad = lo <= s <= hi ? float32((k * dp) * ((1-s) * s)) : +0        (the derivative of the sigmoid from the unclamped s)
+ * wh loss (L:240-246), per object n and channel c with i = ct_ind[b,n], m = ct_01[b,n], binary64 from the float32 values:
+ *   d = wh_pred[b,c,i]*m - wh[b,n,c]*m;  z = |d|;  element = z < 1 ? (0.5*z)*z : z - 0.5
+ *   object = element(c = 0) + element(c = 1); image = slot j sums its objects j, j+256, ... ascending, then the slot order
+ *   M = the sum of ct_01 in the same order;   wh_loss = float32(S / (M*2 + 1e-4))
+ * wh gradient, float32 (what torch's CPU autograd computes): den = float32(M)*2 + 1e-4f;  v = go_wh / den;
+ *   d = wh_pred*m - wh*m in float32;  t = (d < -1 ? -v : d > 1 ? v : v*d) * m;  grad[b,c,i] = +0 + the t of the objects with
+ *   ct_ind == i in ascending n, +0 everywhere else.  One thread owns an (image, index): no atomics.
+ * An index outside [0, H*W) is never used as an address.  At a position with ct_01 != 0 it is counted in out_state, and if
+ * the count is not zero wh_loss and every element of the wh gradient are NaN; at a position with ct_01 == 0 it adds nothing.
+ * ct_loss and its gradient are not affected.
+ *
+ * out_state: 32 bytes on the device, 8-byte aligned: int64 num_pos, int64 the count of bad indices, binary64 M, int64 0.
+ * ---------------------------------------------------------------------- */
+#define PVV_BOX_F32 0
+#define PVV_BOX_I32 1
+#define PVV_BOX_I64 2
+#define PVV_CT_TRAIN_MAX_N 512 /* objects per image: the list of an image is staged in LDS */
+
+/* P:46-66 per object with K:6-32 for a batch: d_ct_hm [B,C,H,W] f32, d_wh [B,N,2] f32, d_ct_cls [B,N] i64, d_ct_ind [B,N] i64,
+ * d_ct_01 [B,N] f32, d_ct_num [B] i64, all contiguous and all written completely.  Two launches. */
+int pvv_ct_targets(const void *d_boxes, int box_kind, const void *d_cls, int cls_is_i64, const void *d_num, int num_is_i64, int B,
+                   int N, int C, int H, int W, float *d_ct_hm, float *d_wh, long long *d_ct_cls, long long *d_ct_ind,
+                   float *d_ct_01, long long *d_ct_num, void *stream);
+
+/* Host-only.  Bytes pvv_ct_loss_forward needs: per (image, tile) two binary64 and one int64, per image four binary64 and two
+ * int64, each of the four parts rounded up to 256 bytes; 0 with pvv_last_error set when the sizes are refused. */
+size_t pvv_ct_loss_workspace_bytes(int B, int C, int H, int W);
+
+/* T:20-26 (L:9-49, L:240-246).  d_out_losses [2] float32 = {ct_loss, wh_loss}; d_out_state as above.  Three launches: the
+ * tiles, the images (with the objects), the batch. */
+int pvv_ct_loss_forward(const float *d_hm_pred, long long hp_image_stride, const float *d_wh_pred, long long wp_image_stride,
+                        const float *d_ct_hm, long long hm_image_stride, const float *d_wh, const void *d_ct_ind, int ind_is_i64,
+                        const float *d_ct_01, int B, int N, int C, int H, int W, void *workspace, size_t workspace_bytes,
+                        float *d_out_losses, void *d_out_state, void *stream);
+
+/* What autograd derives from T:20-26: d_grad_hm [B,C,H,W] and d_grad_wh [B,2,H,W], contiguous float32, from the inputs of the
+ * forward call, its d_out_state and d_grad_losses [2] float32 on the device = {go_ct, go_wh}.  One streaming launch over the
+ * heat map; a fill and one launch of a workgroup per image for the wh gradient. */
+int pvv_ct_loss_backward(const float *d_hm_pred, long long hp_image_stride, const float *d_wh_pred, long long wp_image_stride,
+                         const float *d_ct_hm, long long hm_image_stride, const float *d_wh, const void *d_ct_ind, int ind_is_i64,
+                         const float *d_ct_01, int B, int N, int C, int H, int W, const void *d_out_state,
+                         const float *d_grad_losses, float *d_grad_hm, float *d_grad_wh, void *stream);
+
+/* ------------------------------------------------------------------------
  * Training: vote targets and the PVNet loss (ABI v8, additive).  Citations:
  *   D = lib/utils/pvnet/pvnet_data_utils.py:30-44 (compute_vertex, called per sample at lib/datasets/<dataset>/pvnet.py:53)
  *   T = lib/train/trainers/pvnet.py:25-34 (NetworkWrapper.forward: the vote loss and the cross entropy)
