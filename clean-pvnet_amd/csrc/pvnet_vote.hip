@@ -464,3 +464,6 @@ PVV_EXPORT int pvv_count_inliers(const float *d_direct, const float *d_coords, c
 
 // ---- detector training: heat-map targets and the detector loss, forward and backward (ABI v8, additive) -----
 #include "ct_train.hpp"
+
+// ---- DCNv2 modulated deformable convolution, backward (ABI v8, additive) -------------------
+#include "dcn_train.hpp"

@@ -451,6 +451,59 @@ int pvv_dcn_columns(const float *d_input, const float *d_offset, long long offse
                     int pad_w, int dil_h, int dil_w, int deformable_groups, float *d_col, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Modulated deformable convolution (DCNv2), backward (ABI v8, additive): the five gradients of pvv_dcn_forward, the same
+ * bits on every run -- no float atomic anywhere.  I and C as in the forward's section.  Replaces dcn_v2_cuda_backward
+ * (C:206-335): modulated_deformable_col2im_coord_cuda (I:256-327 with the coordinate weight of I:82-123),
+ * modulated_deformable_col2im_cuda (I:197-254 with the gradient weight of I:56-80), the two SGEMMs (C:289-297, C:311-319 on
+ * the columns of C:300-307) and the bias SGEMV (C:322-329).  Float32 tensors and strides as in pvv_dcn_forward;
+ * d_grad_out [B,M,Ho,Wo] contiguous.  K = C*kh*kw, k = c*kh*kw + t, P = Ho*Wo, p = y*Wo + x, Cg = C/dg; h, w, the window test,
+ * h0, w0, the neighbours v1..v4 (0 outside the plane) and the blend weights w1..w4 = hh*hw, hh*lw, lh*hw, lh*lw are the
+ * forward's.  No fused multiply-add except where `fmaf` is written; everything float32 unless it says binary64.
+ *
+ *  1. gcol[b,k,p]: acc = +0; for o = 0 .. M-1: acc = fmaf(weight[o,k], grad_out[b,o,p], acc)       (v_mfma_f32_32x32x2_f32)
+ *  2. Per (b, g, t, p), over the channels c = g*Cg .. g*Cg + Cg - 1 ascending, from +0, with gc = gcol[b, c*kh*kw + t, p] and
+ *     m = mask[b, g*kh*kw + t, p], and only where the sample lies inside the window (otherwise all three stay exactly +0):
+ *       grad_mask   += gc * val,            val = ((w1*v1 + w2*v2) + w3*v3) + w4*v4
+ *       grad_off_h  += (ch * gc) * m,       ch = (((0 + (-wl)*v1) + (-wh)*v2) + wl*v3) + wh*v4,   wl = float(w0+1) - w, wh = w - float(w0)
+ *       grad_off_w  += (cw * gc) * m,       cw = (((0 + (-hl)*v1) + hl*v2) + (-hh)*v3) + hh*v4,   hl = float(h0+1) - h, hh = h - float(h0)
+ *     max_b = the largest |gc * m| of image b over every (k, p), inside the window or not (compared as bit patterns of the
+ *     absolute value, so a NaN counts as not finite).
+ *  3. grad_input.  max_b not finite: every element of image b is NaN.  max_b = 0: every element is +0.  Otherwise 2^e_b is the
+ *     smallest power of two >= max_b, and each neighbour i inside the plane of each sample inside the window contributes
+ *       n = rint(binary64(w_i * (gc * m)) * 2^(40 - e_b))      (exact scaling, ties to even, |n| <= 2^40)
+ *     to the int64 sum of its element; grad_input = float32(binary64(sum) * 2^(e_b - 40)).  Integer sums do not depend on
+ *     their order.  Refused unless kh*kw*P <= 2^22, so that a sum cannot overflow.
+ *  4. grad_weight.  Image b's pixels are cut into slabs of PVV_DCN_SLAB; per (b, slab, o, k): acc = +0; for p ascending in the
+ *     slab: acc = fmaf(grad_out[b,o,p], col[b,k,p], acc), col the forward's column element (sampled again on the chip).
+ *     grad_weight[o,k] = float32 of the binary64 sum of these over (b, slab) ascending, from +0.
+ *  5. grad_bias[o]: per image, binary64 lane sums s[l] = sum over p = l, l+256, ... ascending from +0, folded as
+ *     s[i] += s[i+w] for w = 128, 64, .., 1; the images' s[0] are added ascending from +0; float32 once.
+ * Zero terms (0 * 0) may be added to fill an instruction in 1 and 4: from +0 they change nothing.
+ * tests/dcn_train_twin.py is this contract in numpy.
+ *
+ * Workspace (caller-allocated, 256-byte aligned; nothing is kept between calls; every part 256-byte aligned): binary64 [M,K]
+ * and [M] accumulators and 65536 max words, then for `chunk` images at a time gcol f32 [chunk,K,P], the grad_weight partials
+ * f32 [chunk, ceil(P/PVV_DCN_SLAB), M, K] and the sums i64 [chunk,C,H,W].  The images go through in chunks; no [B,K,P]
+ * tensor exists and the result does not depend on the chunk size.  Nothing is read back; no host synchronisation.
+ * ---------------------------------------------------------------------- */
+#define PVV_DCN_SLAB 512
+
+/* Host-only; stands for the `ones` and `columns` allocations of C:206-335 (C:247-248).  Bytes for chunks of `chunk_images` images (clamped to [1, B]); <= 0: as many images as fit 256 MiB of per-image
+ * parts, one at least.  Negative (PVV_E_ARG) with pvv_last_error set when the sizes are refused. */
+long long pvv_dcn_backward_workspace_bytes(int B, int C, int H, int W, int M, int kh, int kw, int stride_h, int stride_w, int pad_h,
+                                           int pad_w, int dil_h, int dil_w, int deformable_groups, int chunk_images);
+
+/* Replaces C:206-335 with I:56-123 (the gradient and coordinate weights) and I:197-327 (col2im, col2im_coord).
+ * Any of the five outputs may be NULL: its launches are skipped.  d_grad_input [B,C,H,W], d_grad_offset [B,2*dg*kh*kw,Ho,Wo],
+ * d_grad_mask [B,dg*kh*kw,Ho,Wo], d_grad_weight [M,C,kh,kw], d_grad_bias [M], all contiguous.  The chunk is the largest that
+ * `workspace_bytes` holds; PVV_E_WORKSPACE when it does not hold one image. */
+int pvv_dcn_backward(const float *d_input, const float *d_weight, const float *d_offset, long long offset_image_stride,
+                     const float *d_mask, long long mask_image_stride, const float *d_grad_out, int B, int C, int H, int W, int M,
+                     int kh, int kw, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int deformable_groups,
+                     float *d_grad_input, float *d_grad_offset, float *d_grad_mask, float *d_grad_weight, float *d_grad_bias,
+                     void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------
  * Model metadata (ABI v8, additive): from a mesh's vertices to what every later stage consumes -- the farthest-point
  * keypoints (`fps_3d`), the bounding box (`corner_3d`, `center_3d`) and the diameter.  Citations:
  *   F = lib/csrc/fps/src/farthest_point_sampling.cpp    M = lib/utils/vsd/misc.py:139-154 (calc_pts_diameter)
