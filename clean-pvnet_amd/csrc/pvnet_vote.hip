@@ -467,3 +467,6 @@ PVV_EXPORT int pvv_count_inliers(const float *d_direct, const float *d_coords, c
 
 // ---- DCNv2 modulated deformable convolution, backward (ABI v8, additive) -------------------
 #include "dcn_train.hpp"
+
+// ---- training augmentation: rotate, crop, resize, blur, colour jitter, normalise (ABI v8, additive) -----
+#include "augment.hpp"

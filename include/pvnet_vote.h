@@ -563,6 +563,52 @@ int pvv_model_diameter(const void *d_points, int is_f64, const int *d_n, int B, 
                        double *d_out, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Training augmentation: PVNet's rotate / crop / resize and the loader's transforms for a batch (ABI v8, additive).  Citations:
+ *   P = lib/datasets/linemod/pvnet.py:62-78 (augment; lib/datasets/custom/pvnet.py repeats it)
+ *   A = lib/datasets/augmentation.py (rotate_instance :60-69, crop_or_padding_to_fixed_size_instance :126-167,
+ *       crop_or_padding_to_fixed_size :170-196, crop_resize_instance_v1 :266-295)
+ *   X = lib/datasets/transforms.py:29-99 (ToTensor, Normalize, ColorJitter, RandomBlur, make_transforms)
+ * Device pointers, caller-owned workspace (8-byte aligned), the caller's stream last; nothing is read back, nothing
+ * synchronises, nothing is allocated and nothing is kept between calls.  The kernels draw no random number and evaluate no
+ * transcendental function: the caller hands over the drawn values per sample, cos and sin of the degree included.  No fused
+ * multiply-add anywhere; every reduction is over integers, so no arrival order enters a result and reruns give the same
+ * bytes.  tests/augment_twin.py is this contract in numpy; DESIGN.md section 18 states it in full.
+ * Limits, refused with PVV_E_ARG beyond them: 1 <= B <= 65535, sides in [1, 16384], out_size sides in [8, 16384], K <= 65535.
+ *
+ * pvv_pvnet_augment's params: B records of PVV_AUGMENT_PARAM_BYTES on the device, 8-byte aligned:
+ *   binary64 cos, sin, ratio, u_h, u_w;  int32 th = int(oh * ratio), tw = int(ow * ratio)
+ * pvv_pvnet_transform's params: B records of PVV_TRANSFORM_PARAM_BYTES on the device:
+ *   int32 k (0, 3, 5, 7, 9);  int32 w[9] (the taps centred on w[4], summing to 256);  float32 f[3] (the factors of
+ *   brightness, contrast, saturation);  int32 hue (what is added to PIL's 8-bit hue modulo 256: int(factor * 255) & 255);
+ *   int32 order[4] (0 brightness, 1 contrast, 2 saturation, 3 hue in the drawn order, -1 for a step that is not applied)
+ * ---------------------------------------------------------------------- */
+#define PVV_AUGMENT_PARAM_BYTES 48
+#define PVV_TRANSFORM_PARAM_BYTES 72
+
+/* Host-only.  Bytes pvv_pvnet_augment needs: a record per sample and the rotated windows [B,max_th,max_tw,3], max_th and max_tw
+ * the largest th and tw among the records; 0 with pvv_last_error set when a size is refused. */
+size_t pvv_augment_workspace_bytes(int B, int max_th, int max_tw);
+
+/* P:62-78.  d_img [B,H,W,3] uint8, d_mask [B,H,W] uint8 (foreground: != 0), d_kpt_2d [B,K,2] float32 or binary64.  Writes
+ * d_out_img [B,oh,ow,3] uint8, d_out_mask [B,oh,ow] uint8, d_out_kpt [B,K,2] binary64, d_path [B] int32 (0 no foreground, 1 the
+ * instance branch, 2 the rotated mask is empty: the steps of 0) and d_window [B,6] int32 (th, tw, hbeg, wbeg, pad_h, pad_w).
+ * A fill and five launches: the moments, the rotated mask's box, the window with the keypoints, the rotated image inside each
+ * window, the output pixels.  A record whose th or tw exceeds max_th or max_tw reads zeros beyond them, never out of bounds. */
+int pvv_pvnet_augment(const uint8_t *d_img, const uint8_t *d_mask, const void *d_kpt_2d, int kpt_is_f64, int B, int H, int W, int K,
+                      int oh, int ow, double overlap_ratio, const void *d_params, int max_th, int max_tw, void *d_workspace, size_t workspace_bytes,
+                      uint8_t *d_out_img, uint8_t *d_out_mask, double *d_out_kpt, int32_t *d_path, int32_t *d_window, void *stream);
+
+/* Host-only.  Bytes pvv_pvnet_transform needs when it is given params: one int64 per image and the blurred batch. */
+size_t pvv_transform_workspace_bytes(int B, int h, int w);
+
+/* X:81-90.  d_img [B,h,w,3] uint8 -> d_out [B,3,h,w] float32.  d_params NULL: ToTensor and Normalize only (no workspace
+ * needed).  h_mean, h_std: 3 binary64 each on the host.  has_blur / has_contrast: whether any record asks for the step (its
+ * launch is skipped otherwise).  With params the sides must be at least 8.  At most a fill and three launches. */
+int pvv_pvnet_transform(const uint8_t *d_img, int B, int h, int w, const void *d_params, int has_blur, int has_contrast,
+                        const double *h_mean, const double *h_std, void *d_workspace, size_t workspace_bytes, float *d_out,
+                        void *stream);
+
+/* ------------------------------------------------------------------------
  * Detector training: heat-map targets and the detector loss (ABI v8, additive).  Citations:
  *   P = lib/datasets/tless_train/ct.py:46-66 (prepare_detection, called per object at :86-95)
  *   G = lib/utils/data_utils.py:10-65 (gaussian_radius :10-33, gaussian2D :36-47, draw_umich_gaussian :50-65)
