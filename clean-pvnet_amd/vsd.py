@@ -6,9 +6,9 @@ The reference scores VSD one pose pair at a time on the host: ``Evaluator.vsd_me
 ground-truth pose (lib/utils/renderer/opengl_utils.py:405-492), then runs ``depth_im_to_dist_im``, the two visibility masks
 and ``vsd`` (lib/utils/vsd/) in numpy on every pair.  Here ``render_depth`` rasterises a triangle mesh at every pose of a
 batch in HIP, ``vsd`` turns the renders and the sensor images into the error of every (prediction, ground truth) pair of every
-image, and ``VsdEvaluator`` applies the reference's any-pair rule and counts the hits on the device; nothing is read back
-before ``summarize()``.  Every call runs on the current stream in a workspace from the caching allocator.  There is no CPU
-fallback.
+image (``vsd_from_depth`` is its second half, for renders the caller already holds), and ``VsdEvaluator`` applies the
+reference's any-pair rule and counts the hits on the device; nothing is read back before ``summarize()``.  Every call runs
+on the current stream in a workspace from the caching allocator.  There is no CPU fallback.
 """
 from . import _native
 from ._native import DOUBLE, INT, PTR, SIZE
@@ -105,23 +105,17 @@ def vsd(pose_est, pose_gt, depth_test, K, pts, faces, *, delta=15., tau=20., cos
     :return:            e [n,p,g] float64
     """
     import torch
-    for t, what in ((pose_est, "pose_est"), (pose_gt, "pose_gt"), (K, "K"), (pts, "pts"), (faces, "faces")):
+    for t, what in ((pose_est, "pose_est"), (pose_gt, "pose_gt"), (K, "K"), (depth_test, "depth_test")):
         _native.need_cuda(t, what, "vsd")
-    if cost not in COSTS:
-        raise ValueError("vsd: cost must be 'step' or 'tlinear', got %r" % (cost,))
-    dt, kind = _test_image(depth_test, depth_scale)
     dev = pose_est.device
     n, p = pose_est.shape[:2]
     g = pose_gt.shape[1]
     assert pose_est.shape == (n, p, 3, 4) and pose_gt.shape == (n, g, 3, 4), (pose_est.shape, pose_gt.shape)
-    assert dt.dim() == 3 and dt.shape[0] == n, dt.shape
-    H, W = int(dt.shape[1]), int(dt.shape[2])
-    _check_size((W, H))
+    assert depth_test.dim() == 3 and depth_test.shape[0] == n, depth_test.shape
+    H, W = int(depth_test.shape[1]), int(depth_test.shape[2])
     Km = K.to(device=dev, dtype=torch.float64).contiguous()
     assert Km.shape in ((3, 3), (n, 3, 3)), Km.shape
-    if gt_valid is not None:
-        _native.need_cuda(gt_valid, "gt_valid", "vsd")
-        assert gt_valid.shape == (n, g), gt_valid.shape
+    # the sensor image, cost, gt_valid and the image size are checked by render_depth and vsd_from_depth
     # one render per pose: the n*p predictions, then the n*g ground truths
     poses = torch.cat([pose_est.to(torch.float64).reshape(n * p, 3, 4), pose_gt.to(device=dev, dtype=torch.float64).reshape(n * g, 3, 4)])
     poses = torch.cat([poses[:, :, :3], poses[:, :, 3:] * float(t_scale)], 2)
@@ -131,6 +125,47 @@ def vsd(pose_est, pose_gt, depth_test, K, pts, faces, *, delta=15., tau=20., cos
         Kp = Km
     depth = render_depth(pts, faces, poses, Kp, (W, H), near, far)
     depth_est, depth_gt = depth[:n * p].view(n, p, H, W), depth[n * p:].view(n, g, H, W)
+    e, counts = vsd_from_depth(depth_est, depth_gt, depth_test, Km, delta=delta, tau=tau, cost=cost, depth_scale=depth_scale,
+                               gt_valid=gt_valid, return_counts=True)
+    if return_images:
+        images = {"depth_est": depth_est, "depth_gt": depth_gt}
+        images.update(counts)
+        return e, images
+    return e
+
+
+def vsd_from_depth(depth_est, depth_gt, depth_test, K, *, delta=15., tau=20., cost="step", depth_scale=0.1, gt_valid=None,
+                   return_counts=False):
+    """The second half of ``vsd``: the error of every pair from depth images the caller already holds (renders of
+    ``render_depth`` or of any other renderer with its conventions: eye-space Z in model units, 0 = background).
+    :param depth_est:   [n,p,H,W] float32 CUDA tensor, the renders of the predictions of each image
+    :param depth_gt:    [n,g,H,W] float32, the renders of the ground-truth poses
+    :param depth_test, K, delta, tau, cost, depth_scale, gt_valid:  as for ``vsd``
+    :param return_counts:  also return a dict with the per-pair ``union``, ``inter``, ``cost`` counts [n,p,g] int64
+    :return:            e [n,p,g] float64
+    """
+    import torch
+    for t, what in ((depth_est, "depth_est"), (depth_gt, "depth_gt"), (K, "K")):
+        _native.need_cuda(t, what, "vsd")
+    if cost not in COSTS:
+        raise ValueError("vsd: cost must be 'step' or 'tlinear', got %r" % (cost,))
+    dt, kind = _test_image(depth_test, depth_scale)
+    for t, what in ((depth_est, "depth_est"), (depth_gt, "depth_gt")):
+        if t.dtype != torch.float32:
+            raise TypeError("vsd: %s has dtype %s, the renders are float32" % (what, t.dtype))
+    assert depth_est.dim() == 4 and depth_gt.dim() == 4, (depth_est.shape, depth_gt.shape)
+    dev = depth_est.device
+    n, p, H, W = (int(v) for v in depth_est.shape)
+    g = int(depth_gt.shape[1])
+    assert tuple(depth_gt.shape) == (n, g, H, W), (depth_est.shape, depth_gt.shape)
+    assert tuple(dt.shape) == (n, H, W), dt.shape
+    _check_size((W, H))
+    Km = K.to(device=dev, dtype=torch.float64).contiguous()
+    assert Km.shape in ((3, 3), (n, 3, 3)), Km.shape
+    if gt_valid is not None:
+        _native.need_cuda(gt_valid, "gt_valid", "vsd")
+        assert gt_valid.shape == (n, g), gt_valid.shape
+    depth_est, depth_gt = depth_est.contiguous(), depth_gt.contiguous()
     counts = torch.empty(n, p, g, 3, dtype=torch.int64, device=dev)
     e = torch.empty(n, p, g, dtype=torch.float64, device=dev)
     if n * p * g:
@@ -140,10 +175,8 @@ def vsd(pose_est, pose_gt, depth_test, K, pts, faces, *, delta=15., tau=20., cos
                      counts.data_ptr(), e.data_ptr(), ws.data_ptr(), n, p, g, H, W)
     if gt_valid is not None:
         e = torch.where((gt_valid != 0)[:, None, :], e, torch.full_like(e, float("nan")))
-    if return_images:
-        images = {"depth_est": depth_est, "depth_gt": depth_gt}
-        images.update({k: counts[..., i] for i, k in enumerate(COUNTS)})
-        return e, images
+    if return_counts:
+        return e, {k: counts[..., i] for i, k in enumerate(COUNTS)}
     return e
 
 

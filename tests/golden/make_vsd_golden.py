@@ -14,6 +14,9 @@ poses (translations in metres, as the evaluator holds them), the camera, the ima
 ``np.packbits``.  Asserted while writing: the twin's distance image equals the reference's ``np.linalg.norm(np.dstack(...))``
 bit for bit for the sensor image and for every render, and no stored ``e`` lies within 1e-6 relative of the threshold 0.3.
 
+``vsd_rules.npz`` (``make_rules``) holds constructed images instead of seeds: vsd_twin.rules_images(), whose differences lie
+exactly on delta and tau and one float32 step to either side, under a camera for which distance equals depth (asserted).
+
 Run from the repository root in the build container:  python tests/golden/make_vsd_golden.py
 """
 import importlib.util
@@ -116,12 +119,55 @@ def make(name, d, misc, visibility, vsd_utils):
     return c
 
 
+def make_rules(misc, visibility, vsd_utils):
+    """vsd_rules: the constructed images of vsd_twin.rules_images() -- differences exactly on, one float32 step below and
+    one above delta and tau, invalid pixels, a partial tile -- through the same reference functions as ``make``.  The
+    images themselves are stored (a few kilobytes); keys are ``<case>_<what>``."""
+    K = twin.RULES_K
+    c = dict(K=K, delta=twin.RULES_DELTA, tau=twin.RULES_TAU, cases=np.array(sorted(twin.rules_images())))
+    for name, (depth, gt, est) in twin.rules_images().items():
+        g, p = len(gt), len(est)
+        dist_test = misc.depth_im_to_dist_im(depth, K)
+        assert np.array_equal(dist_test, twin.dist_image(depth, K)) and np.array_equal(dist_test, depth)
+        e = {"step": np.zeros((p, g)), "tlinear": np.zeros((p, g))}
+        counts = np.zeros((p, g, 3), np.int64)
+        cost_sum = np.zeros((p, g))
+        dist_gt, visib_gt, bits_gt, bits_est = {}, {}, [], []
+        for b in range(g):
+            dist_gt[b] = misc.depth_im_to_dist_im(gt[b], K)
+            assert np.array_equal(dist_gt[b], twin.dist_image(gt[b], K)) and np.array_equal(dist_gt[b], gt[b].astype(np.float64))
+            visib_gt[b] = visibility.estimate_visib_mask_gt(dist_test, dist_gt[b], twin.RULES_DELTA)
+            bits_gt.append(np.packbits(visib_gt[b]))
+        for a in range(p):
+            dist_est = misc.depth_im_to_dist_im(est[a], K)
+            assert np.array_equal(dist_est, twin.dist_image(est[a], K)) and np.array_equal(dist_est, est[a].astype(np.float64))
+            for b in range(g):
+                for cost in ("step", "tlinear"):
+                    e[cost][a, b] = vsd_utils.vsd(dist_est, dist_gt[b], dist_test, visib_gt[b], twin.RULES_DELTA, twin.RULES_TAU,
+                                                  cost)
+                visib_est = visibility.estimate_visib_mask_est(dist_test, dist_est, visib_gt[b], twin.RULES_DELTA)
+                inter = np.logical_and(visib_gt[b], visib_est)
+                costs = np.abs(dist_gt[b][inter] - dist_est[inter])
+                counts[a, b] = (np.logical_or(visib_gt[b], visib_est).sum(), inter.sum(), (costs >= twin.RULES_TAU).sum())
+                costs *= (1.0 / twin.RULES_TAU)
+                costs[costs > 1.0] = 1.0
+                cost_sum[a, b] = costs.sum()
+                bits_est.append(np.packbits(visib_est))
+        c.update({name + "_test": depth, name + "_gt": gt, name + "_est": est, name + "_e_step": e["step"],
+                  name + "_e_tlinear": e["tlinear"], name + "_counts": counts, name + "_cost_sum": cost_sum,
+                  name + "_visib_gt_bits": np.stack(bits_gt), name + "_visib_est_bits": np.stack(bits_est).reshape(p, g, -1)})
+    return c
+
+
 def main():
     misc, visibility, vsd_utils = load_reference()
-    for name, d in definitions().items():
-        c = make(name, d, misc, visibility, vsd_utils)
-        print(name, "e_step", np.round(c["e_step"], 4).tolist(), "e_tlinear", np.round(c["e_tlinear"], 4).tolist(),
-              "union", c["counts"][..., 0].tolist())
+    made = [(name, make(name, d, misc, visibility, vsd_utils)) for name, d in definitions().items()]
+    made.append(("vsd_rules", make_rules(misc, visibility, vsd_utils)))
+    for name, c in made:
+        for k in sorted(c):
+            if k.endswith("e_step"):
+                print(name, k, np.round(c[k], 4).tolist(), "e_tlinear", np.round(c[k.replace("e_step", "e_tlinear")], 4).tolist(),
+                      "union", c[k.replace("e_step", "counts")][..., 0].tolist())
         path = os.path.join(OUT, name + ".npz")
         if os.path.exists(path) and "--force" not in sys.argv:       # committed fixtures are not rewritten (zip metadata churn)
             old = dict(np.load(path))

@@ -15,6 +15,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VSDLIB = os.path.join(ROOT, "clean-pvnet_amd", "libpvnet_vsd.so")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 FIXTURES = ("vsd_720", "vsd_360", "vsd_near")
+RULES = "vsd_rules"                                  # constructed images, stored whole (make_vsd_golden.py::make_rules)
+SOUP_SIZES = ((37, 29), (5, 4), (67, 3), (1, 1))     # the sizes tests/test_gpu_vsd_rules.py renders the lattice soups at
 
 
 def load(name):
@@ -24,6 +26,7 @@ def load(name):
 def test_module_imports(pkg):
     from clean_pvnet_amd import vsd
     assert vsd.COSTS == {"step": 0, "tlinear": 1} and callable(vsd.render_depth) and callable(vsd.vsd)
+    assert callable(vsd.vsd_from_depth)
 
 
 # --------------------------------------------------------------------------------- 1. the twin against an independent renderer
@@ -154,10 +157,178 @@ def test_vsd_fixtures_are_reproducible_from_the_reference():
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if " exists," in l]
-    assert len(lines) == len(FIXTURES) and all(l.endswith("identical content") for l in lines), out.stdout
+    assert sorted(l.split()[0] for l in lines) == sorted(FIXTURES + (RULES,)), out.stdout
+    assert all(l.endswith("identical content") for l in lines), out.stdout
 
 
-# ------------------------------------------------------------------------------------------- 3. the library and its arguments
+# ------------------------------------------------------------------------------------- 3. constructed inputs: exact boundaries
+def _render(m, faces=None):
+    return twin.render_depth(m["pts"], m["faces"] if faces is None else faces, m["pose"], m["K"], m["size"], m["near"], m["far"])
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_twin_on_lattice_soups_against_the_ray_caster(seed):
+    """Half-pixel lattice soups put edges exactly through sample centres.  Off the samples that lie on the boundary of some
+    closed triangle the twin and the ray caster agree on coverage, and on depth within 2**-23 relative (float32 rounding).
+    Conditions on the input, not tolerances: the boundary samples are at most 10 % of the covered ones (measured 2.8 % to
+    6.1 % on seeds 0..5), at least 20, and the twin covers some of them and not others."""
+    m = twin.lattice_soup(seed, (37, 29))
+    got = _render(m)
+    want, _ = twin.raycast_depth(m["pts"], m["faces"], m["pose"], m["K"], m["size"], m["near"], m["far"])
+    cov_t, cov_r, bnd = got > 0, want > 0, m["boundary"]
+    covered, on = int((cov_t | cov_r).sum()), int(((cov_t | cov_r) & bnd).sum())
+    both = ~bnd & cov_t & cov_r
+    rel = np.abs(got.astype(np.float64)[both] - want[both]) / want[both]
+    diff_cov = int((cov_t != cov_r)[~bnd].sum())
+    print("soup %d: covered %d, boundary %d (%.1f %%; %d covered by the twin, %d not), coverage differences %d, largest "
+          "relative depth difference %.3g" % (seed, covered, on, 100.0 * on / covered, int((bnd & cov_t).sum()),
+                                              int((bnd & ~cov_t).sum()), diff_cov, rel.max()))
+    assert on <= 0.10 * covered and int(bnd.sum()) >= 20
+    assert (bnd & cov_t).any() and (bnd & ~cov_t).any()
+    assert diff_cov == 0
+    assert rel.size and rel.max() <= 2.0 ** -23
+    f = m["faces"]
+    assert (f[:, 0] == f[:, 1]).any() or (f[:, 1] == f[:, 2]).any() or (f[:, 0] == f[:, 2]).any()       # repeated indices occur
+
+
+@pytest.mark.parametrize("seed", (1, 4))
+def test_twin_partition_equals_its_closed_form(seed):
+    """The union of a partition is its outer rectangle under the ownership rule, as bytes; and every sample inside it
+    belongs to exactly one triangle, every sample outside to none.  The two seeds put each outer line once on sample
+    centres and once on integers."""
+    m = twin.partition_mesh(seed, (26, 19))
+    want = m["closed_form"]
+    np.testing.assert_array_equal(_render(m).view(np.uint32), want.view(np.uint32))
+    owners = sum((_render(m, m["faces"][k:k + 1]) > 0).astype(np.int64) for k in range(len(m["faces"])))
+    np.testing.assert_array_equal(owners, (want > 0).astype(np.int64))
+    assert (want > 0).any() and (want == 0).any() and set(np.unique(want)) == {0.0, 4.0}
+
+
+def test_partition_seeds_put_every_outer_line_on_both_kinds_of_coordinate():
+    ends = [np.array([g[0] for g in twin.partition_mesh(s, (26, 19))["lines"]] + [g[-1] for g in twin.partition_mesh(s, (26, 19))["lines"]])
+            for s in (1, 4)]
+    on_centre = np.stack([e % 1.0 == 0.5 for e in ends])                 # [seed, (left, top, right, bottom)]
+    assert on_centre.any(0).all() and (~on_centre).any(0).all()
+
+
+def test_constructed_meshes_keep_their_promises():
+    """The builders' promises, checked from the snapped coordinates: the sizes at which the sweep changes its path."""
+    m = twin.size_class_mesh()
+    boxes = twin.piece_boxes(m)
+    named = {k: boxes[i] for k, i in m["named"].items()}
+    assert m["size"] == (130, 70) and len(m["faces"]) > 256 and len(m["faces"]) % 256 != 0
+    assert named["box32"][1] == [(32, 2)] and named["box33"][1][0][0] == 33                  # kSmall = 32: the last lane-swept size
+    for name, (x, y) in (("box32", (17, 13)), ("box33", (40, 12))):                          # and the box's last sample is covered
+        assert _render(m, m["faces"][m["named"][name]][None])[y, x] == 2.0 and _render(m)[y, x] == 2.0
+    assert named["whole"][1] == [(130 * 70, 153)] and named["sliver"][1] == [(130 * 70, 153)]
+    assert named["blocks65"][1][0][1] == 65                                                  # one block past a wave's 64
+    assert named["limit"][1] and not named["beyond"][1] and not named["beyond_v"][1]
+    E = twin.eye_space(m["pts"], m["pose"])
+    U, V, ok = twin._snap(m["K"], E[:, 0], E[:, 1], E[:, 2])
+    f = m["faces"]
+    assert np.abs(U[f[m["named"]["limit"]]]).max() == 2 ** 28 and ok[f[m["named"]["limit"]]].all()
+    assert not ok[f[m["named"]["beyond"]]].all() and not ok[f[m["named"]["beyond_v"]]].all()
+    assert np.abs(U[f[m["named"]["whole"]]]).max() == 2 ** 27 and np.abs(V[f[m["named"]["whole"]]]).max() == 2 ** 27
+    first = [b for _, bs in boxes[:256] for b in bs]
+    assert sum(1 for s, _ in first if s <= 32) >= 64 and sum(1 for s, _ in first if s > 32) >= 64
+    img = _render(m)
+    assert (img > 0).all()                                               # the whole-image triangle lies behind everything
+    # blocks of a wave-swept piece in which an owning edge function is largest, and exactly 0, at a covered corner sample
+    # that nothing hides: rejecting a block at `largest <= 0` instead of `< 0` loses these samples
+    kinds = set()
+    for name in ("corner_col", "corner_row", "corner_slant"):
+        k = m["named"][name]
+        assert named[name][1][0][0] > 32                                 # swept by the wave, block by block
+        corners = twin.block_corner_samples(m, k)
+        assert len(corners) >= 2
+        alone, without = _render(m, m["faces"][k][None]), _render(m, np.delete(m["faces"], k, 0))
+        for x, y in corners:
+            assert alone[y, x] == 2.0 and img[y, x] == 2.0 and without[y, x] != 2.0                  # covered and frontmost
+            kinds.add((x % 8 == 0, y % 8 == 7))
+    assert {(True, False), (False, True), (True, True)} <= kinds        # a first column, a last row, a block's corner
+    assert not twin.block_corner_samples(m, m["named"]["blocks65"]) and not twin.block_corner_samples(m, m["named"]["whole"])
+    alone = _render(m, m["faces"][m["named"]["whole"]][None])
+    assert (alone > 0).all() and (alone >= img).all() and (alone == img).sum() > 1000 and (alone > img).sum() > 1000
+    # near clipping
+    c = twin.clip_mesh()
+    cb = twin.piece_boxes(c)
+    inside = [k for k, _ in cb]
+    assert {0, 1, 2, 3} <= set(inside)
+    assert any(len(b) == 2 for _, b in cb)
+    for w in range(0, len(cb), 64):                                      # a wave with a second piece in some lanes only
+        second = [len(b) == 2 for _, b in cb[w:w + 64]]
+        assert any(second) and not all(second)
+    assert (twin.eye_space(c["pts"], c["pose"])[:, 2] == c["near"]).any()
+    kept, dropped = c["far_quads"]
+    assert (_render(c, c["faces"][kept:kept + 2]) == np.float32(c["far"])).sum() >= 50
+    assert not _render(c, c["faces"][dropped:dropped + 2]).any() and cb[dropped][1]          # swept, every sample beyond far
+    assert c["pts"][c["faces"][dropped], 2].min() == np.nextafter(np.float32(c["far"]), np.float32(np.inf))
+    edges = {}
+    for k, (n_in, _) in enumerate(cb):                                   # clipped edges (one end inside) shared by two faces
+        r = c["faces"][k]
+        if len(set(r.tolist())) == 3 and n_in in (1, 2):
+            for a, b in ((r[0], r[1]), (r[1], r[2]), (r[2], r[0])):
+                Za, Zb = c["pts"][a, 2], c["pts"][b, 2]
+                if (Za >= c["near"]) != (Zb >= c["near"]):
+                    edges.setdefault((min(a, b), max(a, b)), []).append(k)
+    assert sum(1 for v in edges.values() if len(v) >= 2) >= 9            # the nine spokes of the two fans
+    # the scalar tail of the resolve pass: P*H*W % 4 takes every value over the sizes the device tests use
+    sizes = [(1,) + s for s in SOUP_SIZES] + [(1, 26, 19), (1,) + c["size"], (1,) + m["size"], (3, 37, 29)]
+    assert {P * W * H % 4 for P, W, H in sizes} == {0, 1, 2, 3}
+
+
+def test_twin_vsd_reproduces_the_rules_fixture():
+    """The stored constructed images through twin.vsd_pair: masks and counts equal to the reference's, 'step' e bit for
+    bit, 'tlinear' e within tlinear_bound; the stored images are what the builder builds; and the table's leading pixels
+    give exactly the masks written out by hand in vsd_twin.RULES_TABLE."""
+    c = load(RULES)
+    built = twin.rules_images()
+    assert sorted(c["cases"].tolist()) == sorted(built) == ["f32", "f64", "small", "zero"]
+    K, delta, tau = c["K"], float(c["delta"]), float(c["tau"])
+    assert (delta, tau) == (twin.RULES_DELTA, twin.RULES_TAU) == (15.0, 20.0)
+    for name in built:
+        depth, gt, est = c[name + "_test"], c[name + "_gt"], c[name + "_est"]
+        for got, want in zip((depth, gt, est), built[name]):
+            assert got.dtype == want.dtype and np.array_equal(got, want)
+        assert np.array_equal(twin.dist_image(depth, K), depth)          # the camera makes distance equal depth
+        for a in range(len(est)):
+            for b in range(len(gt)):
+                step = twin.vsd_pair(est[a], gt[b], depth, K, delta, tau, "step")
+                np.testing.assert_array_equal(np.packbits(step["visib_gt"]), c[name + "_visib_gt_bits"][b])
+                np.testing.assert_array_equal(np.packbits(step["visib_est"]), c[name + "_visib_est_bits"][a, b])
+                assert [step["union"], step["inter"], step["cost"]] == c[name + "_counts"][a, b].tolist()
+                assert step["e"] == c[name + "_e_step"][a, b], (name, a, b)
+                tl = twin.vsd_pair(est[a], gt[b], depth, K, delta, tau, "tlinear")
+                want = float(c[name + "_e_tlinear"][a, b])
+                bound = twin.tlinear_bound(want, tl["m"], float(c[name + "_cost_sum"][a, b]), tl["union"])
+                print("%s[%d,%d] counts %s step %.17g tlinear got %.17g want %.17g |diff| %.3g bound %.3g" %
+                      (name, a, b, c[name + "_counts"][a, b].tolist(), step["e"], tl["e"], want, abs(tl["e"] - want), bound))
+                assert abs(tl["e"] - want) <= bound
+    assert c["zero_counts"].tolist() == [[[0, 0, 0]]] and c["zero_e_step"][0, 0] == 1.0 == c["zero_e_tlinear"][0, 0]
+    # the table, by hand
+    for name, rows in (("f64", list(range(len(twin.RULES_TABLE)))),
+                       ("f32", [k for k in range(len(twin.RULES_TABLE)) if k not in twin.RULES_F64_ROWS])):
+        n = len(rows)
+        table = [twin.RULES_TABLE[k] for k in rows]
+        assert c[name + "_test"].ravel()[:n].tolist() == [float(t[0]) for t in table]
+        assert c[name + "_gt"][0].ravel()[:n].tolist() == [float(t[1]) for t in table]
+        assert c[name + "_est"][0].ravel()[:n].tolist() == [float(t[2]) for t in table]
+        vg = np.unpackbits(c[name + "_visib_gt_bits"][0])[:n].tolist()
+        ve = np.unpackbits(c[name + "_visib_est_bits"][0, 0])[:n].tolist()
+        assert vg == [t[3] for t in table] and ve == [t[4] for t in table], (name, vg, ve)
+    assert [t[3] for t in twin.RULES_TABLE] == [1, 0, 1, 1, 1, 0, 0, 1, 0, 1, 0, 0, 1, 1, 1, 0]
+    assert [t[4] for t in twin.RULES_TABLE] == [1, 1, 1, 1, 1, 0, 1, 0, 0, 1, 1, 0, 1, 1, 1, 1]
+    # what the rows are there for: binary64 visibility would lose the row 2**-30 below, and the three rows around tau cost
+    # 1, 0, 1 under 'step'
+    t, g, e = (np.array([r[k] for r in twin.RULES_TABLE], np.float64) for k in range(3))
+    assert not (g[3] - t[3] <= delta) and np.float32(g[3]) - np.float32(t[3]) <= np.float32(delta)
+    assert (np.abs(g[12:15] - e[12:15]) >= tau).tolist() == [True, False, True]
+    raw = twin.rules_uint16(c["f32_test"])
+    assert raw.dtype == np.uint16 and np.array_equal(twin.sensor_depth(raw, 0.125), c["f32_test"])
+    assert c["f64_test"].size == 300 and c["small_test"].size == 37      # two tiles with a partial second; one partial tile
+
+
+# ------------------------------------------------------------------------------------------- 4. the library and its arguments
 def test_vsd_library_exports_what_the_header_declares():
     txt = open(os.path.join(ROOT, "include", "pvnet_vsd.h")).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
@@ -216,5 +387,7 @@ def test_no_cpu_fallback(pkg):
         vsd.render_depth(pts, faces, P, K, (8, 8))
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         vsd.vsd(P[None], P[None], torch.zeros(1, 8, 8, dtype=torch.uint16), K, pts, faces)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        vsd.vsd_from_depth(torch.zeros(1, 1, 8, 8), torch.zeros(1, 1, 8, 8), torch.zeros(1, 8, 8, dtype=torch.uint16), K)
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         vsd.VsdEvaluator(np.zeros((5, 3), np.float32), np.zeros((2, 3), np.int32), (8, 8), device="cpu")
