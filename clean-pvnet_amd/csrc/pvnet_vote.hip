@@ -470,3 +470,6 @@ PVV_EXPORT int pvv_count_inliers(const float *d_direct, const float *d_coords, c
 
 // ---- training augmentation: rotate, crop, resize, blur, colour jitter, normalise (ABI v8, additive) -----
 #include "augment.hpp"
+
+// ---- detector augmentation: cut-and-paste, warp, colour steps, boxes on the output map (ABI v8, additive) -----
+#include "ct_augment.hpp"

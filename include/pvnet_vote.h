@@ -609,6 +609,62 @@ int pvv_pvnet_transform(const uint8_t *d_img, int B, int h, int w, const void *d
                         void *stream);
 
 /* ------------------------------------------------------------------------
+ * Detector augmentation: the T-LESS detector's training batch from cut-outs and a background, and the detector's input
+ * preparation at inference (ABI v8, additive).  Citations:
+ *   U = lib/utils/tless/tless_utils.py (augment :18-63, cut_and_paste :86-97)
+ *   C = lib/datasets/tless/ct.py:58-70 (Dataset.get_bbox);  C' = lib/datasets/tless_train/ct.py:75-76 (the nearest form)
+ *   G = lib/utils/data_utils.py (get_affine_transform :123-156, grayscale :172-173, lighting_ .. contrast_ :176-199,
+ *       color_aug :202-210)
+ * Device pointers, caller-owned workspace (8-byte aligned), the caller's stream last; nothing is read back, nothing
+ * synchronises, nothing is allocated and nothing is kept between calls.  The kernels draw no random number and evaluate no
+ * transcendental function.  No fused multiply-add anywhere; the only floating-point sum (the grey mean) is binary64 in a
+ * fixed tree, every other reduction is over integers: reruns give the same bytes.  Every source tap is tested against its
+ * image in 64 bits before an address is formed.  tests/ct_augment_twin.py is this contract in numpy; DESIGN.md section 19
+ * states it in full.
+ * Limits, refused with PVV_E_ARG beyond them: 1 <= B <= 65535, sides in [1, 16384], 1 <= N <= PVV_CT_AUGMENT_MAX_N.
+ *
+ * pvv_ct_augment's params: B records of PVV_CT_AUGMENT_PARAM_BYTES on the device, 8-byte aligned:
+ *   binary64 inv_in[6] (the inverse of trans_input), inv_out[6] (of trans_output), light[3] (eigvec . (eigval * alpha));
+ *   float32 a[3], oma[3] (alpha and 1 - alpha of the three colour steps in the drawn order, each rounded to float32);
+ *   int32 order[3] (0 brightness, 1 contrast, 2 saturation in the drawn order), int32 padding
+ * ---------------------------------------------------------------------- */
+#define PVV_CT_AUGMENT_MAX_N 16
+#define PVV_CT_AUGMENT_PARAM_BYTES 160
+#define PVV_CT_BOXES_LINEAR 0
+#define PVV_CT_BOXES_NEAREST 1
+
+/* U:86-97 for every instance of a batch.  d_bg [B,H,W,3] uint8, d_inst_img [B,N,h,w,3] uint8, d_inst_mask [B,N,h,w] uint8
+ * (the object: != 0), d_num [B] int32 (instances n >= num[b] are skipped), d_place_u [B,N,2] binary64 in [0, 1): the uniforms
+ * of dst_y and dst_x.  Writes d_img [B,H,W,3] uint8, d_label [B,H,W] uint8 (0 background, n + 1 instance n) and d_place [B,N,6]
+ * int32 (y_min, x_min, h, w, dst_y, dst_x; h = y_max - y_min, w = x_max - x_min as U:90 has them; a skipped instance -- beyond
+ * num[b] or with an empty mask, where the reference raises -- is (0, 0, -1, -1, 0, 0)).  randint(lo, hi) = lo + floor(u * (hi - lo))
+ * for hi > lo, lo otherwise (an instance larger than the canvas: its pixels outside the canvas are dropped).  Two launches:
+ * the boxes with the placements, then one lane per canvas pixel that walks the instances from the last to the first and takes
+ * the first whose mask covers it -- a gather: every pixel has one owner, no atomics. */
+int pvv_ct_compose(const uint8_t *d_bg, const uint8_t *d_inst_img, const uint8_t *d_inst_mask, const int32_t *d_num,
+                   const double *d_place_u, int B, int H, int W, int N, int h, int w, uint8_t *d_img, uint8_t *d_label,
+                   int32_t *d_place, void *stream);
+
+/* Host-only.  Bytes pvv_ct_augment needs: the box accumulators [B,N,4] int32, one binary64 grey partial per (image, 64 x 4
+ * tile of the input) and the grey means; 0 with pvv_last_error set when a size is refused. */
+size_t pvv_ct_augment_workspace_bytes(int B, int N, int ih, int iw);
+
+/* U:46-63 and C:58-70 for a batch.  d_img [B,H,W,3] uint8 -> d_orig [B,ih,iw,3] uint8 (the 8-bit bilinear warp of
+ * pvv_crop_boxes through inv_in, zero border) and d_inp [B,3,ih,iw] float32: with train != 0 the colour steps of G:202-210 on
+ * float32(orig) / 255 (grey = (c0 * 0.114f + c1 * 0.587f) + c2 * 0.299f, its mean the binary64 fixed-tree sum divided by ih * iw
+ * and rounded once to float32; all three steps use the grey and the mean of the image before any step; the lighting vector is
+ * added in binary64 and rounded once), then (x - mean) / std in float32; with train == 0 the normalisation alone.  h_mean,
+ * h_std: 3 float32 each on the host.  d_label [B,H,W] uint8 (NULL: no boxes, N and d_boxes are ignored) -> d_boxes [B,N,4]
+ * int32 (x, y, x2, y2) on the oh x ow output map: an output pixel belongs to instance i iff, PVV_CT_BOXES_LINEAR, one of the
+ * four taps of the 8-bit bilinear rule through inv_out with a non-zero weight carries label i + 1 (= warpAffine(float mask,
+ * INTER_LINEAR) != 0) or, PVV_CT_BOXES_NEAREST, the tap of the nearest rule of pvv_uncrop_mask does; then
+ * (xmin, ymin, min(xmax + 1, ow - 1), min(ymax + 1, oh - 1)) as boundingRect and C:67-68 give it, (0, 0, 0, 0) for an instance
+ * without a pixel.  A fill and at most five launches. */
+int pvv_ct_augment(const uint8_t *d_img, const uint8_t *d_label, int B, int H, int W, int N, int ih, int iw, int oh, int ow,
+                   int train, int boxes_mode, const void *d_params, const float *h_mean, const float *h_std, void *d_workspace,
+                   size_t workspace_bytes, uint8_t *d_orig, float *d_inp, int32_t *d_boxes, void *stream);
+
+/* ------------------------------------------------------------------------
  * Detector training: heat-map targets and the detector loss (ABI v8, additive).  Citations:
  *   P = lib/datasets/tless_train/ct.py:46-66 (prepare_detection, called per object at :86-95)
  *   G = lib/utils/data_utils.py:10-65 (gaussian_radius :10-33, gaussian2D :36-47, draw_umich_gaussian :50-65)
