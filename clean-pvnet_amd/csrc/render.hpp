@@ -1,0 +1,570 @@
+// render.hpp -- shaded colour images, instance labels and depth of a batch of scenes on the device (include/pvnet_vote.h,
+// "Colour renders").  Included at the end of pvnet_vote.hip after ct_augment.hpp: built with -ffp-contract=off, every double
+// operation below rounds once, in the order written, so that the numpy twin (tests/render_twin.py) gives the same bytes.
+//
+// The coverage code restates that of pvnet_vsd.hip (snapping, near clip, edge functions, the owns-its-line rule, the sweep by
+// piece size) because that library does not record which triangle owns a sample; tests/test_gpu_render.py holds the two
+// rasterisers to the same depth bits.
+//
+//   k_rc_vertices  grid (vertex tiles, B*M): eye-space coordinates in binary64 and the snapped image coordinates of every
+//                  (instance, vertex), once.
+//   k_rc_raster    grid (tiles of 256 faces, B*M).  A lane sets up one face; a piece whose bounding box holds at most
+//                  kRcSmall samples is swept by its own lane, every other piece by the whole wave, 64 blocks of 8x8 samples at a
+//                  time.  Every covered sample offers (bits of float32(Z) << 32) | (m << 24) | f to the 8-byte key image with one
+//                  unsigned 64-bit atomicMin: nearest surface, then lowest instance, then lowest face.
+//   k_rc_shade     one lane per four consecutive pixels of the flattened batch: the owner's colour, label, depth and face, or the
+//                  background; 12 bytes of img leave as three dwords, label as one, depth and face as 16 bytes.  The last group
+//                  (fewer than four pixels) is stored element by element.  Areas: an LDS histogram per block for the block's first
+//                  image, one integer atomic per non-zero bin; a pixel of a later image in the same block adds directly.
+//
+// No float atomics.  Reference behaviour restated: lib/utils/linemod/opengl_renderer.py:171-179,
+// lib/datasets/tless/opengl_renderer.py:150-156 (render(mode='rgb')), lib/utils/linemod/opengl_backend.py:21-67 (the shaders).
+//
+// Index bounds: instance = blockIdx.y < B*M; its object o is used only when 0 <= o < O and its range row satisfies
+// 0 <= first, 0 <= count <= Nmax (Fmax), first + count <= N (F) -- tested on the device before anything is read through it
+// (rc_range).  Vertex i < count <= Nmax indexes slot instance*Nmax + i of the workspace; a face row is used only when its three
+// indices lie in [0, count).  Every sample a kernel touches satisfies 0 <= x < W and 0 <= y < H because a piece's bounding box is
+// clamped to the image rectangle before it is swept; the key image of image b starts at b*H*W.  k_rc_shade: pixel p < B*H*W, the
+// key's instance m < M and face f < count are tested again before the vertex slots are read; histogram bin = label <= M <= 255.
+#pragma once
+
+#include <climits>
+
+namespace {
+
+constexpr int kRcSmall = 32;            // a piece with at most this many samples in its bounding box is swept by its own lane
+constexpr int kRcBadCoord = INT_MIN;    // snapped coordinate of a vertex that has none
+constexpr double kRcSnapLimit = 268435456.0;   // 2^28
+constexpr int kRcMaxSide = 16384;
+constexpr int kRcMaxM = 255;
+constexpr int kRcMaxFaces = 1 << 24;
+constexpr unsigned long long kRcEmpty = ~0ull;
+
+struct RcVtx {                          // 32 bytes, one per (instance, vertex slot)
+    double X, Y, Z;
+    int U, V;
+};
+static_assert(sizeof(RcVtx) == 32, "pvnet_vote.h promises 32 bytes per vertex slot");
+
+struct RcCam { double fx, s, cx, fy, cy; };
+
+struct RcPiece {                        // a clipped, oriented (positive area) triangle in snapped coordinates, with its samples
+    int ax, ay, bx, by, cx, cy;
+    int xmin, ymin, w, h;               // w == 0: no piece
+};
+
+struct RcPlane { double n0, n1, n2, num; };
+
+struct RcRange { int v0, vn, f0, fn; bool ok; };
+
+struct RcScene {                        // what the three kernels share
+    const float *pts;
+    const uint8_t *colors;
+    const int32_t *faces, *ranges, *obj;
+    const double *pose, *K;
+    int N, F, O, Nmax, Fmax, K_batched, B, M, H, W;
+    double near, far;
+};
+
+struct __attribute__((aligned(16))) RcVec4f { float v[4]; };
+struct __attribute__((aligned(16))) RcVec4i { int v[4]; };
+struct __attribute__((aligned(16))) RcVec2k { unsigned long long v[2]; };
+
+__device__ RcCam rc_load_cam(const double *K)
+{
+    RcCam c;
+    c.fx = K[0], c.s = K[1], c.cx = K[2], c.fy = K[4], c.cy = K[5];
+    return c;
+}
+
+__device__ bool rc_pose_finite(const double *P)
+{
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) ok = ok && isfinite(P[i]);
+    return ok;
+}
+
+// The object of instance `inst` and its rows of the mesh, tested against the mesh before use; ok == false: no instance.
+__device__ RcRange rc_range(const RcScene &s, int inst)
+{
+    RcRange r = {0, 0, 0, 0, false};
+    const int o = s.obj ? s.obj[inst] : 0;
+    if (o < 0 || o >= s.O) return r;
+    const int32_t *q = s.ranges + 4 * (size_t)o;
+    r.v0 = q[0], r.vn = q[1], r.f0 = q[2], r.fn = q[3];
+    r.ok = r.v0 >= 0 && r.vn >= 0 && r.vn <= s.Nmax && r.v0 <= s.N - r.vn && r.f0 >= 0 && r.fn >= 0 && r.fn <= s.Fmax &&
+           r.f0 <= s.F - r.fn;
+    return r;
+}
+
+// u = (fx*X + s*Y)/Z + cx, v = (fy*Y)/Z + cy, snapped to 8 sub-pixel bits; kRcBadCoord when out of range or not a number
+__device__ void rc_project_snap(const RcCam &c, double X, double Y, double Z, int *U, int *V)
+{
+    const double u = (c.fx * X + c.s * Y) / Z + c.cx;
+    const double v = (c.fy * Y) / Z + c.cy;
+    const double Ud = floor(256.0 * u + 0.5), Vd = floor(256.0 * v + 0.5);
+    const bool ok = fabs(Ud) <= kRcSnapLimit && fabs(Vd) <= kRcSnapLimit;      // false for NaN
+    *U = ok ? (int)Ud : kRcBadCoord;
+    *V = ok ? (int)Vd : kRcBadCoord;
+}
+
+__global__ __launch_bounds__(kBlock) void k_rc_vertices(RcScene s, RcVtx *__restrict__ vtx)
+{
+    const int inst = blockIdx.y;
+    const RcRange r = rc_range(s, inst);
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (!r.ok || i >= r.vn) return;
+    const double *T = s.pose + (size_t)inst * 12;
+    const RcCam c = rc_load_cam(s.K + (s.K_batched ? (size_t)(inst / s.M) * 9 : 0));
+    const float *p = s.pts + ((size_t)r.v0 + i) * 3;
+    const double x = (double)p[0], y = (double)p[1], z = (double)p[2];
+    RcVtx o;
+    o.X = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
+    o.Y = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
+    o.Z = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
+    o.U = o.V = kRcBadCoord;
+    if (o.Z >= s.near) rc_project_snap(c, o.X, o.Y, o.Z, &o.U, &o.V);
+    vtx[(size_t)inst * s.Nmax + i] = o;
+}
+
+// The vertex where the edge from the inside vertex p to the outside vertex q meets Z = near, projected and snapped.
+__device__ void rc_clip_snap(const RcCam &c, const RcVtx &p, const RcVtx &q, double near, int *U, int *V)
+{
+    const double t = (near - p.Z) / (q.Z - p.Z);
+    const double X = p.X + t * (q.X - p.X);
+    const double Y = p.Y + t * (q.Y - p.Y);
+    rc_project_snap(c, X, Y, near, U, V);
+}
+
+__device__ RcPiece rc_make_piece(int U0, int V0, int U1, int V1, int U2, int V2, int W, int H)
+{
+    RcPiece t;
+    t.w = t.h = 0;
+    t.ax = t.ay = t.bx = t.by = t.cx = t.cy = t.xmin = t.ymin = 0;
+    if (U0 == kRcBadCoord || U1 == kRcBadCoord || U2 == kRcBadCoord) return t;
+    const long long area2 = (long long)(U1 - U0) * (V2 - V0) - (long long)(V1 - V0) * (U2 - U0);
+    if (area2 == 0) return t;
+    if (area2 < 0) {
+        int k = U1; U1 = U2; U2 = k;
+        k = V1; V1 = V2; V2 = k;
+    }
+    // samples (256x + 128, 256y + 128) inside the vertices' box: x >= (Umin - 128)/256, x <= (Umax - 128)/256
+    int xmin = (min(U0, min(U1, U2)) - 128 + 255) >> 8, xmax = (max(U0, max(U1, U2)) - 128) >> 8;
+    int ymin = (min(V0, min(V1, V2)) - 128 + 255) >> 8, ymax = (max(V0, max(V1, V2)) - 128) >> 8;
+    xmin = max(xmin, 0);
+    ymin = max(ymin, 0);
+    xmax = min(xmax, W - 1);
+    ymax = min(ymax, H - 1);
+    if (xmin > xmax || ymin > ymax) return t;
+    t.ax = U0; t.ay = V0; t.bx = U1; t.by = V1; t.cx = U2; t.cy = V2;
+    t.xmin = xmin; t.ymin = ymin; t.w = xmax - xmin + 1; t.h = ymax - ymin + 1;
+    return t;
+}
+
+// E = dx*(py - ay) - dy*(px - ax) > 0, or = 0 on an edge that owns its line.  |dx|, |dy| <= 2^29 and |py - ay|, |px - ax| <
+// 2^29: every product fits 59 bits.
+__device__ bool rc_edge_in(int ax, int ay, int bx, int by, int px, int py)
+{
+    const int dx = bx - ax, dy = by - ay;
+    const long long E = (long long)dx * (py - ay) - (long long)dy * (px - ax);
+    const bool owns = dy > 0 || (dy == 0 && dx > 0);
+    return E > 0 || (E == 0 && owns);
+}
+
+__device__ bool rc_covered(const RcPiece &t, int x, int y)
+{
+    const int px = 256 * x + 128, py = 256 * y + 128;
+    return rc_edge_in(t.ax, t.ay, t.bx, t.by, px, py) && rc_edge_in(t.bx, t.by, t.cx, t.cy, px, py) &&
+           rc_edge_in(t.cx, t.cy, t.ax, t.ay, px, py);
+}
+
+// The largest value an edge function takes on the samples x0..x1, y0..y1 is negative: no sample of the block is inside.
+__device__ bool rc_edge_rejects(int ax, int ay, int bx, int by, int x0, int y0, int x1, int y1)
+{
+    const int dx = bx - ax, dy = by - ay;
+    const int py = 256 * (dx > 0 ? y1 : y0) + 128, px = 256 * (dy > 0 ? x0 : x1) + 128;
+    return (long long)dx * (py - ay) - (long long)dy * (px - ax) < 0;
+}
+
+__device__ bool rc_block_rejected(const RcPiece &t, int x0, int y0, int x1, int y1)
+{
+    return rc_edge_rejects(t.ax, t.ay, t.bx, t.by, x0, y0, x1, y1) || rc_edge_rejects(t.bx, t.by, t.cx, t.cy, x0, y0, x1, y1) ||
+           rc_edge_rejects(t.cx, t.cy, t.ax, t.ay, x0, y0, x1, y1);
+}
+
+// dy = ((y+0.5) - cy)/fy, dx = (((x+0.5) - cx) - s*dy)/fx, den = (n0*dx + n1*dy) + n2, Z = num/den; false when den == 0
+__device__ bool rc_plane_depth(const RcPlane &pl, const RcCam &c, int x, int y, double *dx_, double *dy_, double *Z)
+{
+    const double dy = (((double)y + 0.5) - c.cy) / c.fy;
+    const double dx = ((((double)x + 0.5) - c.cx) - c.s * dy) / c.fx;
+    const double den = (pl.n0 * dx + pl.n1 * dy) + pl.n2;
+    *dx_ = dx, *dy_ = dy;
+    if (den == 0.0) return false;
+    *Z = pl.num / den;
+    return true;
+}
+
+// One covered sample offers its key; `tag` = (m << 24) | f.
+__device__ void rc_offer(unsigned long long *__restrict__ img, int W, int x, int y, const RcPlane &pl, const RcCam &c, double near,
+                         double far, unsigned tag)
+{
+    double dx, dy, Z;
+    if (!rc_plane_depth(pl, c, x, y, &dx, &dy, &Z)) return;
+    if (Z >= near && Z <= far)
+        atomicMin(img + (size_t)y * W + x, ((unsigned long long)__float_as_uint((float)Z) << 32) | tag);
+}
+
+__device__ int rc_rl(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
+
+__device__ double rc_rl(double v, int lane)
+{
+    return __hiloint2double(rc_rl(__double2hiint(v), lane), rc_rl(__double2loint(v), lane));
+}
+
+__device__ RcPiece rc_rl(const RcPiece &t, int lane)
+{
+    RcPiece o;
+    o.ax = rc_rl(t.ax, lane); o.ay = rc_rl(t.ay, lane); o.bx = rc_rl(t.bx, lane); o.by = rc_rl(t.by, lane);
+    o.cx = rc_rl(t.cx, lane); o.cy = rc_rl(t.cy, lane);
+    o.xmin = rc_rl(t.xmin, lane); o.ymin = rc_rl(t.ymin, lane); o.w = rc_rl(t.w, lane); o.h = rc_rl(t.h, lane);
+    return o;
+}
+
+// One piece per lane (w == 0: none).  Small pieces by their own lane, the others by the whole wave.  Called by whole waves.
+__device__ void rc_sweep(const RcPiece &mine, const RcPlane &pl, unsigned tag, unsigned long long *__restrict__ img, int W,
+                         const RcCam &c, double near, double far)
+{
+    const int lane = threadIdx.x & 63;
+    const int cnt = mine.w * mine.h;                       // <= 2^28 by kRcMaxSide
+    const bool small = cnt <= kRcSmall;
+    if (small) {
+        int x = mine.xmin, y = mine.ymin;
+        for (int i = 0; i < cnt; ++i) {
+            if (rc_covered(mine, x, y)) rc_offer(img, W, x, y, pl, c, near, far, tag);
+            if (++x == mine.xmin + mine.w) {
+                x = mine.xmin;
+                ++y;
+            }
+        }
+    }
+    unsigned long long big = __ballot(!small);
+    while (big) {
+        const int src = __ffsll((long long)big) - 1;
+        big &= big - 1;
+        const RcPiece t = rc_rl(mine, src);
+        RcPlane q;
+        q.n0 = rc_rl(pl.n0, src); q.n1 = rc_rl(pl.n1, src); q.n2 = rc_rl(pl.n2, src); q.num = rc_rl(pl.num, src);
+        const unsigned qtag = (unsigned)rc_rl((int)tag, src);
+        const int xmax = t.xmin + t.w - 1, ymax = t.ymin + t.h - 1;
+        const int bx0 = t.xmin >> 3, by0 = t.ymin >> 3;
+        const int nbx = (xmax >> 3) - bx0 + 1, nby = (ymax >> 3) - by0 + 1;
+        const int nblocks = nbx * nby;
+        for (int base = 0; base < nblocks; base += 64) {
+            const int bi = base + lane;
+            const int by = bi / nbx, bx = bi - by * nbx;
+            bool live = bi < nblocks;
+            if (live) {
+                const int x0 = max((bx0 + bx) << 3, t.xmin), y0 = max((by0 + by) << 3, t.ymin);
+                const int x1 = min(((bx0 + bx) << 3) + 7, xmax), y1 = min(((by0 + by) << 3) + 7, ymax);
+                live = !rc_block_rejected(t, x0, y0, x1, y1);
+            }
+            unsigned long long todo = __ballot(live);
+            while (todo) {
+                const int j = __ffsll((long long)todo) - 1;
+                todo &= todo - 1;
+                const int x = ((bx0 + rc_rl(bx, j)) << 3) + (lane & 7), y = ((by0 + rc_rl(by, j)) << 3) + (lane >> 3);
+                if (x >= t.xmin && x <= xmax && y >= t.ymin && y <= ymax && rc_covered(t, x, y))
+                    rc_offer(img, W, x, y, q, c, near, far, qtag);
+            }
+        }
+    }
+}
+
+__device__ void rc_rotate_left(RcVtx &a, RcVtx &b, RcVtx &c, int r)
+{
+    if (r == 1) {
+        const RcVtx k = a; a = b; b = c; c = k;
+    } else if (r == 2) {
+        const RcVtx k = c; c = b; b = a; a = k;
+    }
+}
+
+// n = a x b with a = v1 - v0, b = v2 - v0, num = (n0*v00 + n1*v01) + n2*v02
+__device__ RcPlane rc_plane(const RcVtx &v0, const RcVtx &v1, const RcVtx &v2, double *a, double *b)
+{
+    a[0] = v1.X - v0.X, a[1] = v1.Y - v0.Y, a[2] = v1.Z - v0.Z;
+    b[0] = v2.X - v0.X, b[1] = v2.Y - v0.Y, b[2] = v2.Z - v0.Z;
+    RcPlane pl;
+    pl.n0 = a[1] * b[2] - a[2] * b[1];
+    pl.n1 = a[2] * b[0] - a[0] * b[2];
+    pl.n2 = a[0] * b[1] - a[1] * b[0];
+    pl.num = (pl.n0 * v0.X + pl.n1 * v0.Y) + pl.n2 * v0.Z;
+    return pl;
+}
+
+__global__ __launch_bounds__(kBlock) void k_rc_raster(RcScene s, const RcVtx *__restrict__ vtx, unsigned long long *__restrict__ keys)
+{
+    const int inst = blockIdx.y;
+    const RcRange r = rc_range(s, inst);
+    if (!r.ok || !rc_pose_finite(s.pose + (size_t)inst * 12)) return;      // block-uniform: the instance draws nothing
+    const int b = inst / s.M, m = inst - b * s.M;
+    const RcCam c = rc_load_cam(s.K + (s.K_batched ? (size_t)b * 9 : 0));
+    const int f = blockIdx.x * kBlock + threadIdx.x;
+    const int W = s.W, H = s.H;
+    const double near = s.near;
+    RcPiece pc0 = rc_make_piece(kRcBadCoord, 0, 0, 0, 0, 0, W, H), pc1 = pc0;
+    RcPlane pl = {0.0, 0.0, 0.0, 0.0};
+    if (f < r.fn) {
+        const int32_t *row = s.faces + ((size_t)r.f0 + f) * 3;
+        const int i0 = row[0], i1 = row[1], i2 = row[2];
+        if (i0 >= 0 && i0 < r.vn && i1 >= 0 && i1 < r.vn && i2 >= 0 && i2 < r.vn) {
+            const RcVtx *vp = vtx + (size_t)inst * s.Nmax;
+            RcVtx v0 = vp[i0], v1 = vp[i1], v2 = vp[i2];
+            const int in = (v0.Z >= near ? 1 : 0) | (v1.Z >= near ? 2 : 0) | (v2.Z >= near ? 4 : 0);
+            if (in) {
+                double a[3], bb[3];
+                pl = rc_plane(v0, v1, v2, a, bb);
+                if (in == 7) {
+                    pc0 = rc_make_piece(v0.U, v0.V, v1.U, v1.V, v2.U, v2.V, W, H);
+                } else if (in == 1 || in == 2 || in == 4) {         // one vertex inside: (a, ab, ac)
+                    rc_rotate_left(v0, v1, v2, in == 1 ? 0 : in == 2 ? 1 : 2);
+                    int Ub, Vb, Uc, Vc;
+                    rc_clip_snap(c, v0, v1, near, &Ub, &Vb);
+                    rc_clip_snap(c, v0, v2, near, &Uc, &Vc);
+                    pc0 = rc_make_piece(v0.U, v0.V, Ub, Vb, Uc, Vc, W, H);
+                } else {                                            // one vertex outside, c: (a, b, bc) and (a, bc, ac)
+                    rc_rotate_left(v0, v1, v2, in == 3 ? 0 : in == 6 ? 1 : 2);
+                    int Ub, Vb, Ua, Va;
+                    rc_clip_snap(c, v1, v2, near, &Ub, &Vb);
+                    rc_clip_snap(c, v0, v2, near, &Ua, &Va);
+                    pc0 = rc_make_piece(v0.U, v0.V, v1.U, v1.V, Ub, Vb, W, H);
+                    pc1 = rc_make_piece(v0.U, v0.V, Ub, Vb, Ua, Va, W, H);
+                }
+            }
+        }
+    }
+    const unsigned tag = ((unsigned)m << 24) | ((unsigned)f & 0xffffffu);   // f < fn <= 2^24 wherever a piece exists
+    unsigned long long *img = keys + (size_t)b * H * W;
+    rc_sweep(pc0, pl, tag, img, W, c, near, s.far);
+    if (__any(pc1.w != 0)) rc_sweep(pc1, pl, tag, img, W, c, near, s.far);
+}
+
+struct RcPixel { uint8_t c[3], label; float z; int face; };
+
+// Output 0 for v < 0 or NaN, 255 for v > 255, else floor(v + 0.5)
+__device__ uint8_t rc_to_u8(double v)
+{
+    if (!(v >= 0.0)) return 0;
+    if (v > 255.0) return 255;
+    return (uint8_t)(int)floor(v + 0.5);
+}
+
+// The shading contract of the header for the owner (m, f) of pixel (x, y) of image b; false when the key names nothing that
+// can be read (never for a key the raster wrote).
+__device__ bool rc_shade_owner(const RcScene &s, const RcVtx *__restrict__ vtx, int b, int x, int y, int m, int f, double ambient,
+                               RcPixel *out)
+{
+    if (m >= s.M) return false;
+    const int inst = b * s.M + m;
+    const RcRange r = rc_range(s, inst);
+    if (!r.ok || f >= r.fn) return false;
+    const int32_t *row = s.faces + ((size_t)r.f0 + f) * 3;
+    const int i0 = row[0], i1 = row[1], i2 = row[2];
+    if (i0 < 0 || i0 >= r.vn || i1 < 0 || i1 >= r.vn || i2 < 0 || i2 >= r.vn) return false;
+    const RcVtx *vp = vtx + (size_t)inst * s.Nmax;
+    const RcVtx v0 = vp[i0], v1 = vp[i1], v2 = vp[i2];
+    const RcCam c = rc_load_cam(s.K + (s.K_batched ? (size_t)b * 9 : 0));
+    double a[3], bb[3], dx, dy, Zd = 0.0;
+    const RcPlane pl = rc_plane(v0, v1, v2, a, bb);
+    rc_plane_depth(pl, c, x, y, &dx, &dy, &Zd);
+    const double n[3] = {pl.n0, pl.n1, pl.n2};
+    const double P[3] = {dx * Zd, dy * Zd, Zd};
+    const double q[3] = {P[0] - v0.X, P[1] - v0.Y, P[2] - v0.Z};
+    const double nn = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2];
+    const double qb[3] = {q[1] * bb[2] - q[2] * bb[1], q[2] * bb[0] - q[0] * bb[2], q[0] * bb[1] - q[1] * bb[0]};
+    const double aq[3] = {a[1] * q[2] - a[2] * q[1], a[2] * q[0] - a[0] * q[2], a[0] * q[1] - a[1] * q[0]};
+    const double w1 = ((qb[0] * n[0] + qb[1] * n[1]) + qb[2] * n[2]) / nn;
+    const double w2 = ((aq[0] * n[0] + aq[1] * n[1]) + aq[2] * n[2]) / nn;
+    const double w0 = (1.0 - w1) - w2;
+    const double pp = (P[0] * P[0] + P[1] * P[1]) + P[2] * P[2];
+    const double diffuse = fabs(pl.num) / sqrt(nn * pp);
+    const double t = ambient + diffuse;
+    const double light = t > 1.0 ? 1.0 : t;
+    const uint8_t *C0 = s.colors + ((size_t)r.v0 + i0) * 3, *C1 = s.colors + ((size_t)r.v0 + i1) * 3, *C2 = s.colors + ((size_t)r.v0 + i2) * 3;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double col = (w0 * (double)C0[k] + w1 * (double)C1[k]) + w2 * (double)C2[k];
+        out->c[k] = rc_to_u8(light * col);
+    }
+    out->label = (uint8_t)(m + 1);
+    out->z = (float)Zd;
+    out->face = f;
+    return true;
+}
+
+__global__ __launch_bounds__(kBlock) void k_rc_shade(RcScene s, const RcVtx *__restrict__ vtx, const unsigned long long *__restrict__ keys,
+                                                     const uint8_t *__restrict__ bg, int bg_vec, uint32_t bg_color, double ambient,
+                                                     uint8_t *__restrict__ img, uint8_t *__restrict__ label, float *__restrict__ depth,
+                                                     int32_t *__restrict__ area, int32_t *__restrict__ face)
+{
+    __shared__ int s_hist[kBlock];
+    const int tid = threadIdx.x;
+    s_hist[tid] = 0;
+    __syncthreads();
+    const size_t HW = (size_t)s.H * s.W, total = HW * s.B;
+    const size_t first = (size_t)blockIdx.x * kBlock * 4;                 // < total by the grid
+    const size_t b0 = first / HW;
+    const size_t g = (size_t)blockIdx.x * kBlock + tid, p0 = 4 * g;
+    if (p0 < total) {
+        const int cnt = total - p0 >= 4 ? 4 : (int)(total - p0);
+        unsigned long long key[4] = {kRcEmpty, kRcEmpty, kRcEmpty, kRcEmpty};
+        if (cnt == 4) {                                                  // 32 bytes at a multiple of 32
+            const RcVec2k k0 = *reinterpret_cast<const RcVec2k *>(keys + p0), k1 = *reinterpret_cast<const RcVec2k *>(keys + p0 + 2);
+            key[0] = k0.v[0], key[1] = k0.v[1], key[2] = k1.v[0], key[3] = k1.v[1];
+        } else {
+            for (int j = 0; j < cnt; ++j) key[j] = keys[p0 + j];
+        }
+        uint8_t bgb[12];
+        const bool any_empty = key[0] == kRcEmpty || key[1] == kRcEmpty || key[2] == kRcEmpty || key[3] == kRcEmpty;
+        if (bg && any_empty) {
+            if (bg_vec && cnt == 4) {
+                const uint32_t *b4 = reinterpret_cast<const uint32_t *>(bg) + 3 * g;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const uint32_t q = b4[k];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) bgb[4 * k + j] = (uint8_t)(q >> (8 * j));
+                }
+            } else {
+                for (int j = 0; j < 3 * cnt; ++j) bgb[j] = bg[p0 * 3 + j];
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 12; ++j) bgb[j] = (uint8_t)(bg_color >> (8 * (j % 3)));
+        }
+        size_t b = p0 / HW;
+        const size_t rem = p0 - b * HW;
+        int y = (int)(rem / (size_t)s.W), x = (int)(rem - (size_t)y * s.W);
+        RcPixel px[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            RcPixel o;
+            o.c[0] = bgb[3 * j], o.c[1] = bgb[3 * j + 1], o.c[2] = bgb[3 * j + 2];
+            o.label = 0, o.z = 0.f, o.face = -1;
+            if (j < cnt && key[j] != kRcEmpty) {
+                const unsigned tag = (unsigned)key[j];
+                RcPixel owned;
+                if (rc_shade_owner(s, vtx, (int)b, x, y, (int)(tag >> 24), (int)(tag & 0xffffffu), ambient, &owned)) {
+                    o = owned;
+                    if (b == b0) atomicAdd(&s_hist[o.label], 1);
+                    else atomicAdd(area + b * s.M + (o.label - 1), 1);
+                }
+            }
+            px[j] = o;
+            if (++x == s.W) {
+                x = 0;
+                if (++y == s.H) y = 0, ++b;
+            }
+        }
+        if (cnt == 4) {
+            uint32_t w[3] = {0, 0, 0};
+#pragma unroll
+            for (int j = 0; j < 12; ++j) w[j / 4] |= (uint32_t)px[j / 3].c[j % 3] << (8 * (j % 4));
+            uint32_t *o4 = reinterpret_cast<uint32_t *>(img) + 3 * g;
+            o4[0] = w[0], o4[1] = w[1], o4[2] = w[2];
+            reinterpret_cast<uint32_t *>(label)[g] = (uint32_t)px[0].label | ((uint32_t)px[1].label << 8) | ((uint32_t)px[2].label << 16) |
+                                                     ((uint32_t)px[3].label << 24);
+            RcVec4f z;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) z.v[j] = px[j].z;
+            reinterpret_cast<RcVec4f *>(depth)[g] = z;
+            if (face) {
+                RcVec4i fv;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) fv.v[j] = px[j].face;
+                reinterpret_cast<RcVec4i *>(face)[g] = fv;
+            }
+        } else {                                                         // the last one to three pixels of the batch
+            for (int j = 0; j < cnt; ++j) {
+                const size_t p = p0 + j;
+                img[p * 3] = px[j].c[0], img[p * 3 + 1] = px[j].c[1], img[p * 3 + 2] = px[j].c[2];
+                label[p] = px[j].label;
+                depth[p] = px[j].z;
+                if (face) face[p] = px[j].face;
+            }
+        }
+    }
+    __syncthreads();
+    if (tid >= 1 && tid <= s.M && s_hist[tid] != 0) atomicAdd(area + b0 * s.M + (tid - 1), s_hist[tid]);
+}
+
+struct RcLayout { size_t vtx, keys, total; };
+
+RcLayout rc_layout(int B, int M, int Nmax, int H, int W)
+{
+    RcLayout L;
+    L.vtx = 0;
+    L.keys = aug_up(sizeof(RcVtx) * (size_t)B * M * Nmax);
+    L.total = L.keys + aug_up(sizeof(unsigned long long) * (size_t)B * H * W);
+    return L;
+}
+
+int rc_check(int B, int M, int Nmax, int H, int W)
+{
+    if (B < 1 || M < 1 || M > kRcMaxM || (long long)B * M > 65535) return fail(PVV_E_ARG, "render: B >= 1, M in [1, 255] and B*M <= 65535 are required");
+    if (H < 1 || W < 1 || H > kRcMaxSide || W > kRcMaxSide) return fail(PVV_E_ARG, "render: the image's sides must lie in [1, 16384]");
+    if (Nmax < 1 || Nmax > INT_MAX / 3) return fail(PVV_E_ARG, "render: the largest vertex count must lie in [1, 2^31 / 3)");
+    if (((size_t)B * H * W + 1023) / 1024 > (size_t)INT_MAX) return fail(PVV_E_ARG, "render: B*H*W must stay below 2^41");
+    return PVV_OK;
+}
+
+}  // namespace
+
+PVV_EXPORT size_t pvv_render_workspace_bytes(int B, int M, int Nmax, int H, int W)
+{
+    if (rc_check(B, M, Nmax, H, W)) return 0;
+    return rc_layout(B, M, Nmax, H, W).total;
+}
+
+PVV_EXPORT int pvv_render_color(const float *d_pts, const uint8_t *d_colors, const int32_t *d_faces, int N, int F, const int32_t *d_ranges,
+                                int O, int Nmax, int Fmax, const double *d_pose, const int32_t *d_obj, const double *d_K, int K_batched,
+                                const uint8_t *d_bg, const uint8_t *h_bg_color, int B, int M, int H, int W, double near, double far,
+                                double ambient, void *d_workspace, size_t workspace_bytes, uint8_t *d_img, uint8_t *d_label, float *d_depth,
+                                int32_t *d_area, int32_t *d_face, void *stream)
+{
+    if (int e = rc_check(B, M, Nmax, H, W)) return e;
+    if (N < 1 || N > INT_MAX / 3 || F < 0 || F > INT_MAX / 3 || Nmax > N) return fail(PVV_E_ARG, "render: N in [1, 2^31 / 3), F in [0, 2^31 / 3) and Nmax <= N are required");
+    if (Fmax < 0 || Fmax > kRcMaxFaces || Fmax > F) return fail(PVV_E_ARG, "render: an object may have at most 2^24 faces (and no more than F)");
+    if (O < 1) return fail(PVV_E_ARG, "render: at least one object is required");
+    if (!(near > 0.0) || !(far >= near) || !(ambient >= 0.0)) return fail(PVV_E_ARG, "render: 0 < near <= far and ambient >= 0 are required");
+    if (!d_pts || !d_colors || (F > 0 && !d_faces) || !d_ranges || !d_pose || !d_K || !h_bg_color || !d_workspace || !d_img || !d_label ||
+        !d_depth || !d_area)
+        return fail(PVV_E_ARG, "render: NULL pointer");
+    if ((uintptr_t)d_workspace % 32 != 0 || (uintptr_t)d_img % 4 != 0 || (uintptr_t)d_label % 4 != 0 || (uintptr_t)d_depth % 16 != 0 ||
+        (uintptr_t)d_face % 16 != 0 || (uintptr_t)d_area % 4 != 0 || (uintptr_t)d_pose % 8 != 0 || (uintptr_t)d_K % 8 != 0)
+        return fail(PVV_E_ARG, "render: workspace must be 32-byte, depth and face 16-byte, pose and K 8-byte, img, label and area 4-byte aligned");
+    const RcLayout L = rc_layout(B, M, Nmax, H, W);
+    if (workspace_bytes < L.total) return fail(PVV_E_WORKSPACE, "render: workspace smaller than pvv_render_workspace_bytes()");
+    hipStream_t st = (hipStream_t)stream;
+    RcVtx *vtx = (RcVtx *)((uint8_t *)d_workspace + L.vtx);
+    unsigned long long *keys = (unsigned long long *)((uint8_t *)d_workspace + L.keys);
+    const size_t total = (size_t)B * H * W;
+    if (hipMemsetAsync(keys, 0xff, total * sizeof(unsigned long long), st) != hipSuccess) return fail(PVV_E_ARG, "render: hipMemsetAsync failed");
+    if (hipMemsetAsync(d_area, 0, sizeof(int32_t) * (size_t)B * M, st) != hipSuccess) return fail(PVV_E_ARG, "render: hipMemsetAsync failed");
+    RcScene s;
+    s.pts = d_pts, s.colors = d_colors, s.faces = d_faces, s.ranges = d_ranges, s.obj = d_obj, s.pose = d_pose, s.K = d_K;
+    s.N = N, s.F = F, s.O = O, s.Nmax = Nmax, s.Fmax = Fmax, s.K_batched = K_batched, s.B = B, s.M = M, s.H = H, s.W = W;
+    s.near = near, s.far = far;
+    if (Fmax > 0) {
+        hipLaunchKernelGGL(k_rc_vertices, dim3((Nmax + kBlock - 1) / kBlock, B * M), dim3(kBlock), 0, st, s, vtx);
+        if (int e = check_launch("k_rc_vertices")) return e;
+        hipLaunchKernelGGL(k_rc_raster, dim3((Fmax + kBlock - 1) / kBlock, B * M), dim3(kBlock), 0, st, s, (const RcVtx *)vtx, keys);
+        if (int e = check_launch("k_rc_raster")) return e;
+    }
+    const uint32_t bgc = (uint32_t)h_bg_color[0] | ((uint32_t)h_bg_color[1] << 8) | ((uint32_t)h_bg_color[2] << 16);
+    const int bg_vec = d_bg && (uintptr_t)d_bg % 4 == 0;
+    hipLaunchKernelGGL(k_rc_shade, dim3((unsigned)((total + 1023) / 1024)), dim3(kBlock), 0, st, s, (const RcVtx *)vtx,
+                       (const unsigned long long *)keys, d_bg, bg_vec, bgc, ambient, d_img, d_label, d_depth, d_area, d_face);
+    return check_launch("k_rc_shade");
+}

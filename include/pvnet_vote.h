@@ -665,6 +665,78 @@ int pvv_ct_augment(const uint8_t *d_img, const uint8_t *d_label, int B, int H, i
                    size_t workspace_bytes, uint8_t *d_orig, float *d_inp, int32_t *d_boxes, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Colour renders: shaded colour images, instance labels and depth of a batch of scenes, several objects per image with exact
+ * occlusion (ABI v8, additive; the newest section -- it stands in front of the two sections whose place at the end of this file
+ * is fixed).  Citations:
+ *   R = lib/utils/linemod/opengl_renderer.py:171-179 and lib/datasets/tless/opengl_renderer.py:150-156 (render(mode='rgb'), one
+ *       pose at a time through an OpenGL context)
+ *   S = lib/utils/linemod/opengl_backend.py:21-67 (the colour shaders), :243-247 (the read-back)
+ *   A = linemod_to_coco.py:184 (fused masks under 400 pixels are dropped: d_area decides that without a read-back)
+ * Device pointers, caller-owned workspace, the caller's stream last; nothing is read back, nothing synchronises, nothing is
+ * allocated and nothing is kept between calls.  No fused multiply-add anywhere, no float atomics: reruns give the same bytes,
+ * whatever the batch or the launch shape.  tests/render_twin.py is this contract in numpy.
+ * Limits, refused with PVV_E_ARG beyond them: 1 <= M <= 255, B*M <= 65535, sides in [1, 16384], at most 2^24 faces per object.
+ *
+ * The scene.  One mesh holds O objects: pts [N,3] float32, colors [N,3] uint8, faces [F,3] int32 with indices local to their
+ * object, ranges [O,4] int32 on the device = (first vertex, vertex count, first face, face count).  Image b holds the M
+ * instances pose[b,m] ([R | t], binary64) of the objects obj[b,m] (NULL: object 0 everywhere).  An instance with obj outside
+ * [0, O), with a range row that does not lie inside the mesh or exceeds Nmax / Fmax, or with a non-finite pose entry draws
+ * nothing; a face row with an index outside [0, vertex count of its object) is skipped.  All of this is tested on the device.
+ *
+ * Geometry: eye space, near clip, projection, snapping, coverage and the depth value are those of include/pvnet_vsd.h, word
+ * for word: binary64 eye space once per (instance, vertex); 8 sub-pixel bits; 64-bit integer edge functions with the
+ * owns-its-line rule; clip pieces with the new vertex computed in the p -> q direction; Z = num/den from the unclipped
+ * triangle's plane, kept when den != 0 and near <= Z <= far.  With M = 1 the depth image equals pvs_render_depth_batched's as
+ * bit patterns.
+ *
+ * Ownership: every covered, kept sample of face f of instance m offers the 64-bit key (bits of float32(Z) << 32) | (m << 24) | f
+ * and the pixel keeps the unsigned minimum (one integer atomic per sample): the nearest surface wins, equal float32 depths go
+ * to the lowest instance, then to the lowest face.
+ *
+ * Shading, per owned pixel (x, y), binary64, each line rounded once in this order:
+ *   v0, v1, v2 = the owner's eye-space vertices in face-row order;  a = v1 - v0;  b = v2 - v0
+ *   n = (a1*b2 - a2*b1, a2*b0 - a0*b2, a0*b1 - a1*b0);  num = (n0*v00 + n1*v01) + n2*v02
+ *   dy = ((y+0.5) - cy)/fy;  dx = (((x+0.5) - cx) - s*dy)/fx;  den = (n0*dx + n1*dy) + n2;  Zd = num/den
+ *   P = (dx*Zd, dy*Zd, Zd);  q = P - v0;  nn = (n0*n0 + n1*n1) + n2*n2
+ *   w1 = ((q x b) . n)/nn;  w2 = ((a x q) . n)/nn    (cross products in the component order of n, dots as (.0 + .1) + .2)
+ *   w0 = (1.0 - w1) - w2
+ *   c = (w0*C0 + w1*C1) + w2*C2 per channel, the uint8 vertex colours widened
+ *   pp = (P0*P0 + P1*P1) + P2*P2;  diffuse = |num| / sqrt(nn*pp)      (the light at the camera origin; a flat normal that
+ *                                                                      always faces the viewer, as dFdx x dFdy does in S)
+ *   t = ambient + diffuse;  light = t > 1.0 ? 1.0 : t;  v = light*c
+ *   output 0 for v < 0 or NaN, 255 for v > 255, else floor(v + 0.5)   (coverage comes from snapped coordinates: a sample may lie
+ *                                                                      up to 1/256 px outside the true triangle and a weight be
+ *                                                                      slightly negative; the clamp is the rule)
+ *   depth = float32(Zd), equal to the key's high word;  label = m + 1;  face = f
+ * A pixel nobody owns: img = bg or bg_color, label 0, depth 0, face -1.
+ * Deviations from S, all stated: S interpolates the vertices' unit light vectors and renormalises, here the direction is taken
+ * at the sample; parity with OpenGL's fill rule and its float32 shader is unpinned, as for the depth renderer; flat shading and
+ * vertex colour only (no textures, no Phong).
+ * ---------------------------------------------------------------------- */
+#define PVV_RENDER_MAX_M 255
+#define PVV_RENDER_MAX_FACES (1 << 24)
+#define PVV_RENDER_MAX_SIDE 16384
+
+/* Host-only.  Bytes pvv_render_color needs: 32 bytes per (instance, vertex slot) -- B*M*Nmax slots, Nmax the largest vertex count
+ * of an object -- plus the 8-byte key image [B,H,W], each of the two parts rounded up to 256 bytes; 0 with pvv_last_error set
+ * when a size is refused. */
+size_t pvv_render_workspace_bytes(int B, int M, int Nmax, int H, int W);
+
+/* R:171-179 with S:21-67 for a batch.  d_pts, d_colors, d_faces, d_ranges as above (N vertices, F face rows, O objects; Nmax
+ * and Fmax are the largest vertex and face count of an object, computed by the host that built d_ranges); d_pose [B,M,3,4]
+ * binary64; d_obj [B,M] int32 or NULL; d_K [9] row-major, shared when K_batched == 0, else [B,9]; d_bg [B,H,W,3] uint8 or NULL
+ * for h_bg_color (3 bytes on the host).  d_workspace: pvv_render_workspace_bytes(B, M, Nmax, H, W) bytes, 32-byte aligned.
+ * Writes d_img [B,H,W,3] uint8, d_label [B,H,W] uint8, d_depth [B,H,W] float32 (16-byte aligned), d_area [B,M] int32 (the pixels
+ * each instance owns) and, unless NULL, d_face [B,H,W] int32 (16-byte aligned).  Two fills and three launches: the vertices, the
+ * raster into the key image, the shading pass.  Returns 0, PVV_E_ARG / PVV_E_WORKSPACE with pvv_last_error set (checked before
+ * any launch) or a hipError_t. */
+int pvv_render_color(const float *d_pts, const uint8_t *d_colors, const int32_t *d_faces, int N, int F, const int32_t *d_ranges,
+                     int O, int Nmax, int Fmax, const double *d_pose, const int32_t *d_obj, const double *d_K, int K_batched,
+                     const uint8_t *d_bg, const uint8_t *h_bg_color, int B, int M, int H, int W, double near, double far,
+                     double ambient, void *d_workspace, size_t workspace_bytes, uint8_t *d_img, uint8_t *d_label, float *d_depth,
+                     int32_t *d_area, int32_t *d_face, void *stream);
+
+/* ------------------------------------------------------------------------
  * Detector training: heat-map targets and the detector loss (ABI v8, additive).  Citations:
  *   P = lib/datasets/tless_train/ct.py:46-66 (prepare_detection, called per object at :86-95)
  *   G = lib/utils/data_utils.py:10-65 (gaussian_radius :10-33, gaussian2D :36-47, draw_umich_gaussian :50-65)
