@@ -476,3 +476,6 @@ PVV_EXPORT int pvv_count_inliers(const float *d_direct, const float *d_coords, c
 
 // ---- colour renders: shaded images, instance labels and depth of a batch of scenes (ABI v8, additive) -----
 #include "render.hpp"
+
+// ---- detector evaluation: COCO box AP, map, match and accumulate (ABI v8, additive) -----
+#include "det_eval.hpp"

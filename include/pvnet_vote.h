@@ -737,6 +737,75 @@ int pvv_render_color(const float *d_pts, const uint8_t *d_colors, const int32_t 
                      int32_t *d_area, int32_t *d_face, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Detector evaluation: COCO box AP (ABI v8, additive).  Citations:
+ *   E = lib/evaluators/tless_test/ct.py:32-79 (Evaluator.evaluate, summarize)
+ *   C = lib/evaluators/tless_test/coco_eval.py (computeIoU :164-191, evaluateImg :236-314, accumulate :316-421, Params :499-512)
+ *   U = lib/utils/data_utils.py:159-162 (affine_transform)
+ * Device pointers, the caller's stream last; nothing is read back, nothing synchronises, nothing is allocated.  Everything is
+ * binary64 in the order written, without contraction; integers where the reference counts.  No floating-point atomics: reruns
+ * and any split of the same images into calls give the same bytes.  tests/det_eval_twin.py is this contract in numpy.
+ *
+ * Two-decimal rounding, float('{:.2f}'.format(v)) (E:56, E:61):  p = v*100;  e = fma(v, 100, -p), the exact residual;
+ *   n = rint(p);  n + 1 when p - n == 0.5 and e > 0;  n - 1 when p - n == -0.5 and e < 0;  the result is n / 100.0.
+ * Box IoU (C:189-190, the rule of maskUtils.iou for xywh boxes):  ga = gw*gh;  da = dw*dh;
+ *   w = min(dx+dw, gx+gw) - max(dx, gx), 0 for w <= 0;  h alike;  i = w*h;  u = crowd ? da : (da+ga) - i;  i/u.
+ * The order's key, 63 bits: category index << 55 | (2^23 - 1 - n) << 31 | image rank << 7 | rank inside (image, category);
+ *   a row that is not evaluated has the key 2^63 - 1.
+ * The match word of a detection and an area range: bit t = matched at IoU threshold t, bit 10 + t = ignored there.
+ * ---------------------------------------------------------------------- */
+#define PVV_DET_T 10               /* IoU thresholds */
+#define PVV_DET_R 101              /* recall thresholds */
+#define PVV_DET_A 4                /* area ranges */
+#define PVV_DET_M 3                /* detection caps */
+#define PVV_DET_MAX_K 128          /* detection rows per image */
+#define PVV_DET_MAX_D 100          /* detections of one category in one image that are kept (maxDets[-1]) */
+#define PVV_DET_MAX_G 64           /* ground truths of one category in one image: a 64-bit mask per lane */
+#define PVV_DET_MAX_C 255          /* categories: 8 bits of the key, one value left for the rows left out */
+#define PVV_DET_MAX_IMAGES (1 << 24)
+
+/* The IoU rule on its own: d_dt [D,4], d_gt [G,4] xywh binary64, d_iscrowd [G] int32, d_out [D,G].  One launch. */
+int pvv_det_box_iou(const double *d_dt, int D, const double *d_gt, const int32_t *d_iscrowd, int G, double *d_out, void *stream);
+
+/* E:35-37, 47, 53-61 for the B*K rows of d_detection [B,K,6] float32 (x0, y0, x1, y1, score, label), one lane per row:
+ * the box times down_ratio in float32, both corners through the image's transform in binary64 (x*t00 + y*t01) + t02, xywh, the
+ * two-decimal rounding of the four values and the score, area = w*h of the rounded values, the label truncated and mapped
+ * through d_label_to_cat [n_labels] to the category index.  d_block [B,8] binary64 = {t00, t01, t02, t10, t11, t12, the image's
+ * rank among the ground truth's images in ascending id, 0}: the host computes it, the kernels evaluate no transcendental.
+ * Writes d_box [B*K,4], d_score, d_area [B*K] binary64, d_score_int (n) and d_cat [B*K] int32.  *d_err is OR-ed with 1 when a
+ * value is not finite, |n| of a score reaches 2^23 or a label lies outside [0, n_labels).  One launch. */
+int pvv_det_map(const float *d_detection, const double *d_block, const int32_t *d_label_to_cat, int n_labels, int B, int K,
+                float down_ratio, double *d_box, double *d_score, double *d_area, int32_t *d_score_int, int32_t *d_cat,
+                int32_t *d_err, void *stream);
+
+/* C:122-159 and C:236-314 for the B images of a call, one workgroup per image, on the outputs of pvv_det_map.  d_num [B] int32
+ * or int64 (num_is_i64), or NULL for K: the rows of an image that count; an image with none is left out altogether (E:43-44).
+ * Ground truth, sorted by (image rank, category index) and in annotation order inside a cell: d_gt_box [N,4], d_gt_area [N]
+ * binary64, d_gt_iscrowd [N] int32, d_gt_off [I*C + 1] int32 (cell = rank*C + category).  At most PVV_DET_MAX_G per cell: the
+ * host checks it.  d_iou_thrs [PVV_DET_T], d_area_rng [PVV_DET_A,2] binary64, taken by the host from numpy as C:507-510 does.
+ * The image's rows are ordered by (category, n descending, row) inside the workgroup, cut at PVV_DET_MAX_D per category, the
+ * IoUs of a category go to LDS and the 40 (area range, threshold) pairs are lanes of one wave running C:274-297 as it stands.
+ * Writes, at the ordered position of each row, d_keys [B*K] and d_words [B*K,PVV_DET_A] (all of them), and adds the count of
+ * non-ignored ground truths of every evaluated (image, category) to d_npig [C,PVV_DET_A] (integer atomics).  One launch. */
+int pvv_det_match(const double *d_box, const double *d_area, const int32_t *d_score_int, const int32_t *d_cat, const void *d_num,
+                  int num_is_i64, const double *d_block, int B, int K, const double *d_gt_box, const double *d_gt_area,
+                  const int32_t *d_gt_iscrowd, const int32_t *d_gt_off, int I, int C, const double *d_iou_thrs,
+                  const double *d_area_rng, long long *d_keys, uint32_t *d_words, int32_t *d_npig, void *stream);
+
+/* Host-only.  Bytes pvv_det_accumulate needs for N rows: 20 bytes per (area range, cap, threshold, row); 0 with pvv_last_error
+ * set when N is refused. */
+size_t pvv_det_accumulate_workspace_bytes(long long N);
+
+/* C:316-421 on the keys of all calls sorted ascending (d_keys_sorted [N], d_perm [N] int64 = the position of each in d_words'
+ * rows): one workgroup per (category, area range, cap), one wave per threshold.  Filter by rank < cap (h_max_dets [PVV_DET_M] on
+ * the host), integer prefix counts of true and false positives, rc = tp/npig, pr = tp/((fp+tp) + 2^-52), the backward running
+ * maximum as a suffix maximum, searchsorted(rc, recThrs, 'left') as PVV_DET_R binary searches (d_rec_thrs from numpy, C:508); a
+ * search that ends past the last row writes 0.  d_precision, d_scores [T,R,C,A,M] and d_recall [T,C,A,M] binary64: the caller
+ * fills them with -1, cells with npig == 0 are not written.  The workspace is 8-byte aligned.  One launch. */
+int pvv_det_accumulate(const long long *d_keys_sorted, const long long *d_perm, const uint32_t *d_words, long long N,
+                       const int32_t *d_npig, int C, const double *d_rec_thrs, const int32_t *h_max_dets, void *d_workspace,
+                       size_t workspace_bytes, double *d_precision, double *d_recall, double *d_scores, void *stream);
+
+/* ------------------------------------------------------------------------
  * Detector training: heat-map targets and the detector loss (ABI v8, additive).  Citations:
  *   P = lib/datasets/tless_train/ct.py:46-66 (prepare_detection, called per object at :86-95)
  *   G = lib/utils/data_utils.py:10-65 (gaussian_radius :10-33, gaussian2D :36-47, draw_umich_gaussian :50-65)

@@ -1,0 +1,387 @@
+"""numpy twin of the detector evaluation (include/pvnet_vote.h, "Detector evaluation"; clean_pvnet_amd/det_eval.py): the map with
+its two-decimal rounding, the box IoU, the greedy matching, the order's key and the accumulation, each the contract restated
+with one rounding per operation in the order written, so that the device's outputs can be compared as bytes.  The scenarios at
+the end are the inputs of tests/golden/det_eval_*.npz (tests/golden/make_det_eval_golden.py runs the reference's own classes on
+them)."""
+import functools
+import os
+
+import numpy as np
+
+F32, F64 = np.float32, np.float64
+T, R, A, M = 10, 101, 4, 3
+MAX_K, MAX_D, MAX_G = 128, 100, 64
+SENTINEL = (1 << 63) - 1
+IOU_THRS = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)
+REC_THRS = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
+MAX_DETS = [1, 10, 100]
+AREA_RNG = np.array([[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]], F64)
+EPS = float(np.spacing(1))
+
+
+# ------------------------------------------------------------------------------------------------------------ rounding
+def _split(a):
+    c = 134217729.0 * a
+    hi = c - (c - a)
+    return hi, a - hi
+
+
+def round2(v):
+    """float('{:.2f}'.format(v)) elementwise: (n, n / 100.0).  p + e == v * 100 exactly (Dekker's product stands in for the
+    device's fma); n = rint(p), moved by one when p sits on a half and e decides."""
+    v = np.asarray(v, F64)
+    with np.errstate(all="ignore"):
+        p = v * 100.0
+        ah, al = _split(v)
+        bh, bl = _split(np.float64(100.0))
+        e = ((ah * bh - p) + ah * bl + al * bh) + al * bl
+        n = np.rint(p)
+        d = p - n
+        n = np.where((d == 0.5) & (e > 0), n + 1.0, np.where((d == -0.5) & (e < 0), n - 1.0, n))
+        return n, n / 100.0
+
+
+def bad_value(v):
+    with np.errstate(all="ignore"):
+        return ~(np.abs(np.asarray(v, F64) * 100.0) < 4503599627370496.0)
+
+
+# ------------------------------------------------------------------------------------------------------------ the transform
+def affine(cx, cy, scale, dw, dh):
+    k = float(dw) / float(scale)
+    return [[k, 0.0, dw * 0.5 - (k * cx + 0.0 * cy)], [-0.0, k, dh * 0.5 - (k * cy - 0.0 * cx)]]
+
+
+def invert_affine(Mx):
+    m = [float(v) for row in Mx for v in row]
+    D = m[0] * m[4] - m[1] * m[3]
+    D = 1. / D if D != 0 else 0.
+    A11, A22, m1, m3 = m[4] * D, m[0] * D, m[1] * (-D), m[3] * (-D)
+    return [A11, m1, -A11 * m[2] - m1 * m[5], m3, A22, -m3 * m[2] - A22 * m[5]]
+
+
+def inverse_transform(center, scale, inp_hw):
+    h, w = (int(v) for v in inp_hw)
+    c, s = np.asarray(center, F32).ravel(), np.asarray(scale, F32).ravel()
+    return invert_affine(affine(float(c[0]), float(c[1]), float(s[0]), w, h))
+
+
+def make_block(images_sorted, img_ids, center, scale, inp_hw):
+    block = np.zeros((len(img_ids), 8), F64)
+    for b, i in enumerate(img_ids):
+        block[b, :6] = inverse_transform(center[b], np.atleast_1d(scale[b]), inp_hw)
+        block[b, 6] = float(np.searchsorted(images_sorted, i))
+    return block
+
+
+# ------------------------------------------------------------------------------------------------------------ the stages
+def box_iou(dt, gt, iscrowd):
+    dt, gt = np.asarray(dt, F64).reshape(-1, 4), np.asarray(gt, F64).reshape(-1, 4)
+    out = np.zeros((len(dt), len(gt)), F64)
+    for d in range(len(dt)):
+        for g in range(len(gt)):
+            ga, da = gt[g, 2] * gt[g, 3], dt[d, 2] * dt[d, 3]
+            w = min(dt[d, 0] + dt[d, 2], gt[g, 0] + gt[g, 2]) - max(dt[d, 0], gt[g, 0])
+            if w <= 0:
+                continue
+            h = min(dt[d, 1] + dt[d, 3], gt[g, 1] + gt[g, 3]) - max(dt[d, 1], gt[g, 1])
+            if h <= 0:
+                continue
+            i = w * h
+            u = da if iscrowd[g] else (da + ga) - i
+            with np.errstate(all="ignore"):
+                out[d, g] = np.float64(i) / np.float64(u)
+    return out
+
+
+def map_rows(detection, block, label_to_cat, down_ratio=4):
+    """``pvv_det_map``: (dict of box [B*K,4], score, area, n, cat; raw [B*K,4] before the rounding; err)."""
+    det = np.asarray(detection, F32)
+    B, K = det.shape[:2]
+    rows = det.reshape(B * K, 6)
+    t = np.repeat(np.asarray(block, F64), K, axis=0)
+    with np.errstate(all="ignore"):
+        sc = (rows[:, :4] * F32(down_ratio)).astype(F64)
+        c = np.empty((B * K, 4), F64)
+        for j in range(2):
+            x, y = sc[:, 2 * j], sc[:, 2 * j + 1]
+            c[:, 2 * j] = (x * t[:, 0] + y * t[:, 1]) + t[:, 2]
+            c[:, 2 * j + 1] = (x * t[:, 3] + y * t[:, 4]) + t[:, 5]
+        c[:, 2] = c[:, 2] - c[:, 0]
+        c[:, 3] = c[:, 3] - c[:, 1]
+        raw = c.copy()
+        bad = bad_value(c).any(axis=1) | bad_value(rows[:, 4])
+        _, box = round2(c)
+        n, score = round2(rows[:, 4].astype(F64))
+        big = ~(np.abs(n) < 8388608.0)
+        bad |= big
+        n = np.where(big, 0.0, n).astype(np.int32)
+        area = box[:, 2] * box[:, 3]
+        lf = rows[:, 5]
+        ok = (lf > F32(-1)) & (lf < F32(len(label_to_cat)))
+        cat = np.full(B * K, -1, np.int32)
+        cat[ok] = np.asarray(label_to_cat, np.int32)[lf[ok].astype(np.int64)]
+        bad |= ~ok
+    return {"box": box, "score": score, "area": area, "n": n, "cat": cat}, raw, int(bad.any())
+
+
+def match(mapped, num, block, gt, B, K):
+    """``pvv_det_match``: keys [B*K] int64, words [B*K,4] uint32, npig [C,4] int32 (the counts of this call)."""
+    C = len(gt["cats"])
+    keys = np.full(B * K, SENTINEL, np.int64)
+    words = np.zeros((B * K, A), np.uint32)
+    npig = np.zeros((C, A), np.int32)
+    for b in range(B):
+        rows = K if num is None else min(max(int(num[b]), 0), K)
+        if rows == 0:
+            continue
+        rank = int(block[b, 6])
+        local = []
+        for k in range(K):
+            ci = int(mapped["cat"][b * K + k]) if k < rows else -1
+            cf = ci if ci >= 0 else 0xffffff
+            local.append((cf << 40) | ((8388607 - int(mapped["n"][b * K + k])) << 8) | k)
+        local.sort()
+        ds = 0
+        for c in range(C):
+            de = sum(1 for v in local if (v >> 40) <= c)
+            g0, g1 = int(gt["off"][rank * C + c]), int(gt["off"][rank * C + c + 1])
+            G, D = g1 - g0, min(de - ds, MAX_D)
+            for j in range(ds, de):
+                if j - ds < MAX_D:
+                    keys[b * K + j] = (c << 55) | (((local[j] >> 8) & 0xffffff) << 31) | (rank << 7) | (j - ds)
+            if D > 0 or G > 0:
+                r = [b * K + (local[ds + d] & 0xff) for d in range(D)]
+                iou_m = box_iou(mapped["box"][r], gt["box"][g0:g1], gt["crowd"][g0:g1])
+                crowd = [bool(v) for v in gt["crowd"][g0:g1]]
+                for a in range(A):
+                    lo, hi = AREA_RNG[a]
+                    ig = [crowd[g] or gt["area"][g0 + g] < lo or gt["area"][g0 + g] > hi for g in range(G)]
+                    npig[c, a] += sum(1 for v in ig if not v)
+                    order = [g for g in range(G) if not ig[g]] + [g for g in range(G) if ig[g]]
+                    for t in range(T):
+                        gtm = [False] * G
+                        for d in range(D):
+                            iou = min(IOU_THRS[t], 1 - 1e-10)
+                            m = -1
+                            for g in order:
+                                if gtm[g] and not crowd[g]:
+                                    continue
+                                if m > -1 and not ig[m] and ig[g]:
+                                    break
+                                if iou_m[d, g] < iou:
+                                    continue
+                                iou = iou_m[d, g]
+                                m = g
+                            if m >= 0:
+                                gtm[m] = True
+                                dig = ig[m]
+                            else:
+                                da = mapped["area"][r[d]]
+                                dig = bool(da < lo or da > hi)
+                            words[b * K + ds + d, a] |= np.uint32((int(m >= 0) << t) | (int(dig) << (T + t)))
+            ds = de
+    return keys, words, npig
+
+
+def order(keys):
+    perm = np.argsort(keys, kind="stable")
+    return keys[perm], perm.astype(np.int64)
+
+
+def accumulate(keys_sorted, perm, words, npig, C):
+    precision = -np.ones((T, R, C, A, M))
+    recall = -np.ones((T, C, A, M))
+    scores = -np.ones((T, R, C, A, M))
+    for c in range(C):
+        lo, hi = np.searchsorted(keys_sorted, c << 55), np.searchsorted(keys_sorted, (c + 1) << 55)
+        k, w = keys_sorted[lo:hi], words[perm[lo:hi]]
+        for a in range(A):
+            if npig[c, a] == 0:
+                continue
+            for m, cap in enumerate(MAX_DETS):
+                keep = (k & 127) < cap
+                sn = (8388607 - ((k[keep] >> 31) & 0xffffff)).astype(F64)
+                wa = w[keep, a]
+                nd = int(keep.sum())
+                for t in range(T):
+                    mt, ig = ((wa >> t) & 1).astype(bool), ((wa >> (T + t)) & 1).astype(bool)
+                    tp, fp = np.cumsum(mt & ~ig).astype(F64), np.cumsum(~mt & ~ig).astype(F64)
+                    rc = tp / F64(npig[c, a])
+                    pr = tp / ((fp + tp) + EPS)
+                    pm = np.maximum.accumulate(pr[::-1])[::-1]
+                    recall[t, c, a, m] = rc[-1] if nd else 0
+                    inds = np.searchsorted(rc, REC_THRS, side="left")
+                    hit = inds < nd
+                    q, ss = np.zeros(R), np.zeros(R)
+                    q[hit], ss[hit] = pm[inds[hit]], sn[inds[hit]] / 100.0
+                    precision[t, :, c, a, m] = q
+                    scores[t, :, c, a, m] = ss
+    return precision, recall, scores
+
+
+def prepare_gt(gt):
+    """The host side of the ground truth (det_eval.prepare_gt restated without its checks)."""
+    images, cats = np.unique(gt["image_id"]), np.unique(gt["category_id"])
+    rank, ci = np.searchsorted(images, gt["ann_image_id"]), np.searchsorted(cats, gt["ann_category_id"])
+    cell = rank * len(cats) + ci
+    o = np.argsort(cell, kind="stable")
+    off = np.zeros(len(images) * len(cats) + 1, np.int64)
+    np.cumsum(np.bincount(cell, minlength=len(images) * len(cats)), out=off[1:])
+    return {"images": images, "cats": cats, "label_to_cat": np.searchsorted(cats, gt["category_id"]).astype(np.int32),
+            "box": np.asarray(gt["ann_bbox"], F64).reshape(-1, 4)[o], "area": np.asarray(gt["ann_area"], F64)[o],
+            "crowd": (np.asarray(gt["ann_iscrowd"])[o] != 0).astype(np.int32), "off": off.astype(np.int32)}
+
+
+def evaluate(s, splits=None):
+    """The whole path on a scenario ``s``: dict of every stage's output.  ``splits``: lists of batch positions, one per call."""
+    g = prepare_gt(s)
+    B, K = s["detection"].shape[:2]
+    C = len(g["cats"])
+    num = None if s.get("num") is None else np.asarray(s["num"])
+    out = {"mapped": [], "raw": [], "keys": [], "words": [], "npig": np.zeros((C, A), np.int32), "err": 0}
+    for idx in (splits or [list(range(B))]):
+        idx = list(idx)
+        block = make_block(g["images"], [s["img_ids"][b] for b in idx], s["center"][idx], s["scale"][idx], s["inp_hw"])
+        mapped, raw, err = map_rows(s["detection"][idx], block, g["label_to_cat"], s.get("down_ratio", 4))
+        keys, words, npig = match(mapped, None if num is None else num[idx], block, g, len(idx), K)
+        out["mapped"].append(mapped), out["raw"].append(raw), out["keys"].append(keys), out["words"].append(words)
+        out["npig"] += npig
+        out["err"] |= err
+    keys, words = np.concatenate(out["keys"]), np.concatenate(out["words"])
+    out["keys_sorted"], out["perm"] = order(keys)
+    out["precision"], out["recall"], out["scores"] = accumulate(out["keys_sorted"], out["perm"], words, out["npig"], C)
+    return out
+
+
+def tie_margin(raw):
+    """The smallest distance of 100 * v from a half over the finite values: what the dot product's order would have to move."""
+    f = np.abs(raw[np.isfinite(raw)] * 100.0)
+    return float(np.min(np.abs((f - np.floor(f)) - 0.5))) if f.size else 0.5
+
+
+# ------------------------------------------------------------------------------------------------------------ the scenarios
+GT_FIELDS = ("ann_image_id", "ann_category_id", "ann_bbox", "ann_area", "ann_iscrowd", "image_id", "image_height", "image_width",
+             "category_id")
+
+
+def _pack(images, cat_ids, K, inp_hw, feed):
+    """images: {id: dict(hw, center, scale, gts [(cat, xywh, area or None, crowd)], dets [(cat, xyxy image px, score)] or rows)}"""
+    ann = {k: [] for k in GT_FIELDS[:5]}
+    for i in images:                                               # annotation order: as listed, images interleaved by id order given
+        for cat, xywh, area, crowd in images[i]["gts"]:
+            ann["ann_image_id"].append(i), ann["ann_category_id"].append(cat), ann["ann_bbox"].append(xywh)
+            ann["ann_area"].append(xywh[2] * xywh[3] if area is None else area), ann["ann_iscrowd"].append(crowd)
+    B = len(feed)
+    det = np.zeros((B, K, 6), F32)
+    num = np.zeros(B, np.int64)
+    center, scale = np.zeros((B, 2), F32), np.zeros((B, 2), F32)
+    for b, i in enumerate(feed):
+        im = images[i]
+        center[b], scale[b] = im["center"], im["scale"]
+        inv = inverse_transform(center[b], scale[b], inp_hw)
+        rows = []
+        for cat, xyxy, score in im["dets"]:
+            p = [(xyxy[0] - inv[2]) / inv[0] / 4, (xyxy[1] - inv[5]) / inv[4] / 4, (xyxy[2] - inv[2]) / inv[0] / 4, (xyxy[3] - inv[5]) / inv[4] / 4]
+            rows.append(p + [score, cat_ids.index(cat)])
+        assert len(rows) <= K
+        num[b] = len(rows)
+        if rows:
+            det[b, :len(rows)] = np.array(rows, F64).astype(F32)
+    return {"ann_image_id": np.array(ann["ann_image_id"], np.int64), "ann_category_id": np.array(ann["ann_category_id"], np.int64),
+            "ann_bbox": np.array(ann["ann_bbox"], F64).reshape(-1, 4), "ann_area": np.array(ann["ann_area"], F64),
+            "ann_iscrowd": np.array(ann["ann_iscrowd"], np.int32), "image_id": np.array(list(images), np.int64),
+            "image_height": np.array([images[i]["hw"][0] for i in images], np.int64),
+            "image_width": np.array([images[i]["hw"][1] for i in images], np.int64), "category_id": np.array(cat_ids, np.int64),
+            "detection": det, "num": num, "img_ids": np.array(feed, np.int64), "center": center, "scale": scale,
+            "inp_hw": np.array(inp_hw, np.int64)}
+
+
+def _random_image(rng, cat_ids, n_gt, n_det, hw=(540, 720), crowd_p=0.12):
+    h, w = hw
+    gts, dets = [], []
+    for _ in range(n_gt):
+        side = float(rng.choice([14.0, 40.0, 130.0])) * rng.uniform(0.7, 1.5)
+        bw, bh = round(side * rng.uniform(0.6, 1.4), 2), round(side * rng.uniform(0.6, 1.4), 2)
+        x, y = round(rng.uniform(0, w - bw), 2), round(rng.uniform(0, h - bh), 2)
+        gts.append((int(rng.choice(cat_ids)), [x, y, bw, bh], round(bw * bh * rng.uniform(0.5, 1.0), 2), int(rng.random() < crowd_p)))
+    while len(dets) < n_det:
+        if gts and rng.random() < 0.75:
+            cat, (x, y, bw, bh), _, _ = gts[rng.integers(len(gts))]
+            j = rng.normal(0, 0.08, 4) * [bw, bh, bw, bh]
+            box = [x + j[0], y + j[1], x + bw + j[2], y + bh + j[3]]
+            cat = cat if rng.random() < 0.9 else int(rng.choice(cat_ids))
+        else:
+            bw, bh = rng.uniform(8, 200, 2)
+            x, y = rng.uniform(0, w - bw), rng.uniform(0, h - bh)
+            box, cat = [x, y, x + bw, y + bh], int(rng.choice(cat_ids))
+        dets.append((cat, box, float(rng.uniform(0.03, 1.0))))
+    return gts, dets
+
+
+def scenario_rules():
+    """The hand-made cases: an IoU exactly on a threshold, a crowd taken by several detections, the early stop, a match to an
+    out-of-range ground truth next to an unmatched out-of-range detection, score ties, an image without detections, one without
+    ground truth, a category with ground truth only, one with neither, more than 100 rows of a category, caps 1 and 10 biting."""
+    rng = np.random.default_rng(20)
+    cat_ids = [7, 3, 11, 25, 20]
+    ident = dict(hw=(128, 160), center=(80.0, 64.0), scale=(160.0, 160.0))
+    wide = dict(hw=(540, 720), center=(355.5, 262.25), scale=(812.0, 812.0))
+    images = {}
+    images[40] = dict(wide, gts=[], dets=[])
+    g40, d40 = _random_image(rng, [7], 6, 110, crowd_p=0.0)
+    g40b, d40b = _random_image(rng, [3], 2, 8, crowd_p=0.0)
+    images[40]["gts"], images[40]["dets"] = g40 + g40b, d40[:60] + d40b + d40[60:]
+    images[12] = dict(ident, gts=[(7, [0, 0, 2, 1], None, 0), (7, [10, 10, 40, 40], None, 1), (3, [58, 58, 26, 26], None, 1),
+                                  (3, [60, 60, 20, 20], None, 0)],
+                      dets=[(7, [0, 0, 1, 1], 0.9), (7, [12, 12, 20, 20], 0.8), (7, [15, 15, 30, 30], 0.804), (7, [20, 20, 45, 45], 0.796),
+                            (3, [62, 60, 82, 80], 0.6), (3, [61, 60, 81, 80], 0.6), (7, [0, 0, 2, 1], 0.5)])
+    images[33] = dict(ident, gts=[(11, [10, 10, 50, 40], None, 0), (11, [100, 10, 10, 10], None, 0), (20, [30, 70, 40, 30], 700.0, 0)],
+                      dets=[(11, [10, 10, 60, 50], 0.7), (11, [100, 80, 150, 120], 0.8), (11, [100, 10, 110, 20], 0.95),
+                            (11, [101, 10, 111, 20], 0.804), (7, [5, 5, 30, 30], 0.796)])
+    images[8] = dict(ident, gts=[(3, [20, 20, 30, 30], None, 0), (20, [70, 20, 50, 60], None, 0)], dets=[])
+    images[21] = dict(wide, gts=[], dets=_random_image(rng, [3, 11], 0, 9)[1])
+    g5, d5 = _random_image(rng, [7, 3, 11], 7, 30)
+    images[5] = dict(wide, gts=g5, dets=d5)
+    images[77] = dict(ident, gts=[(7, [1, 1, 20, 20], None, 0)], dets=[])           # in gt, never passed
+    return _pack(images, cat_ids, 128, (128, 160), [40, 12, 33, 8, 21, 5])
+
+
+def scenario_random(seed=7, B=8, K=40):
+    """Seeded images with their own centres and scales, every row counting (``num`` is None)."""
+    rng = np.random.default_rng(seed)
+    cat_ids = [1, 2, 5, 9]
+    images = {}
+    for i in rng.permutation(np.arange(100, 100 + 3 * B, 3))[:B]:
+        g, d = _random_image(rng, cat_ids[:3], int(rng.integers(2, 8)), K)
+        images[int(i)] = dict(hw=(540, 720), center=(float(F32(rng.uniform(300, 420))), float(F32(rng.uniform(220, 320)))),
+                              scale=(float(F32(rng.uniform(600, 900))),) * 2, gts=g, dets=d)
+    s = _pack(images, cat_ids, K, (136, 180), list(images)[::-1])
+    s["num"] = None
+    return s
+
+
+SCENARIOS = {"det_eval_rules": scenario_rules, "det_eval_random": scenario_random}
+
+
+def load_fixture(path):
+    """A tests/golden/det_eval_*.npz as a scenario dict (``num`` None when the file has none) with the reference's ``ref_*``."""
+    with np.load(path) as z:
+        s = {k: z[k] for k in z.files}
+    if not bool(s.pop("has_num")):
+        s["num"] = None
+    return s
+
+
+@functools.lru_cache(maxsize=None)
+def fixture_with_twin(name):
+    """(scenario with the reference's results, the twin's stage outputs for one call with all images): computed once and shared by
+    the tests; treat both as read-only."""
+    s = load_fixture(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", name + ".npz"))
+    return s, evaluate(s)
+
+
+def used_rows(s):
+    """The flat row indices b*K + k that the reference was given, in its order."""
+    B, K = s["detection"].shape[:2]
+    return np.array([b * K + k for b in range(B) for k in range(K if s["num"] is None else int(s["num"][b]))], np.int64)

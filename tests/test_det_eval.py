@@ -1,0 +1,226 @@
+"""Detector evaluation (include/pvnet_vote.h's newest section, clean_pvnet_amd.det_eval) without a GPU: the module and its entry
+points exist, the host side raises what it must, the twin's two-decimal rounding equals Python's own ``'{:.2f}'.format``, and the
+numpy twin of the contract (tests/det_eval_twin.py) reproduces the reference's own ``Evaluator`` and ``COCOeval`` on the fixtures
+of tests/golden/make_det_eval_golden.py bit for bit.  The GPU tests (tests/test_gpu_det_eval.py) then hold the device to the twin
+bit for bit."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import det_eval_twin as twin
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+VOTELIB = os.path.join(ROOT, "clean-pvnet_amd", "libpvnet_vote.so")
+METRICSLIB = os.path.join(ROOT, "clean-pvnet_amd", "libpvnet_metrics.so")
+HEADER = os.path.join(ROOT, "include", "pvnet_vote.h")
+FIXTURES = tuple(twin.SCENARIOS)
+SYMBOLS = {"pvv_det_box_iou", "pvv_det_map", "pvv_det_match", "pvv_det_accumulate_workspace_bytes", "pvv_det_accumulate"}
+# What a different order of the dot product, a fused multiply-add or the three-point solve in place of the closed form can move a
+# mapped coordinate by: a few ulp of 100 * v, v < 2^10, so far below 1e-9.  A fixture whose coordinates all stay further than this
+# from a half of the second decimal is decided by none of them.
+TIE_MARGIN = 1e-7
+
+
+def _bits(a):
+    return np.ascontiguousarray(np.asarray(a, np.float64)).view(np.uint64)
+
+
+def _exported(path):
+    nm = subprocess.check_output(["nm", "-D", "--defined-only", path]).decode()
+    return {l.split()[-1] for l in nm.splitlines() if " T " in l}
+
+
+# ------------------------------------------------------------------------------------------------ 0. the module and the symbols
+def test_module_imports(pkg):
+    from clean_pvnet_amd import det_eval
+    assert (det_eval.T, det_eval.R, det_eval.A, det_eval.M) == (twin.T, twin.R, twin.A, twin.M)
+    assert (det_eval.MAX_K, det_eval.MAX_D, det_eval.MAX_G) == (twin.MAX_K, twin.MAX_D, twin.MAX_G)
+    assert callable(det_eval.box_iou) and all(callable(getattr(det_eval.DetEvaluator, f)) for f in ("evaluate", "summarize"))
+    assert np.array_equal(_bits(det_eval.IOU_THRS), _bits(twin.IOU_THRS)) and np.array_equal(_bits(det_eval.REC_THRS), _bits(twin.REC_THRS))
+    assert det_eval.SENTINEL == twin.SENTINEL
+
+
+def test_header_declares_and_vote_library_exports_the_entry_points():
+    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    assert SYMBOLS <= set(re.findall(r"\b(pvv_[a-z0-9_]+)\s*\(", txt))
+    assert SYMBOLS <= _exported(VOTELIB)
+    assert not any(s.startswith("pvv_det_") for s in _exported(METRICSLIB))
+    assert "#define PVV_ABI_VERSION 8" in open(HEADER).read()                      # additive: the version did not move
+    for name, value in (("T", twin.T), ("R", twin.R), ("A", twin.A), ("M", twin.M), ("MAX_K", twin.MAX_K), ("MAX_D", twin.MAX_D),
+                        ("MAX_G", twin.MAX_G)):
+        assert re.search(r"#define PVV_DET_%s %d\b" % (name, value), txt), name
+
+
+def test_library_refuses_bad_arguments_before_any_launch():
+    import ctypes
+    L = ctypes.CDLL(VOTELIB)
+    L.pvv_det_accumulate_workspace_bytes.restype = ctypes.c_size_t
+    L.pvv_det_accumulate_workspace_bytes.argtypes = [ctypes.c_longlong]
+    L.pvv_last_error.restype = ctypes.c_char_p
+    up = lambda n: (n + 255) // 256 * 256                                          # noqa: E731
+    assert L.pvv_det_accumulate_workspace_bytes(1000) == 3 * up(120 * 1000 * 4) + 120 * 1000 * 8
+    assert L.pvv_det_accumulate_workspace_bytes(1 << 31) == 0 and b"2^31" in L.pvv_last_error()
+    f = ctypes.c_float(4)
+    assert L.pvv_det_map(None, None, None, 5, 1, 20, f, None, None, None, None, None, None, None) == -1       # NULL
+    assert L.pvv_det_map(None, None, None, 5, 1, 129, f, None, None, None, None, None, None, None) == -1 and b"MAX_K" in L.pvv_last_error()
+    assert L.pvv_det_match(*([None] * 5), 0, None, 1, 20, *([None] * 4), 3, 256, *([None] * 6)) == -1
+    assert L.pvv_det_box_iou(None, 2, None, None, 2, None, None) == -1
+
+
+# ------------------------------------------------------------------------------------------------ 1. the host side
+def _tiny_gt(n_in_cell=1):
+    return {"ann_image_id": np.full(n_in_cell, 4), "ann_category_id": np.full(n_in_cell, 2), "ann_bbox": np.tile([1., 1., 5., 5.], (n_in_cell, 1)),
+            "ann_area": np.full(n_in_cell, 25.), "ann_iscrowd": np.zeros(n_in_cell, np.int32), "image_id": np.array([9, 4]),
+            "image_height": np.array([64, 64]), "image_width": np.array([64, 64]), "category_id": np.array([2, 1])}
+
+
+def test_host_errors(pkg):
+    import torch
+    from clean_pvnet_amd import det_eval
+    with pytest.raises(ValueError, match="at most 64"):
+        det_eval.DetEvaluator(_tiny_gt(65))
+    det_eval.DetEvaluator(_tiny_gt(64))
+    bad = _tiny_gt()
+    bad["ann_image_id"] = np.array([5])
+    with pytest.raises(ValueError, match="does not list"):
+        det_eval.DetEvaluator(bad)
+    ev = det_eval.DetEvaluator(_tiny_gt())
+    c, s = np.full((2, 2), 32., np.float32), np.full((2, 2), 64., np.float32)
+    with pytest.raises(ValueError, match="twice"):
+        ev.evaluate(torch.zeros(2, 5, 6), [4, 4], c, s, (64, 64))
+    with pytest.raises(ValueError, match="not in gt"):
+        ev.evaluate(torch.zeros(2, 5, 6), [4, 7], c, s, (64, 64))
+    with pytest.raises(ValueError, match=r"K must lie in \[1, 128\]"):
+        ev.evaluate(torch.zeros(2, 129, 6), [4, 9], c, s, (64, 64))
+    with pytest.raises(TypeError, match="float32"):
+        ev.evaluate(torch.zeros(2, 5, 6, dtype=torch.float64), [4, 9], c, s, (64, 64))
+    with pytest.raises(TypeError, match="int32 or int64"):
+        ev.evaluate(torch.zeros(2, 5, 6), [4, 9], c, s, (64, 64), num=torch.zeros(2))
+    with pytest.raises(RuntimeError, match="no CPU fallback"):                      # everything above is checked before the device
+        ev.evaluate(torch.zeros(2, 5, 6), [4, 9], c, s, (64, 64))
+
+
+@pytest.mark.parametrize("name", FIXTURES)
+def test_host_preparation_equals_the_twins(pkg, name):
+    from clean_pvnet_amd import det_eval
+    s, _ = twin.fixture_with_twin(name)
+    mine, want = det_eval.prepare_gt(s), twin.prepare_gt(s)
+    assert all(np.array_equal(mine[k], want[k]) and mine[k].dtype == want[k].dtype for k in want)
+    for b in range(len(s["img_ids"])):
+        assert det_eval.inverse_transform(s["center"][b], s["scale"][b], s["inp_hw"]) == twin.inverse_transform(s["center"][b], s["scale"][b], s["inp_hw"])
+    assert np.array_equal(_bits(det_eval.summarize_stats(s["ref_precision"], s["ref_recall"])), _bits(s["ref_stats"]))
+
+
+# ------------------------------------------------------------------------------------------------ 2. the rounding
+def _python_round2(v):
+    return float("{:.2f}".format(v))
+
+
+def test_rounding_on_the_known_hard_values():
+    vals = [0.125, 0.375, 2.675, 1.005, 0.285, 0.005, 0.015, 0.025, 0.5, 1e-9, 0.0, 8388607.125, 12345.675, 0.994999999999999996,
+            float(np.float32(0.285)), float(np.float32(0.805)), float(np.float32(0.115))]
+    vals = np.array(vals + [-v for v in vals], np.float64)
+    n, r = twin.round2(vals)
+    want = np.array([_python_round2(v) for v in vals])
+    assert np.array_equal(_bits(r), _bits(want))                                    # the sign of a zero included
+    assert np.array_equal(n, np.rint(want * 100))
+    assert _python_round2(0.125) == 0.12 and _python_round2(0.375) == 0.38 and _python_round2(2.675) == 2.67   # ties to even, and no tie
+
+
+def test_rounding_on_seeded_doubles():
+    rng = np.random.default_rng(5)
+    halves = (rng.integers(-200000, 200000, 30000) + 0.5) / 100.0                   # as near to a tie as a double gets, and around it
+    vals = np.concatenate([rng.uniform(-1000, 1000, 30000), rng.uniform(-1, 1, 10000), halves, np.nextafter(halves[:15000], np.inf),
+                           np.nextafter(halves[15000:], -np.inf)])
+    assert len(vals) == 100000
+    _, r = twin.round2(vals)
+    want = np.array([_python_round2(v) for v in vals.tolist()])
+    assert np.array_equal(_bits(r), _bits(want))
+
+
+def test_box_iou_rule():
+    iou = twin.box_iou([[0, 0, 1, 1], [5, 5, 1, 1], [1, 0, 1, 1]], [[0, 0, 2, 1], [0, 0, 2, 1]], [0, 1])
+    assert iou[0, 0] == 0.5 and iou[0, 1] == 1.0                                   # exactly on a threshold; a crowd divides by da
+    assert iou[1, 0] == 0.0 and iou[2, 0] == 0.5
+
+
+# ------------------------------------------------------------------------------------------------ 3. the twin against the reference
+@pytest.mark.parametrize("name", FIXTURES)
+def test_twin_reproduces_the_reference_fixture(name):
+    s, out = twin.fixture_with_twin(name)
+    assert np.array_equal(_bits(twin.IOU_THRS), _bits(s["ref_iou_thrs"])) and np.array_equal(_bits(twin.REC_THRS), _bits(s["ref_rec_thrs"]))
+    assert out["err"] == 0
+    # the fixture needs no exclusion: no mapped coordinate lies where the dot product's order could decide the second decimal
+    rows = twin.used_rows(s)
+    assert twin.tie_margin(out["raw"][0][rows]) > TIE_MARGIN
+    mapped = out["mapped"][0]
+    assert len(rows) == len(s["ref_score"])
+    assert np.array_equal(_bits(mapped["box"][rows]), _bits(s["ref_box"]))
+    assert np.array_equal(_bits(mapped["score"][rows]), _bits(s["ref_score"]))
+    cats = np.unique(s["category_id"])
+    assert np.array_equal(cats[mapped["cat"][rows]], s["ref_category"])
+    assert out["precision"].shape == s["ref_precision"].shape and out["recall"].shape == s["ref_recall"].shape
+    for k in ("precision", "recall", "scores"):
+        assert np.array_equal(_bits(out[k]), _bits(s["ref_" + k])), k
+    from tests.det_eval_twin import T, R, A, M
+    assert out["precision"].shape == (T, R, len(cats), A, M)
+
+
+@pytest.mark.parametrize("name", FIXTURES)
+def test_twin_gives_the_same_bytes_for_any_split(name):
+    s, out = twin.fixture_with_twin(name)
+    B = len(s["img_ids"])
+    for splits in ([[b] for b in range(B)], [[0, 1, 2], [3], list(range(4, B))]):
+        other = twin.evaluate(s, splits)
+        assert np.array_equal(out["keys_sorted"], other["keys_sorted"]) and np.array_equal(out["npig"], other["npig"])
+        for k in ("precision", "recall", "scores"):
+            assert np.array_equal(_bits(out[k]), _bits(other[k]))
+
+
+def test_rules_fixture_holds_the_cases_it_is_for():
+    s, out = twin.fixture_with_twin("det_eval_rules")
+    g = twin.prepare_gt(s)
+    m, K, C = out["mapped"][0], s["detection"].shape[1], len(g["cats"])
+    keys, words, feed = out["keys"][0].reshape(-1, K), out["words"][0].reshape(-1, K, twin.A), list(s["img_ids"])
+    live = keys != twin.SENTINEL
+    cat_of, n_of, img_of, rank_of = keys >> 55, (keys >> 31) & 0xffffff, (keys >> 7) & 0xffffff, keys & 127
+    # score ties after the rounding, within an image and across images
+    b12, b33 = feed.index(12), feed.index(33)
+    tie = 8388607 - 80
+    assert (n_of[b12][live[b12]] == tie).sum() >= 3 and (n_of[b33][live[b33]] == tie).sum() >= 2
+    # a crowd ground truth taken by several detections: matched and ignored at every threshold, in the range 'all'
+    c7 = int(np.searchsorted(g["cats"], 7))
+    taken = [(words[b12, j, 0] & 0x3ff) == 0x3ff and (words[b12, j, 0] >> 10) == 0x3ff for j in range(K) if live[b12, j] and cat_of[b12, j] == c7]
+    assert sum(taken) >= 3
+    # the IoU of exactly 0.5 matches at the first threshold only
+    first = [j for j in range(K) if live[b12, j] and cat_of[b12, j] == c7 and rank_of[b12, j] == 0][0]
+    assert words[b12, first, 0] == 0x1
+    # the early stop: held by the regular ground truth up to 0.8, by the crowd (and ignored) above
+    c3 = int(np.searchsorted(g["cats"], 3))
+    w = [int(words[b12, j, 0]) for j in range(K) if live[b12, j] and cat_of[b12, j] == c3]
+    assert any((x & 0x3ff) == 0x3ff and (x >> 10) == 0x380 for x in w)
+    # matched to an out-of-range ground truth, next to an unmatched out-of-range detection: both ignored in 'small', not in 'all'
+    c11 = int(np.searchsorted(g["cats"], 11))
+    w = [(int(words[b33, j, 1]), int(words[b33, j, 0])) for j in range(K) if live[b33, j] and cat_of[b33, j] == c11]
+    assert any(sm == (0x3ff | 0x3ff << 10) and al == 0x3ff for sm, al in w) and any(sm == 0x3ff << 10 and al == 0 for sm, al in w)
+    # an image without detections is skipped, its ground truth with it: category 3 has one more ground truth in the file
+    b8 = feed.index(8)
+    assert s["num"][b8] == 0 and not live[b8].any()
+    in_eval = np.isin(s["ann_image_id"], [i for i, n in zip(feed, s["num"]) if n > 0]) & (s["ann_iscrowd"] == 0)
+    for c in range(C):
+        assert out["npig"][c, 0] == (in_eval & (s["ann_category_id"] == g["cats"][c])).sum()
+    assert out["npig"][c3, 0] < ((s["ann_category_id"] == 3) & (s["ann_iscrowd"] == 0)).sum()
+    # an image with detections and no ground truth
+    b21 = feed.index(21)
+    assert live[b21].any() and not (s["ann_image_id"] == 21).any()
+    # a category with ground truth and no detection, and one with neither
+    c20, c25 = int(np.searchsorted(g["cats"], 20)), int(np.searchsorted(g["cats"], 25))
+    assert out["npig"][c20, 0] > 0 and not (cat_of[live] == c20).any() and (out["precision"][:, :, c20, 0, 2] == 0).all()
+    assert (out["precision"][:, :, c25] == -1).all() and (out["recall"][:, c25] == -1).all()
+    # more than 100 rows of one category in an image: cut; caps 1 and 10 bite
+    b40 = feed.index(40)
+    assert (m["cat"].reshape(-1, K)[b40, :s["num"][b40]] == c7).sum() > 100 and (live[b40] & (cat_of[b40] == c7)).sum() == 100
+    assert not np.array_equal(out["recall"][..., 0], out["recall"][..., 1]) and not np.array_equal(out["recall"][..., 1], out["recall"][..., 2])
