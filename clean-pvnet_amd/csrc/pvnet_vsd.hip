@@ -1,5 +1,6 @@
 // pvnet_vsd.hip -- a batched depth rasteriser and the Visible Surface Discrepancy of a whole batch on the device, native HIP
-// for gfx950 (include/pvnet_vsd.h has both arithmetic contracts and the reference lines each pass replaces).
+// for gfx950 (include/pvnet_vsd.h has both arithmetic contracts and the reference lines each pass replaces).  The coverage rules
+// of the rasteriser -- snapping, near clip, edge functions, the sweep -- are raster.hpp's, shared with the colour renderer.
 //
 //   k_vertices    grid (vertex tiles, P): eye-space coordinates in binary64 and the snapped image coordinates of every
 //                 (pose, vertex), once -- not once per triangle corner.
@@ -17,7 +18,7 @@
 //
 // Index bounds: vertex i < N (grid tail and the face check 0 <= index < N before any vertex is read), triangle f < F, pose
 // p < P by the grid; every sample a kernel touches satisfies 0 <= x < W and 0 <= y < H because a piece's bounding box is
-// clamped to the image rectangle before it is swept; pixel index < H*W and tile < ntiles in k_vsd.
+// clamped to the image rectangle before it is swept (raster.hpp, make_piece); pixel index < H*W and tile < ntiles in k_vsd.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -31,48 +32,12 @@
 namespace {
 
 #include "eval_common.hpp"
+#include "raster.hpp"
 
-constexpr int kSmall = 32;           // a piece with at most this many samples in its bounding box is swept by its own lane
-constexpr int kBadCoord = INT_MIN;   // snapped coordinate of a vertex that has none (outside the near plane, or too large)
-constexpr double kSnapLimit = 268435456.0;   // 2^28
+using namespace raster;
+
 constexpr int kTilesPerBlock = 4;    // k_vsd: tiles of 256 pixels a block walks
 constexpr unsigned kEmpty = 0xffffffffu;
-
-struct Vtx {                         // 32 bytes, one per (pose, vertex)
-    double X, Y, Z;
-    int U, V;
-};
-
-struct Cam {
-    double fx, s, cx, fy, cy;
-};
-
-struct Piece {                       // a clipped, oriented (positive area) triangle in snapped coordinates, with its samples
-    int ax, ay, bx, by, cx, cy;
-    int xmin, ymin, w, h;            // w == 0: no piece
-};
-
-__device__ Cam load_cam(const double *K)
-{
-    Cam c;
-    c.fx = K[0];
-    c.s = K[1];
-    c.cx = K[2];
-    c.fy = K[4];
-    c.cy = K[5];
-    return c;
-}
-
-// u = (fx*X + s*Y)/Z + cx, v = (fy*Y)/Z + cy, snapped to 8 sub-pixel bits; kBadCoord when out of range or not a number
-__device__ void project_snap(const Cam &c, double X, double Y, double Z, int *U, int *V)
-{
-    const double u = (c.fx * X + c.s * Y) / Z + c.cx;
-    const double v = (c.fy * Y) / Z + c.cy;
-    const double Ud = floor(256.0 * u + 0.5), Vd = floor(256.0 * v + 0.5);
-    const bool ok = fabs(Ud) <= kSnapLimit && fabs(Vd) <= kSnapLimit;      // false for NaN
-    *U = ok ? (int)Ud : kBadCoord;
-    *V = ok ? (int)Vd : kBadCoord;
-}
 
 __global__ __launch_bounds__(kBlock) void k_vertices(const float *__restrict__ pts, const double *__restrict__ pose,
                                                      const double *__restrict__ K, Vtx *__restrict__ vtx, int N, int K_batched,
@@ -81,170 +46,25 @@ __global__ __launch_bounds__(kBlock) void k_vertices(const float *__restrict__ p
     const int p = blockIdx.y;
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= N) return;
-    const double *T = pose + (size_t)p * 12;
     const Cam c = load_cam(K + (K_batched ? (size_t)p * 9 : 0));
-    const double x = (double)pts[i * 3], y = (double)pts[i * 3 + 1], z = (double)pts[i * 3 + 2];
-    Vtx o;
-    o.X = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
-    o.Y = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
-    o.Z = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
-    o.U = o.V = kBadCoord;
-    if (o.Z >= near) project_snap(c, o.X, o.Y, o.Z, &o.U, &o.V);
-    vtx[(size_t)p * N + i] = o;
+    vtx[(size_t)p * N + i] = vertex(pose + (size_t)p * 12, c, (double)pts[i * 3], (double)pts[i * 3 + 1], (double)pts[i * 3 + 2], near);
 }
 
-// The vertex where the edge from the inside vertex p to the outside vertex q meets Z = near, projected and snapped.
-__device__ void clip_snap(const Cam &c, const Vtx &p, const Vtx &q, double near, int *U, int *V)
-{
-    const double t = (near - p.Z) / (q.Z - p.Z);
-    const double X = p.X + t * (q.X - p.X);
-    const double Y = p.Y + t * (q.Y - p.Y);
-    project_snap(c, X, Y, near, U, V);
-}
+// The depth sink: an unsigned atomicMin on the float bits of a sample's depth, the same image whichever lane owns the piece.
+struct DepthSink {
+    unsigned *img;
+    int W;
+    double near, far;
 
-__device__ Piece make_piece(int U0, int V0, int U1, int V1, int U2, int V2, int W, int H)
-{
-    Piece t;
-    t.w = t.h = 0;
-    t.ax = t.ay = t.bx = t.by = t.cx = t.cy = t.xmin = t.ymin = 0;
-    if (U0 == kBadCoord || U1 == kBadCoord || U2 == kBadCoord) return t;
-    const long long area2 = (long long)(U1 - U0) * (V2 - V0) - (long long)(V1 - V0) * (U2 - U0);
-    if (area2 == 0) return t;
-    if (area2 < 0) {
-        int k = U1; U1 = U2; U2 = k;
-        k = V1; V1 = V2; V2 = k;
+    __device__ void operator()(int x, int y, const Plane &pl, const Cam &c) const
+    {
+        double dx, dy, Z;
+        if (!plane_depth(pl, c, x, y, &dx, &dy, &Z)) return;
+        if (Z >= near && Z <= far) atomicMin(img + (size_t)y * W + x, __float_as_uint((float)Z));
     }
-    // samples (256x + 128, 256y + 128) inside the vertices' box: x >= (Umin - 128)/256, x <= (Umax - 128)/256
-    int xmin = (min(U0, min(U1, U2)) - 128 + 255) >> 8, xmax = (max(U0, max(U1, U2)) - 128) >> 8;
-    int ymin = (min(V0, min(V1, V2)) - 128 + 255) >> 8, ymax = (max(V0, max(V1, V2)) - 128) >> 8;
-    xmin = max(xmin, 0);
-    ymin = max(ymin, 0);
-    xmax = min(xmax, W - 1);
-    ymax = min(ymax, H - 1);
-    if (xmin > xmax || ymin > ymax) return t;
-    t.ax = U0; t.ay = V0; t.bx = U1; t.by = V1; t.cx = U2; t.cy = V2;
-    t.xmin = xmin; t.ymin = ymin; t.w = xmax - xmin + 1; t.h = ymax - ymin + 1;
-    return t;
-}
 
-// E = dx*(py - ay) - dy*(px - ax) > 0, or = 0 on an edge that owns its line.  |dx|, |dy| <= 2^29 and |py - ay|, |px - ax| <
-// 2^29: every product fits 59 bits.
-__device__ bool edge_in(int ax, int ay, int bx, int by, int px, int py)
-{
-    const int dx = bx - ax, dy = by - ay;
-    const long long E = (long long)dx * (py - ay) - (long long)dy * (px - ax);
-    const bool owns = dy > 0 || (dy == 0 && dx > 0);
-    return E > 0 || (E == 0 && owns);
-}
-
-__device__ bool covered(const Piece &t, int x, int y)
-{
-    const int px = 256 * x + 128, py = 256 * y + 128;
-    return edge_in(t.ax, t.ay, t.bx, t.by, px, py) && edge_in(t.bx, t.by, t.cx, t.cy, px, py) &&
-           edge_in(t.cx, t.cy, t.ax, t.ay, px, py);
-}
-
-// The largest value an edge function takes on the samples x0..x1, y0..y1 is negative: no sample of the block is inside.
-__device__ bool edge_rejects(int ax, int ay, int bx, int by, int x0, int y0, int x1, int y1)
-{
-    const int dx = bx - ax, dy = by - ay;
-    const int py = 256 * (dx > 0 ? y1 : y0) + 128, px = 256 * (dy > 0 ? x0 : x1) + 128;
-    return (long long)dx * (py - ay) - (long long)dy * (px - ax) < 0;
-}
-
-__device__ bool block_rejected(const Piece &t, int x0, int y0, int x1, int y1)
-{
-    return edge_rejects(t.ax, t.ay, t.bx, t.by, x0, y0, x1, y1) || edge_rejects(t.bx, t.by, t.cx, t.cy, x0, y0, x1, y1) ||
-           edge_rejects(t.cx, t.cy, t.ax, t.ay, x0, y0, x1, y1);
-}
-
-struct Plane {
-    double n0, n1, n2, num;
+    __device__ const DepthSink &of(int) const { return *this; }
 };
-
-__device__ void shade(unsigned *__restrict__ img, int W, int x, int y, const Plane &pl, const Cam &c, double near, double far)
-{
-    const double dy = (((double)y + 0.5) - c.cy) / c.fy;
-    const double dx = ((((double)x + 0.5) - c.cx) - c.s * dy) / c.fx;
-    const double den = (pl.n0 * dx + pl.n1 * dy) + pl.n2;
-    if (den == 0.0) return;
-    const double Z = pl.num / den;
-    if (Z >= near && Z <= far) atomicMin(img + (size_t)y * W + x, __float_as_uint((float)Z));
-}
-
-__device__ int rl(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
-
-__device__ double rl(double v, int lane)
-{
-    return __hiloint2double(rl(__double2hiint(v), lane), rl(__double2loint(v), lane));
-}
-
-__device__ Piece rl(const Piece &t, int lane)
-{
-    Piece o;
-    o.ax = rl(t.ax, lane); o.ay = rl(t.ay, lane); o.bx = rl(t.bx, lane); o.by = rl(t.by, lane);
-    o.cx = rl(t.cx, lane); o.cy = rl(t.cy, lane);
-    o.xmin = rl(t.xmin, lane); o.ymin = rl(t.ymin, lane); o.w = rl(t.w, lane); o.h = rl(t.h, lane);
-    return o;
-}
-
-// One piece per lane (w == 0: none).  Small pieces by their own lane, the others by the whole wave.
-__device__ void sweep(const Piece &mine, const Plane &pl, unsigned *__restrict__ img, int W, const Cam &c, double near,
-                      double far)
-{
-    const int lane = threadIdx.x & 63;
-    const int cnt = mine.w * mine.h;                       // <= 2^28 by PVS_MAX_SIDE
-    const bool small = cnt <= kSmall;
-    if (small) {
-        int x = mine.xmin, y = mine.ymin;
-        for (int i = 0; i < cnt; ++i) {
-            if (covered(mine, x, y)) shade(img, W, x, y, pl, c, near, far);
-            if (++x == mine.xmin + mine.w) {
-                x = mine.xmin;
-                ++y;
-            }
-        }
-    }
-    unsigned long long big = __ballot(!small);
-    while (big) {
-        const int src = __ffsll((long long)big) - 1;
-        big &= big - 1;
-        const Piece t = rl(mine, src);
-        Plane q;
-        q.n0 = rl(pl.n0, src); q.n1 = rl(pl.n1, src); q.n2 = rl(pl.n2, src); q.num = rl(pl.num, src);
-        const int xmax = t.xmin + t.w - 1, ymax = t.ymin + t.h - 1;
-        const int bx0 = t.xmin >> 3, by0 = t.ymin >> 3;
-        const int nbx = (xmax >> 3) - bx0 + 1, nby = (ymax >> 3) - by0 + 1;
-        const int nblocks = nbx * nby;
-        for (int base = 0; base < nblocks; base += 64) {
-            const int bi = base + lane;
-            const int by = bi / nbx, bx = bi - by * nbx;
-            bool live = bi < nblocks;
-            if (live) {
-                const int x0 = max((bx0 + bx) << 3, t.xmin), y0 = max((by0 + by) << 3, t.ymin);
-                const int x1 = min(((bx0 + bx) << 3) + 7, xmax), y1 = min(((by0 + by) << 3) + 7, ymax);
-                live = !block_rejected(t, x0, y0, x1, y1);
-            }
-            unsigned long long todo = __ballot(live);
-            while (todo) {
-                const int j = __ffsll((long long)todo) - 1;
-                todo &= todo - 1;
-                const int x = ((bx0 + rl(bx, j)) << 3) + (lane & 7), y = ((by0 + rl(by, j)) << 3) + (lane >> 3);
-                if (x >= t.xmin && x <= xmax && y >= t.ymin && y <= ymax && covered(t, x, y))
-                    shade(img, W, x, y, q, c, near, far);
-            }
-        }
-    }
-}
-
-__device__ void rotate_left(Vtx &a, Vtx &b, Vtx &c, int r)
-{
-    if (r == 1) {
-        const Vtx k = a; a = b; b = c; c = k;
-    } else if (r == 2) {
-        const Vtx k = c; c = b; b = a; a = k;
-    }
-}
 
 __global__ __launch_bounds__(kBlock) void k_raster(const int32_t *__restrict__ faces, const Vtx *__restrict__ vtx,
                                                    const double *__restrict__ pose, const double *__restrict__ K,
@@ -255,43 +75,17 @@ __global__ __launch_bounds__(kBlock) void k_raster(const int32_t *__restrict__ f
     if (!pose_finite(pose + (size_t)p * 12)) return;       // block-uniform: an all-zero image
     const Cam c = load_cam(K + (K_batched ? (size_t)p * 9 : 0));
     const int f = blockIdx.x * kBlock + threadIdx.x;
-    Piece pc0 = make_piece(kBadCoord, 0, 0, 0, 0, 0, W, H), pc1 = pc0;
-    Plane pl = {0.0, 0.0, 0.0, 0.0};
+    Face fc = {};                                           // no piece
     if (f < F) {
         const int i0 = faces[f * 3], i1 = faces[f * 3 + 1], i2 = faces[f * 3 + 2];
         if (i0 >= 0 && i0 < N && i1 >= 0 && i1 < N && i2 >= 0 && i2 < N) {
             const Vtx *vp = vtx + (size_t)p * N;
-            Vtx v0 = vp[i0], v1 = vp[i1], v2 = vp[i2];
-            const int m = (v0.Z >= near ? 1 : 0) | (v1.Z >= near ? 2 : 0) | (v2.Z >= near ? 4 : 0);
-            if (m) {
-                const double a0 = v1.X - v0.X, a1 = v1.Y - v0.Y, a2 = v1.Z - v0.Z;
-                const double b0 = v2.X - v0.X, b1 = v2.Y - v0.Y, b2 = v2.Z - v0.Z;
-                pl.n0 = a1 * b2 - a2 * b1;
-                pl.n1 = a2 * b0 - a0 * b2;
-                pl.n2 = a0 * b1 - a1 * b0;
-                pl.num = (pl.n0 * v0.X + pl.n1 * v0.Y) + pl.n2 * v0.Z;
-                if (m == 7) {
-                    pc0 = make_piece(v0.U, v0.V, v1.U, v1.V, v2.U, v2.V, W, H);
-                } else if (m == 1 || m == 2 || m == 4) {           // one vertex inside: (a, ab, ac)
-                    rotate_left(v0, v1, v2, m == 1 ? 0 : m == 2 ? 1 : 2);
-                    int Ub, Vb, Uc, Vc;
-                    clip_snap(c, v0, v1, near, &Ub, &Vb);
-                    clip_snap(c, v0, v2, near, &Uc, &Vc);
-                    pc0 = make_piece(v0.U, v0.V, Ub, Vb, Uc, Vc, W, H);
-                } else {                                            // one vertex outside, c: (a, b, bc) and (a, bc, ac)
-                    rotate_left(v0, v1, v2, m == 3 ? 0 : m == 6 ? 1 : 2);
-                    int Ub, Vb, Ua, Va;
-                    clip_snap(c, v1, v2, near, &Ub, &Vb);
-                    clip_snap(c, v0, v2, near, &Ua, &Va);
-                    pc0 = make_piece(v0.U, v0.V, v1.U, v1.V, Ub, Vb, W, H);
-                    pc1 = make_piece(v0.U, v0.V, Ub, Vb, Ua, Va, W, H);
-                }
-            }
+            fc = clip_face(c, vp[i0], vp[i1], vp[i2], near, W, H);
         }
     }
-    unsigned *img = depth + (size_t)p * H * W;
-    sweep(pc0, pl, img, W, c, near, far);
-    if (__any(pc1.w != 0)) sweep(pc1, pl, img, W, c, near, far);
+    const DepthSink sink = {depth + (size_t)p * H * W, W, near, far};
+    sweep(fc.pc0, fc.pl, sink, c);
+    if (__any(fc.pc1.w != 0)) sweep(fc.pc1, fc.pl, sink, c);
 }
 
 __global__ __launch_bounds__(kBlock) void k_resolve(unsigned *__restrict__ depth, size_t total)

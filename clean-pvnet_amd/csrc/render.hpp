@@ -2,14 +2,13 @@
 // "Colour renders").  Included at the end of pvnet_vote.hip after ct_augment.hpp: built with -ffp-contract=off, every double
 // operation below rounds once, in the order written, so that the numpy twin (tests/render_twin.py) gives the same bytes.
 //
-// The coverage code restates that of pvnet_vsd.hip (snapping, near clip, edge functions, the owns-its-line rule, the sweep by
-// piece size) because that library does not record which triangle owns a sample; tests/test_gpu_render.py holds the two
-// rasterisers to the same depth bits.
+// The coverage rules (snapping, near clip, edge functions, the owns-its-line rule, the sweep by piece size) are those of
+// raster.hpp, which the depth rasteriser of pvnet_vsd.hip draws with too; only the sink of a covered sample is this file's own.
 //
 //   k_rc_vertices  grid (vertex tiles, B*M): eye-space coordinates in binary64 and the snapped image coordinates of every
 //                  (instance, vertex), once.
 //   k_rc_raster    grid (tiles of 256 faces, B*M).  A lane sets up one face; a piece whose bounding box holds at most
-//                  kRcSmall samples is swept by its own lane, every other piece by the whole wave, 64 blocks of 8x8 samples at a
+//                  raster::kSmall samples is swept by its own lane, every other piece by the whole wave, 64 blocks of 8x8 samples at a
 //                  time.  Every covered sample offers (bits of float32(Z) << 32) | (m << 24) | f to the 8-byte key image with one
 //                  unsigned 64-bit atomicMin: nearest surface, then lowest instance, then lowest face.
 //   k_rc_shade     one lane per four consecutive pixels of the flattened batch: the owner's colour, label, depth and face, or the
@@ -32,28 +31,14 @@
 
 namespace {
 
-constexpr int kRcSmall = 32;            // a piece with at most this many samples in its bounding box is swept by its own lane
-constexpr int kRcBadCoord = INT_MIN;    // snapped coordinate of a vertex that has none
-constexpr double kRcSnapLimit = 268435456.0;   // 2^28
+#include "raster.hpp"
+
 constexpr int kRcMaxSide = 16384;
 constexpr int kRcMaxM = 255;
 constexpr int kRcMaxFaces = 1 << 24;
 constexpr unsigned long long kRcEmpty = ~0ull;
 
-struct RcVtx {                          // 32 bytes, one per (instance, vertex slot)
-    double X, Y, Z;
-    int U, V;
-};
-static_assert(sizeof(RcVtx) == 32, "pvnet_vote.h promises 32 bytes per vertex slot");
-
-struct RcCam { double fx, s, cx, fy, cy; };
-
-struct RcPiece {                        // a clipped, oriented (positive area) triangle in snapped coordinates, with its samples
-    int ax, ay, bx, by, cx, cy;
-    int xmin, ymin, w, h;               // w == 0: no piece
-};
-
-struct RcPlane { double n0, n1, n2, num; };
+static_assert(sizeof(raster::Vtx) == 32, "pvnet_vote.h promises 32 bytes per vertex slot");
 
 struct RcRange { int v0, vn, f0, fn; bool ok; };
 
@@ -69,13 +54,6 @@ struct RcScene {                        // what the three kernels share
 struct __attribute__((aligned(16))) RcVec4f { float v[4]; };
 struct __attribute__((aligned(16))) RcVec4i { int v[4]; };
 struct __attribute__((aligned(16))) RcVec2k { unsigned long long v[2]; };
-
-__device__ RcCam rc_load_cam(const double *K)
-{
-    RcCam c;
-    c.fx = K[0], c.s = K[1], c.cx = K[2], c.fy = K[4], c.cy = K[5];
-    return c;
-}
 
 __device__ bool rc_pose_finite(const double *P)
 {
@@ -98,256 +76,57 @@ __device__ RcRange rc_range(const RcScene &s, int inst)
     return r;
 }
 
-// u = (fx*X + s*Y)/Z + cx, v = (fy*Y)/Z + cy, snapped to 8 sub-pixel bits; kRcBadCoord when out of range or not a number
-__device__ void rc_project_snap(const RcCam &c, double X, double Y, double Z, int *U, int *V)
-{
-    const double u = (c.fx * X + c.s * Y) / Z + c.cx;
-    const double v = (c.fy * Y) / Z + c.cy;
-    const double Ud = floor(256.0 * u + 0.5), Vd = floor(256.0 * v + 0.5);
-    const bool ok = fabs(Ud) <= kRcSnapLimit && fabs(Vd) <= kRcSnapLimit;      // false for NaN
-    *U = ok ? (int)Ud : kRcBadCoord;
-    *V = ok ? (int)Vd : kRcBadCoord;
-}
-
-__global__ __launch_bounds__(kBlock) void k_rc_vertices(RcScene s, RcVtx *__restrict__ vtx)
+__global__ __launch_bounds__(kBlock) void k_rc_vertices(RcScene s, raster::Vtx *__restrict__ vtx)
 {
     const int inst = blockIdx.y;
     const RcRange r = rc_range(s, inst);
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (!r.ok || i >= r.vn) return;
-    const double *T = s.pose + (size_t)inst * 12;
-    const RcCam c = rc_load_cam(s.K + (s.K_batched ? (size_t)(inst / s.M) * 9 : 0));
+    const raster::Cam c = raster::load_cam(s.K + (s.K_batched ? (size_t)(inst / s.M) * 9 : 0));
     const float *p = s.pts + ((size_t)r.v0 + i) * 3;
-    const double x = (double)p[0], y = (double)p[1], z = (double)p[2];
-    RcVtx o;
-    o.X = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
-    o.Y = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
-    o.Z = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
-    o.U = o.V = kRcBadCoord;
-    if (o.Z >= s.near) rc_project_snap(c, o.X, o.Y, o.Z, &o.U, &o.V);
-    vtx[(size_t)inst * s.Nmax + i] = o;
+    vtx[(size_t)inst * s.Nmax + i] = raster::vertex(s.pose + (size_t)inst * 12, c, (double)p[0], (double)p[1], (double)p[2], s.near);
 }
 
-// The vertex where the edge from the inside vertex p to the outside vertex q meets Z = near, projected and snapped.
-__device__ void rc_clip_snap(const RcCam &c, const RcVtx &p, const RcVtx &q, double near, int *U, int *V)
-{
-    const double t = (near - p.Z) / (q.Z - p.Z);
-    const double X = p.X + t * (q.X - p.X);
-    const double Y = p.Y + t * (q.Y - p.Y);
-    rc_project_snap(c, X, Y, near, U, V);
-}
+// The key sink: a covered sample offers (bits of float32(Z) << 32) | tag with one unsigned 64-bit atomicMin, tag = (m << 24) | f
+// of the lane that owns the piece.
+struct RcKeySink {
+    unsigned long long *img;
+    int W;
+    double near, far;
+    unsigned tag;
 
-__device__ RcPiece rc_make_piece(int U0, int V0, int U1, int V1, int U2, int V2, int W, int H)
-{
-    RcPiece t;
-    t.w = t.h = 0;
-    t.ax = t.ay = t.bx = t.by = t.cx = t.cy = t.xmin = t.ymin = 0;
-    if (U0 == kRcBadCoord || U1 == kRcBadCoord || U2 == kRcBadCoord) return t;
-    const long long area2 = (long long)(U1 - U0) * (V2 - V0) - (long long)(V1 - V0) * (U2 - U0);
-    if (area2 == 0) return t;
-    if (area2 < 0) {
-        int k = U1; U1 = U2; U2 = k;
-        k = V1; V1 = V2; V2 = k;
+    __device__ void operator()(int x, int y, const raster::Plane &pl, const raster::Cam &c) const
+    {
+        double dx, dy, Z;
+        if (!raster::plane_depth(pl, c, x, y, &dx, &dy, &Z)) return;
+        if (Z >= near && Z <= far)
+            atomicMin(img + (size_t)y * W + x, ((unsigned long long)__float_as_uint((float)Z) << 32) | tag);
     }
-    // samples (256x + 128, 256y + 128) inside the vertices' box: x >= (Umin - 128)/256, x <= (Umax - 128)/256
-    int xmin = (min(U0, min(U1, U2)) - 128 + 255) >> 8, xmax = (max(U0, max(U1, U2)) - 128) >> 8;
-    int ymin = (min(V0, min(V1, V2)) - 128 + 255) >> 8, ymax = (max(V0, max(V1, V2)) - 128) >> 8;
-    xmin = max(xmin, 0);
-    ymin = max(ymin, 0);
-    xmax = min(xmax, W - 1);
-    ymax = min(ymax, H - 1);
-    if (xmin > xmax || ymin > ymax) return t;
-    t.ax = U0; t.ay = V0; t.bx = U1; t.by = V1; t.cx = U2; t.cy = V2;
-    t.xmin = xmin; t.ymin = ymin; t.w = xmax - xmin + 1; t.h = ymax - ymin + 1;
-    return t;
-}
 
-// E = dx*(py - ay) - dy*(px - ax) > 0, or = 0 on an edge that owns its line.  |dx|, |dy| <= 2^29 and |py - ay|, |px - ax| <
-// 2^29: every product fits 59 bits.
-__device__ bool rc_edge_in(int ax, int ay, int bx, int by, int px, int py)
-{
-    const int dx = bx - ax, dy = by - ay;
-    const long long E = (long long)dx * (py - ay) - (long long)dy * (px - ax);
-    const bool owns = dy > 0 || (dy == 0 && dx > 0);
-    return E > 0 || (E == 0 && owns);
-}
+    __device__ RcKeySink of(int lane) const { return {img, W, near, far, (unsigned)raster::rl((int)tag, lane)}; }
+};
 
-__device__ bool rc_covered(const RcPiece &t, int x, int y)
-{
-    const int px = 256 * x + 128, py = 256 * y + 128;
-    return rc_edge_in(t.ax, t.ay, t.bx, t.by, px, py) && rc_edge_in(t.bx, t.by, t.cx, t.cy, px, py) &&
-           rc_edge_in(t.cx, t.cy, t.ax, t.ay, px, py);
-}
-
-// The largest value an edge function takes on the samples x0..x1, y0..y1 is negative: no sample of the block is inside.
-__device__ bool rc_edge_rejects(int ax, int ay, int bx, int by, int x0, int y0, int x1, int y1)
-{
-    const int dx = bx - ax, dy = by - ay;
-    const int py = 256 * (dx > 0 ? y1 : y0) + 128, px = 256 * (dy > 0 ? x0 : x1) + 128;
-    return (long long)dx * (py - ay) - (long long)dy * (px - ax) < 0;
-}
-
-__device__ bool rc_block_rejected(const RcPiece &t, int x0, int y0, int x1, int y1)
-{
-    return rc_edge_rejects(t.ax, t.ay, t.bx, t.by, x0, y0, x1, y1) || rc_edge_rejects(t.bx, t.by, t.cx, t.cy, x0, y0, x1, y1) ||
-           rc_edge_rejects(t.cx, t.cy, t.ax, t.ay, x0, y0, x1, y1);
-}
-
-// dy = ((y+0.5) - cy)/fy, dx = (((x+0.5) - cx) - s*dy)/fx, den = (n0*dx + n1*dy) + n2, Z = num/den; false when den == 0
-__device__ bool rc_plane_depth(const RcPlane &pl, const RcCam &c, int x, int y, double *dx_, double *dy_, double *Z)
-{
-    const double dy = (((double)y + 0.5) - c.cy) / c.fy;
-    const double dx = ((((double)x + 0.5) - c.cx) - c.s * dy) / c.fx;
-    const double den = (pl.n0 * dx + pl.n1 * dy) + pl.n2;
-    *dx_ = dx, *dy_ = dy;
-    if (den == 0.0) return false;
-    *Z = pl.num / den;
-    return true;
-}
-
-// One covered sample offers its key; `tag` = (m << 24) | f.
-__device__ void rc_offer(unsigned long long *__restrict__ img, int W, int x, int y, const RcPlane &pl, const RcCam &c, double near,
-                         double far, unsigned tag)
-{
-    double dx, dy, Z;
-    if (!rc_plane_depth(pl, c, x, y, &dx, &dy, &Z)) return;
-    if (Z >= near && Z <= far)
-        atomicMin(img + (size_t)y * W + x, ((unsigned long long)__float_as_uint((float)Z) << 32) | tag);
-}
-
-__device__ int rc_rl(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
-
-__device__ double rc_rl(double v, int lane)
-{
-    return __hiloint2double(rc_rl(__double2hiint(v), lane), rc_rl(__double2loint(v), lane));
-}
-
-__device__ RcPiece rc_rl(const RcPiece &t, int lane)
-{
-    RcPiece o;
-    o.ax = rc_rl(t.ax, lane); o.ay = rc_rl(t.ay, lane); o.bx = rc_rl(t.bx, lane); o.by = rc_rl(t.by, lane);
-    o.cx = rc_rl(t.cx, lane); o.cy = rc_rl(t.cy, lane);
-    o.xmin = rc_rl(t.xmin, lane); o.ymin = rc_rl(t.ymin, lane); o.w = rc_rl(t.w, lane); o.h = rc_rl(t.h, lane);
-    return o;
-}
-
-// One piece per lane (w == 0: none).  Small pieces by their own lane, the others by the whole wave.  Called by whole waves.
-__device__ void rc_sweep(const RcPiece &mine, const RcPlane &pl, unsigned tag, unsigned long long *__restrict__ img, int W,
-                         const RcCam &c, double near, double far)
-{
-    const int lane = threadIdx.x & 63;
-    const int cnt = mine.w * mine.h;                       // <= 2^28 by kRcMaxSide
-    const bool small = cnt <= kRcSmall;
-    if (small) {
-        int x = mine.xmin, y = mine.ymin;
-        for (int i = 0; i < cnt; ++i) {
-            if (rc_covered(mine, x, y)) rc_offer(img, W, x, y, pl, c, near, far, tag);
-            if (++x == mine.xmin + mine.w) {
-                x = mine.xmin;
-                ++y;
-            }
-        }
-    }
-    unsigned long long big = __ballot(!small);
-    while (big) {
-        const int src = __ffsll((long long)big) - 1;
-        big &= big - 1;
-        const RcPiece t = rc_rl(mine, src);
-        RcPlane q;
-        q.n0 = rc_rl(pl.n0, src); q.n1 = rc_rl(pl.n1, src); q.n2 = rc_rl(pl.n2, src); q.num = rc_rl(pl.num, src);
-        const unsigned qtag = (unsigned)rc_rl((int)tag, src);
-        const int xmax = t.xmin + t.w - 1, ymax = t.ymin + t.h - 1;
-        const int bx0 = t.xmin >> 3, by0 = t.ymin >> 3;
-        const int nbx = (xmax >> 3) - bx0 + 1, nby = (ymax >> 3) - by0 + 1;
-        const int nblocks = nbx * nby;
-        for (int base = 0; base < nblocks; base += 64) {
-            const int bi = base + lane;
-            const int by = bi / nbx, bx = bi - by * nbx;
-            bool live = bi < nblocks;
-            if (live) {
-                const int x0 = max((bx0 + bx) << 3, t.xmin), y0 = max((by0 + by) << 3, t.ymin);
-                const int x1 = min(((bx0 + bx) << 3) + 7, xmax), y1 = min(((by0 + by) << 3) + 7, ymax);
-                live = !rc_block_rejected(t, x0, y0, x1, y1);
-            }
-            unsigned long long todo = __ballot(live);
-            while (todo) {
-                const int j = __ffsll((long long)todo) - 1;
-                todo &= todo - 1;
-                const int x = ((bx0 + rc_rl(bx, j)) << 3) + (lane & 7), y = ((by0 + rc_rl(by, j)) << 3) + (lane >> 3);
-                if (x >= t.xmin && x <= xmax && y >= t.ymin && y <= ymax && rc_covered(t, x, y))
-                    rc_offer(img, W, x, y, q, c, near, far, qtag);
-            }
-        }
-    }
-}
-
-__device__ void rc_rotate_left(RcVtx &a, RcVtx &b, RcVtx &c, int r)
-{
-    if (r == 1) {
-        const RcVtx k = a; a = b; b = c; c = k;
-    } else if (r == 2) {
-        const RcVtx k = c; c = b; b = a; a = k;
-    }
-}
-
-// n = a x b with a = v1 - v0, b = v2 - v0, num = (n0*v00 + n1*v01) + n2*v02
-__device__ RcPlane rc_plane(const RcVtx &v0, const RcVtx &v1, const RcVtx &v2, double *a, double *b)
-{
-    a[0] = v1.X - v0.X, a[1] = v1.Y - v0.Y, a[2] = v1.Z - v0.Z;
-    b[0] = v2.X - v0.X, b[1] = v2.Y - v0.Y, b[2] = v2.Z - v0.Z;
-    RcPlane pl;
-    pl.n0 = a[1] * b[2] - a[2] * b[1];
-    pl.n1 = a[2] * b[0] - a[0] * b[2];
-    pl.n2 = a[0] * b[1] - a[1] * b[0];
-    pl.num = (pl.n0 * v0.X + pl.n1 * v0.Y) + pl.n2 * v0.Z;
-    return pl;
-}
-
-__global__ __launch_bounds__(kBlock) void k_rc_raster(RcScene s, const RcVtx *__restrict__ vtx, unsigned long long *__restrict__ keys)
+__global__ __launch_bounds__(kBlock) void k_rc_raster(RcScene s, const raster::Vtx *__restrict__ vtx, unsigned long long *__restrict__ keys)
 {
     const int inst = blockIdx.y;
     const RcRange r = rc_range(s, inst);
     if (!r.ok || !rc_pose_finite(s.pose + (size_t)inst * 12)) return;      // block-uniform: the instance draws nothing
     const int b = inst / s.M, m = inst - b * s.M;
-    const RcCam c = rc_load_cam(s.K + (s.K_batched ? (size_t)b * 9 : 0));
+    const raster::Cam c = raster::load_cam(s.K + (s.K_batched ? (size_t)b * 9 : 0));
     const int f = blockIdx.x * kBlock + threadIdx.x;
-    const int W = s.W, H = s.H;
-    const double near = s.near;
-    RcPiece pc0 = rc_make_piece(kRcBadCoord, 0, 0, 0, 0, 0, W, H), pc1 = pc0;
-    RcPlane pl = {0.0, 0.0, 0.0, 0.0};
+    raster::Face fc = {};                                                   // no piece
     if (f < r.fn) {
         const int32_t *row = s.faces + ((size_t)r.f0 + f) * 3;
         const int i0 = row[0], i1 = row[1], i2 = row[2];
         if (i0 >= 0 && i0 < r.vn && i1 >= 0 && i1 < r.vn && i2 >= 0 && i2 < r.vn) {
-            const RcVtx *vp = vtx + (size_t)inst * s.Nmax;
-            RcVtx v0 = vp[i0], v1 = vp[i1], v2 = vp[i2];
-            const int in = (v0.Z >= near ? 1 : 0) | (v1.Z >= near ? 2 : 0) | (v2.Z >= near ? 4 : 0);
-            if (in) {
-                double a[3], bb[3];
-                pl = rc_plane(v0, v1, v2, a, bb);
-                if (in == 7) {
-                    pc0 = rc_make_piece(v0.U, v0.V, v1.U, v1.V, v2.U, v2.V, W, H);
-                } else if (in == 1 || in == 2 || in == 4) {         // one vertex inside: (a, ab, ac)
-                    rc_rotate_left(v0, v1, v2, in == 1 ? 0 : in == 2 ? 1 : 2);
-                    int Ub, Vb, Uc, Vc;
-                    rc_clip_snap(c, v0, v1, near, &Ub, &Vb);
-                    rc_clip_snap(c, v0, v2, near, &Uc, &Vc);
-                    pc0 = rc_make_piece(v0.U, v0.V, Ub, Vb, Uc, Vc, W, H);
-                } else {                                            // one vertex outside, c: (a, b, bc) and (a, bc, ac)
-                    rc_rotate_left(v0, v1, v2, in == 3 ? 0 : in == 6 ? 1 : 2);
-                    int Ub, Vb, Ua, Va;
-                    rc_clip_snap(c, v1, v2, near, &Ub, &Vb);
-                    rc_clip_snap(c, v0, v2, near, &Ua, &Va);
-                    pc0 = rc_make_piece(v0.U, v0.V, v1.U, v1.V, Ub, Vb, W, H);
-                    pc1 = rc_make_piece(v0.U, v0.V, Ub, Vb, Ua, Va, W, H);
-                }
-            }
+            const raster::Vtx *vp = vtx + (size_t)inst * s.Nmax;
+            fc = raster::clip_face(c, vp[i0], vp[i1], vp[i2], s.near, s.W, s.H);
         }
     }
     const unsigned tag = ((unsigned)m << 24) | ((unsigned)f & 0xffffffu);   // f < fn <= 2^24 wherever a piece exists
-    unsigned long long *img = keys + (size_t)b * H * W;
-    rc_sweep(pc0, pl, tag, img, W, c, near, s.far);
-    if (__any(pc1.w != 0)) rc_sweep(pc1, pl, tag, img, W, c, near, s.far);
+    const RcKeySink sink = {keys + (size_t)b * s.H * s.W, s.W, s.near, s.far, tag};
+    raster::sweep(fc.pc0, fc.pl, sink, c);
+    if (__any(fc.pc1.w != 0)) raster::sweep(fc.pc1, fc.pl, sink, c);
 }
 
 struct RcPixel { uint8_t c[3], label; float z; int face; };
@@ -362,7 +141,7 @@ __device__ uint8_t rc_to_u8(double v)
 
 // The shading contract of the header for the owner (m, f) of pixel (x, y) of image b; false when the key names nothing that
 // can be read (never for a key the raster wrote).
-__device__ bool rc_shade_owner(const RcScene &s, const RcVtx *__restrict__ vtx, int b, int x, int y, int m, int f, double ambient,
+__device__ bool rc_shade_owner(const RcScene &s, const raster::Vtx *__restrict__ vtx, int b, int x, int y, int m, int f, double ambient,
                                RcPixel *out)
 {
     if (m >= s.M) return false;
@@ -372,12 +151,12 @@ __device__ bool rc_shade_owner(const RcScene &s, const RcVtx *__restrict__ vtx, 
     const int32_t *row = s.faces + ((size_t)r.f0 + f) * 3;
     const int i0 = row[0], i1 = row[1], i2 = row[2];
     if (i0 < 0 || i0 >= r.vn || i1 < 0 || i1 >= r.vn || i2 < 0 || i2 >= r.vn) return false;
-    const RcVtx *vp = vtx + (size_t)inst * s.Nmax;
-    const RcVtx v0 = vp[i0], v1 = vp[i1], v2 = vp[i2];
-    const RcCam c = rc_load_cam(s.K + (s.K_batched ? (size_t)b * 9 : 0));
+    const raster::Vtx *vp = vtx + (size_t)inst * s.Nmax;
+    const raster::Vtx v0 = vp[i0], v1 = vp[i1], v2 = vp[i2];
+    const raster::Cam c = raster::load_cam(s.K + (s.K_batched ? (size_t)b * 9 : 0));
     double a[3], bb[3], dx, dy, Zd = 0.0;
-    const RcPlane pl = rc_plane(v0, v1, v2, a, bb);
-    rc_plane_depth(pl, c, x, y, &dx, &dy, &Zd);
+    const raster::Plane pl = raster::plane(v0, v1, v2, a, bb);
+    raster::plane_depth(pl, c, x, y, &dx, &dy, &Zd);
     const double n[3] = {pl.n0, pl.n1, pl.n2};
     const double P[3] = {dx * Zd, dy * Zd, Zd};
     const double q[3] = {P[0] - v0.X, P[1] - v0.Y, P[2] - v0.Z};
@@ -403,7 +182,7 @@ __device__ bool rc_shade_owner(const RcScene &s, const RcVtx *__restrict__ vtx, 
     return true;
 }
 
-__global__ __launch_bounds__(kBlock) void k_rc_shade(RcScene s, const RcVtx *__restrict__ vtx, const unsigned long long *__restrict__ keys,
+__global__ __launch_bounds__(kBlock) void k_rc_shade(RcScene s, const raster::Vtx *__restrict__ vtx, const unsigned long long *__restrict__ keys,
                                                      const uint8_t *__restrict__ bg, int bg_vec, uint32_t bg_color, double ambient,
                                                      uint8_t *__restrict__ img, uint8_t *__restrict__ label, float *__restrict__ depth,
                                                      int32_t *__restrict__ area, int32_t *__restrict__ face)
@@ -505,7 +284,7 @@ RcLayout rc_layout(int B, int M, int Nmax, int H, int W)
 {
     RcLayout L;
     L.vtx = 0;
-    L.keys = aug_up(sizeof(RcVtx) * (size_t)B * M * Nmax);
+    L.keys = aug_up(sizeof(raster::Vtx) * (size_t)B * M * Nmax);
     L.total = L.keys + aug_up(sizeof(unsigned long long) * (size_t)B * H * W);
     return L;
 }
@@ -547,7 +326,7 @@ PVV_EXPORT int pvv_render_color(const float *d_pts, const uint8_t *d_colors, con
     const RcLayout L = rc_layout(B, M, Nmax, H, W);
     if (workspace_bytes < L.total) return fail(PVV_E_WORKSPACE, "render: workspace smaller than pvv_render_workspace_bytes()");
     hipStream_t st = (hipStream_t)stream;
-    RcVtx *vtx = (RcVtx *)((uint8_t *)d_workspace + L.vtx);
+    raster::Vtx *vtx = (raster::Vtx *)((uint8_t *)d_workspace + L.vtx);
     unsigned long long *keys = (unsigned long long *)((uint8_t *)d_workspace + L.keys);
     const size_t total = (size_t)B * H * W;
     if (hipMemsetAsync(keys, 0xff, total * sizeof(unsigned long long), st) != hipSuccess) return fail(PVV_E_ARG, "render: hipMemsetAsync failed");
@@ -559,12 +338,12 @@ PVV_EXPORT int pvv_render_color(const float *d_pts, const uint8_t *d_colors, con
     if (Fmax > 0) {
         hipLaunchKernelGGL(k_rc_vertices, dim3((Nmax + kBlock - 1) / kBlock, B * M), dim3(kBlock), 0, st, s, vtx);
         if (int e = check_launch("k_rc_vertices")) return e;
-        hipLaunchKernelGGL(k_rc_raster, dim3((Fmax + kBlock - 1) / kBlock, B * M), dim3(kBlock), 0, st, s, (const RcVtx *)vtx, keys);
+        hipLaunchKernelGGL(k_rc_raster, dim3((Fmax + kBlock - 1) / kBlock, B * M), dim3(kBlock), 0, st, s, (const raster::Vtx *)vtx, keys);
         if (int e = check_launch("k_rc_raster")) return e;
     }
     const uint32_t bgc = (uint32_t)h_bg_color[0] | ((uint32_t)h_bg_color[1] << 8) | ((uint32_t)h_bg_color[2] << 16);
     const int bg_vec = d_bg && (uintptr_t)d_bg % 4 == 0;
-    hipLaunchKernelGGL(k_rc_shade, dim3((unsigned)((total + 1023) / 1024)), dim3(kBlock), 0, st, s, (const RcVtx *)vtx,
+    hipLaunchKernelGGL(k_rc_shade, dim3((unsigned)((total + 1023) / 1024)), dim3(kBlock), 0, st, s, (const raster::Vtx *)vtx,
                        (const unsigned long long *)keys, d_bg, bg_vec, bgc, ambient, d_img, d_label, d_depth, d_area, d_face);
     return check_launch("k_rc_shade");
 }

@@ -1,7 +1,7 @@
 """Colour renders on the MI355X (clean_pvnet_amd.render) against the numpy twin (tests/render_twin.py, itself pinned in
 tests/test_render.py): img, label, depth, face and area as bytes; the near clip; the ties of coincident triangles; reruns and
 batch independence; with one instance the depth bits of the depth rasteriser (clean_pvnet_amd.vsd.render_depth), which is what
-holds the two restated rasterisers together; and the hand-off of the outputs to the augmentation modules.
+holds the two rasterisers (one coverage code, two sinks) together; and the hand-off of the outputs to the augmentation modules.
 
 The shapes are the smallest at which these kernels can go wrong: 70 x 45 (neither side a multiple of 8 or 4, 2 x 3150 pixels = 1575
 groups of four over two blocks of the shading pass with a block that spans both images), a mesh of 194 faces and one of 300 (two
