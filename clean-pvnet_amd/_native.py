@@ -44,6 +44,9 @@ def call(lib, symbol, dev, *args):
 
 
 def workspace(nbytes, dev):
+    """``nbytes`` (at least 16) of uninitialised device memory from the caching allocator.  A caller must not rely on its contents --
+    a block comes back as the last call left it -- and every kernel clears what it assumes clear: tests/test_gpu_guarded.py enforces
+    this by running each entry point on workspaces filled with 0x00, 0xFF and 0xA5."""
     import torch
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)   # caching allocator: stream-ordered, no hipMalloc per call
 
