@@ -474,6 +474,9 @@ PVV_EXPORT int pvv_count_inliers(const float *d_direct, const float *d_coords, c
 // ---- detector augmentation: cut-and-paste, warp, colour steps, boxes on the output map (ABI v8, additive) -----
 #include "ct_augment.hpp"
 
+// ---- T-LESS PVNet augmentation: rotated cut-outs, occlusion, the crop around the target (ABI v8, additive) -----
+#include "tless_augment.hpp"
+
 // ---- colour renders: shaded images, instance labels and depth of a batch of scenes (ABI v8, additive) -----
 #include "render.hpp"
 

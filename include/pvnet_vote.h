@@ -665,6 +665,86 @@ int pvv_ct_augment(const uint8_t *d_img, const uint8_t *d_label, int B, int H, i
                    size_t workspace_bytes, uint8_t *d_orig, float *d_inp, int32_t *d_boxes, void *stream);
 
 /* ------------------------------------------------------------------------
+ * T-LESS PVNet augmentation: the T-LESS PVNet loader's training sample from a rotated target cut-out, rotated distractor
+ * cut-outs and a background, and its crop around what is left of the target (ABI v8, additive).  Citations:
+ *   T = lib/utils/tless/tless_train_utils.py (cut_and_paste :94-120, get_fused_image :123-136, rotate_image :153-172)
+ *   U = lib/utils/tless/tless_utils.py:86-97 (cut_and_paste)
+ *   D = lib/datasets/tless_train/pvnet.py (read_data :60-69, get_training_img :73-105, __getitem__ :113-116)
+ *   V = lib/utils/tless/tless_pvnet_utils.py (magnify_box :13-18, augment :21-73)
+ *   G = lib/utils/data_utils.py (affine_transform :159-162, color_aug :202-210)
+ * The rules of "Detector augmentation" hold: device pointers, caller-owned workspace (8-byte aligned), the caller's stream last;
+ * nothing is read back, nothing synchronises, nothing is allocated or kept; no random number and no transcendental function on
+ * the device; no fused multiply-add; the grey mean is the only floating-point sum (binary64, fixed tree); every other reduction
+ * is over integers; every source tap is tested against its image in 64 bits before an address is formed.
+ * tests/tless_augment_twin.py is this contract in numpy; DESIGN.md section 22 states it in full.
+ * Limits, refused with PVV_E_ARG beyond them: 1 <= B <= 65535, sides in [1, 16384], 0 <= N <= PVV_TLESS_MAX_N, K <= 65535.
+ *
+ * A cut-out's record, PVV_TLESS_CUT_BYTES on the device, 8-byte aligned, built by the host in binary64 (T:154-165):
+ *   binary64 M[6]   getRotationMatrix2D((w / 2, h / 2), angle, 1) with M[2] += bound_w / 2 - w / 2, M[5] += bound_h / 2 - h / 2
+ *   binary64 inv[6] its inverse in invertAffineTransform's operation order
+ *   int32 bound_h = int(h |cos| + w |sin|), bound_w = int(h |sin| + w |cos|), two int32 of padding
+ * Both bounds are <= pvv_tless_rotate_side(h, w) = floor(sqrt(h^2 + w^2)).
+ * ---------------------------------------------------------------------- */
+#define PVV_TLESS_MAX_N 16
+#define PVV_TLESS_CUT_BYTES 112
+
+/* Host-only.  D, the side of the square plane a rotated h x w cut-out is stored in; 0 for sides outside [1, 16384]. */
+int pvv_tless_rotate_side(int h, int w);
+
+/* T:153-172 for P cut-outs: d_src [P,h,w,channels] uint8, channels 1 or 3, d_cuts P records -> d_out [P,D,D,channels]: inside
+ * bound_w x bound_h the warp through inv with zero border -- nearest == 0: the 8-bit bilinear rule of pvv_crop_boxes (what the
+ * reference's call does: its INTER_NEAREST stands in the position of dst, so the flags keep their default); nearest != 0: the
+ * rule of pvv_uncrop_mask -- and zero outside.  One launch. */
+int pvv_tless_rotate(const uint8_t *d_src, const void *d_cuts, int P, int h, int w, int channels, int D, int nearest,
+                     uint8_t *d_out, void *stream);
+
+/* Host-only.  Bytes pvv_tless_compose needs: the accumulators, a coverage byte per canvas pixel and the rotated masks of the
+ * 1 + N cut-outs (one byte per pixel of their D x D planes); 0 with pvv_last_error set when a size is refused. */
+size_t pvv_tless_compose_workspace_bytes(int B, int N, int H, int W, int ht, int wt, int ho, int wo);
+
+/* D:73-105 for a batch.  d_bg [B,H,W,3], d_fused_bg [B,H,W,3] or NULL (= d_bg), d_img [B,ht,wt,3], d_mask [B,ht,wt],
+ * d_other_img [B,N,ho,wo,3], d_other_mask [B,N,ho,wo], all uint8; d_kpt [B,K,2] binary64; d_num [B] int32 or NULL (= N):
+ * distractors n >= num[b] are skipped; d_cuts [B,1+N] records, the target's first; d_place_u [B,1+N,2] binary64 in [0, 1), the
+ * uniforms of dst_y and dst_x; d_flags [B,2] int32: target on top by draw (D:93), black fused background (T:95).
+ * The masks are rotated as one-channel images (T:115, D:65); a rotated cut-out covers where its rotated mask != 0, its box and
+ * placement are U:87-93 with randint(lo, hi) = lo + floor(u (hi - lo)) for hi > lo, lo otherwise; pixel_num is the sum of the
+ * rotated target mask's values (D:74).  Keypoints: (M . kpt - (x_min, y_min)) + (dst_x, dst_y) (D:66, 80-82).  The fused canvas
+ * is d_fused_bg or black with the distractors pasted in order, later over earlier (T:105-118).  visible = the target's pixels
+ * that no distractor covers (D:96-97).  path: 0 the target over the fused canvas by draw; else 1 the distractors over the
+ * target on d_bg when (double)visible / (double)pixel_num >= ratio; else 2 as 0; 3 a target whose rotated mask is empty (the
+ * reference raises): the fused canvas, an empty mask.  ratio > 0.  Colours are sampled through inv when a pixel's owner is
+ * known; rotated images are not stored.  Writes d_out_img [B,H,W,3], d_out_mask [B,H,W] (0 / 1), d_out_kpt [B,K,2],
+ * d_bbox [B,4] int32 (x, y, x + w - 1, y + h - 1 of the mask, D:102-103; the whole canvas for an empty mask), d_path [B] int32,
+ * d_place [B,1+N,6] int32 (y_min, x_min, h, w, dst_y, dst_x; (0, 0, -1, -1, 0, 0) for a skipped or empty cut-out) and
+ * d_visible [B,2] int64 (visible, pixel_num).  A fill and at most six launches. */
+int pvv_tless_compose(const uint8_t *d_bg, const uint8_t *d_fused_bg, const uint8_t *d_img, const uint8_t *d_mask,
+                      const double *d_kpt, const uint8_t *d_other_img, const uint8_t *d_other_mask, const int32_t *d_num,
+                      const void *d_cuts, const double *d_place_u, const int32_t *d_flags, int B, int H, int W, int N, int K,
+                      int ht, int wt, int ho, int wo, int nearest, double ratio, void *d_workspace, size_t workspace_bytes,
+                      uint8_t *d_out_img, uint8_t *d_out_mask, double *d_out_kpt, int32_t *d_bbox, int32_t *d_path,
+                      int32_t *d_place, long long *d_visible, void *stream);
+
+/* Host-only.  Bytes pvv_tless_augment needs: a record per sample, one binary64 grey partial per (image, 64 x 4 tile of the
+ * input) and the grey means; 0 with pvv_last_error set when a size is refused. */
+size_t pvv_tless_augment_workspace_bytes(int B, int ih, int iw);
+
+/* V:21-73 (train) and D:115-116 for a batch.  d_img [B,H,W,3], d_mask [B,H,W] uint8, d_kpt [B,K,2] binary64, d_bbox [B,4] int32
+ * (x0, y0, x1, y1) on the device; d_factor [B] float32, the drawn scale factor; d_box_ratio [B] binary64; d_colour: B records of
+ * PVV_CT_AUGMENT_PARAM_BYTES whose colour fields are read (ignored with train == 0: no colour steps).  scale = float32(max(x1
+ * - x0 + 1, y1 - y0 + 1)) * factor in float32; center = ((x0 + x1) / 2, (y0 + y1) / 2); trans = [[a, 0, iw / 2 - a cx], [0, a, ih /
+ * 2 - a cy]], a = iw / scale, in binary64 on the device; d_orig [B,ih,iw,3]: the 8-bit bilinear warp inside the rectangle of
+ * magnify_box (the box through trans, (p - mean) ratio + mean, rint half to even, clipped to iw - 1 / ih - 1) and zero outside;
+ * d_inp [B,3,ih,iw] float32: the colour steps and the normalisation of pvv_ct_augment, the grey mean taken over d_orig;
+ * d_out_mask [B,ih,iw]: the nearest warp of d_mask; d_out_kpt = trans . kpt; d_trans [B,2,3], d_center [B,2] binary64;
+ * d_scale [B,2] float32; d_box [B,4] int32, the kept rectangle, inclusive.  h_mean, h_std: 3 float32 each on the host.  At most
+ * four launches. */
+int pvv_tless_augment(const uint8_t *d_img, const uint8_t *d_mask, const double *d_kpt, const int32_t *d_bbox, int B, int H, int W,
+                      int K, int ih, int iw, int train, const float *d_factor, const double *d_box_ratio, const void *d_colour,
+                      const float *h_mean, const float *h_std, void *d_workspace, size_t workspace_bytes, uint8_t *d_orig,
+                      float *d_inp, uint8_t *d_out_mask, double *d_out_kpt, double *d_trans, double *d_center, float *d_scale,
+                      int32_t *d_box, void *stream);
+
+/* ------------------------------------------------------------------------
  * Colour renders: shaded colour images, instance labels and depth of a batch of scenes, several objects per image with exact
  * occlusion (ABI v8, additive; the newest section -- it stands in front of the two sections whose place at the end of this file
  * is fixed).  Citations:
