@@ -482,3 +482,6 @@ PVV_EXPORT int pvv_count_inliers(const float *d_direct, const float *d_coords, c
 
 // ---- detector evaluation: COCO box AP, map, match and accumulate (ABI v8, additive) -----
 #include "det_eval.hpp"
+
+// ---- optimizer step: clipped Adam / RAdam / SGD for all parameter tensors in one launch (ABI v8, additive) -----
+#include "optim.hpp"

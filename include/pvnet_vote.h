@@ -504,6 +504,68 @@ int pvv_dcn_backward(const float *d_input, const float *d_weight, const float *d
                      void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Optimizer step: the clipped Adam / RAdam / SGD step of every parameter tensor in one launch (ABI v8, additive).  Citations:
+ *   T = lib/train/trainers/trainer.py:42-45 (zero_grad, clip_grad_value_(..., 40), optimizer.step)
+ *   O = lib/train/optimizer.py:12-27 (make_optimizer: every parameter is a param group of its own)
+ *   R = lib/utils/optimizer/radam.py:29-95 (RAdam.step);  torch.optim.Adam (no amsgrad, L2 decay), torch.optim.SGD (momentum)
+ * O makes torch's foreach / fused steps run once per tensor; here one launch reads p, g, m, v once and writes p, m, v once for all
+ * of them.  Nothing synchronises, nothing is allocated and nothing is kept between calls.
+ *
+ * The table, built on the host per step and uploaded by the caller: n_tensors rows (pvv_optim_row, 80 bytes, 8-byte aligned)
+ * and the chunk prefix, n_tensors + 1 int32: chunk_start[0] = 0, chunk_start[t+1] = chunk_start[t] + ceil(numel_t /
+ * PVV_OPTIM_CHUNK), chunk_start[n_tensors] = n_chunks.  Block b works on chunk b - chunk_start[t] of the tensor t with
+ * chunk_start[t] <= b < chunk_start[t+1], found by a binary search.  Every row has numel >= 1 (the caller skips empty tensors).
+ * p, g, m, v are float32, dense, 4-byte aligned; a chunk whose four addresses are 16-byte aligned moves in 16-byte loads and
+ * stores, any other and the last numel % 4 elements one element at a time.  No byte outside [0, numel) of a tensor is touched.
+ *
+ * The arithmetic contract: float32, one rounding per operation as written, no fused multiply-add, `/` and sqrt correctly rounded,
+ * subnormals kept (tests/optim_twin.py is this contract in numpy; the device equals it byte for byte).  The scalars s[] are
+ * computed on the host in binary64 by the reference's own expressions and rounded to float32 once; t is the tensor's step count
+ * after this step, bc1 = 1 - beta1^t, bc2 = 1 - beta2^t.
+ *
+ * Clip (PVV_OPTIM_CLIP, c = clip_value >= 0):  g = g < -c ? -c : (g > c ? c : g).  A NaN stays NaN, +-Inf becomes +-c.  The
+ *   clamped value is used and not written back to g (clip_grad_value_ writes it: the one deviation from T).
+ * PVV_OPTIM_ADAM   s = {wd, 1 - beta1, beta2, 1 - beta2, sqrt(bc2), eps, -(lr / bc1)}
+ *   g = g + s0*p;  m = m + s1*(g - m);  v = v*s2 + s3*(g*g);  den = sqrt(v)/s4 + s5;  p = p + s6*(m/den)
+ * PVV_OPTIM_RADAM  s = {beta1, 1 - beta1, beta2, 1 - beta2, eps, -wd*lr, -step_size*lr}, N_sma and step_size as R:68-80
+ *   v = v*s2 + s3*(g*g);  m = m*s0 + s1*g;
+ *   unless PVV_OPTIM_ROW_NO_UPDATE (step_size = -1 of degenerated_to_sgd = False):
+ *     if PVV_OPTIM_ROW_DECAY (wd != 0):  p = p + s5*p
+ *     if PVV_OPTIM_ROW_ADAPTIVE (N_sma >= 5):  p = p + s6*(m/(sqrt(v) + s4));  else  p = p + s6*m
+ * PVV_OPTIM_SGD    s = {wd, momentum, -lr};  v is NULL and not touched
+ *   g = g + s0*p;  m = PVV_OPTIM_ROW_FIRST ? g : m*s1 + g  (m is not read on a tensor's first step);  p = p + s2*m
+ * PVV_OPTIM_ZERO_GRAD: +0 is stored to every element of g after it is read: the zero_grad() of the next iteration.
+ * ---------------------------------------------------------------------- */
+#define PVV_OPTIM_CHUNK 8192
+#define PVV_OPTIM_ADAM 0
+#define PVV_OPTIM_RADAM 1
+#define PVV_OPTIM_SGD 2
+#define PVV_OPTIM_CLIP 1
+#define PVV_OPTIM_ZERO_GRAD 2
+#define PVV_OPTIM_ROW_ADAPTIVE 1
+#define PVV_OPTIM_ROW_DECAY 2
+#define PVV_OPTIM_ROW_NO_UPDATE 4
+#define PVV_OPTIM_ROW_FIRST 8
+
+typedef struct pvv_optim_row {
+    void *p, *g, *m, *v;        /* device pointers to numel float32 each; v NULL for PVV_OPTIM_SGD */
+    long long numel;            /* >= 1 */
+    int32_t flags;              /* PVV_OPTIM_ROW_* */
+    int32_t reserved;           /* 0 */
+    float s[8];                 /* the scalars of the kind, as above; the rest 0 */
+} pvv_optim_row;
+
+/* Host-only.  PVV_OPTIM_CHUNK of the built library. */
+int pvv_optim_chunk(void);
+
+/* One launch of n_chunks blocks.  d_rows [n_tensors] and d_chunk_start [n_tensors + 1] on the device, as above; `flags` is
+ * PVV_OPTIM_CLIP | PVV_OPTIM_ZERO_GRAD or 0.  n_tensors = 0 launches nothing.  Refused with PVV_E_ARG: an unknown kind or flag,
+ * n_chunks < n_tensors or >= 2^31, a negative or NaN clip_value with PVV_OPTIM_CLIP, a NULL or misaligned table.  The library
+ * cannot check the table's contents: it lives on the device. */
+int pvv_optim_step(int kind, const pvv_optim_row *d_rows, const int32_t *d_chunk_start, int n_tensors, long long n_chunks,
+                   float clip_value, int flags, void *stream);
+
+/* ------------------------------------------------------------------------
  * Model metadata (ABI v8, additive): from a mesh's vertices to what every later stage consumes -- the farthest-point
  * keypoints (`fps_3d`), the bounding box (`corner_3d`, `center_3d`) and the diameter.  Citations:
  *   F = lib/csrc/fps/src/farthest_point_sampling.cpp    M = lib/utils/vsd/misc.py:139-154 (calc_pts_diameter)
