@@ -251,7 +251,7 @@ class DetEvaluator:
             raise ValueError("det_eval: K must lie in [1, %d], got %d" % (MAX_K, K))
         ids = [int(v) for v in np.asarray(img_ids).ravel()]
         center = np.asarray(center, np.float32).reshape(-1, 2)
-        scale = np.asarray(scale, np.float32).reshape(len(center), -1)
+        scale = np.asarray(scale, np.float32).reshape(len(center), -1 if len(center) else 2)      # (an empty batch is a no-op below)
         if not (len(ids) == len(center) == B):
             raise ValueError("det_eval: %d images, %d ids, %d centres" % (B, len(ids), len(center)))
         images = self._gt["images"]

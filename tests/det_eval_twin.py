@@ -41,6 +41,15 @@ def round2(v):
         return n, n / 100.0
 
 
+def seeded_round2_values():
+    """100 000 doubles of both signs: uniform ones, the halves of the second decimal (as near to a tie as a double gets) and their
+    two neighbours.  The rounding is held to Python's on them, the twin's on the host and the device's on the GPU."""
+    rng = np.random.default_rng(5)
+    halves = (rng.integers(-200000, 200000, 30000) + 0.5) / 100.0
+    return np.concatenate([rng.uniform(-1000, 1000, 30000), rng.uniform(-1, 1, 10000), halves, np.nextafter(halves[:15000], np.inf),
+                           np.nextafter(halves[15000:], -np.inf)])
+
+
 def bad_value(v):
     with np.errstate(all="ignore"):
         return ~(np.abs(np.asarray(v, F64) * 100.0) < 4503599627370496.0)
@@ -361,7 +370,72 @@ def scenario_random(seed=7, B=8, K=40):
     return s
 
 
-SCENARIOS = {"det_eval_rules": scenario_rules, "det_eval_random": scenario_random}
+CATS30 = [47, 5, 86, 29, 71, 11, 62, 38, 2, 89, 53, 20, 74, 8, 35, 80, 17, 59, 26, 44, 68, 14, 83, 32, 56, 23, 77, 41, 65, 50]   # as T-LESS: 30
+IDENT = dict(hw=(128, 160), center=(80.0, 64.0), scale=(160.0, 160.0))        # with inp_hw (128, 160): raw = float32(x / 4) * 4
+WIDE = dict(hw=(540, 720), center=(355.5, 262.25), scale=(812.0, 812.0))
+
+
+def _image_margin(im, cat_ids, inp_hw):
+    """``tie_margin`` of one image's detections, mapped as ``_pack`` and ``map_rows`` map them."""
+    s = _pack({0: dict(im, gts=[])}, cat_ids, max(len(im["dets"]), 1), inp_hw, [0])
+    block = make_block(np.array([0]), [0], s["center"], s["scale"], inp_hw)
+    return tie_margin(map_rows(s["detection"], block, np.arange(len(cat_ids)))[1][:len(im["dets"])])
+
+
+def scenario_edges():
+    """Areas exactly on 32^2 and 96^2, in the ground truth (one by its ``area`` field alone) and in unmatched detections whose
+    rounded box is on the edge while the raw one is not; one cell of 64 ground truths with crowds at both ends of the mask under
+    100 detections; 30 categories of which the first, a middle one and the last are used.  The identity transform throughout."""
+    rng = np.random.default_rng(64)
+    inp_hw, by_id = (128, 160), sorted(CATS30)
+    first, mid, last = by_id[0], by_id[14], by_id[29]
+    images = {}
+    g17, d17 = _random_image(rng, [first, mid, last], 6, 20)
+    images[17] = dict(IDENT, gts=g17, dets=d17)
+    edge = [[4, 4, 32, 32], [44, 4, 16, 64], [64, 4, 96, 96], [4, 76, 40, 20], [4, 100, 10, 12]]
+    images[9] = dict(IDENT, gts=[(mid, b, 1024.0 if b[2:] == [40, 20] else None, 0) for b in edge],
+                     dets=[(mid, [200, 0, 232.004, 32], 0.95),             # rounds to 32.00 x 32: raw area above 32^2
+                           (mid, [200, 40, 231.996, 72], 0.9),             # rounds to 32.00 x 32: raw area below 32^2
+                           (mid, [200, 100, 296.004, 196], 0.85),          # rounds to 96.00 x 96: raw area above 96^2
+                           (mid, [320, 100, 415.996, 196], 0.8)]           # rounds to 96.00 x 96: raw area below 96^2
+                     + [(mid, [b[0], b[1], b[0] + b[2], b[1] + b[3]], 0.6 - 0.05 * j) for j, b in enumerate(edge)])
+    grid = []
+    for g in range(64):
+        bw, bh = (36, 36) if g == 63 else (38, 30) if g == 62 else (int(v) for v in rng.integers(18, 41, 2))
+        grid.append((first, [44 * (g % 8) + 2, 44 * (g // 8) + 2, bw, bh], None, int(g in (0, 17, 40, 63))))
+    dets = []
+    while len(dets) < 100:
+        _, (x, y, bw, bh), _, _ = grid[rng.integers(64)]
+        j = rng.normal(0, 0.08, 4) * [bw, bh, bw, bh]
+        d = (first, [x + j[0], y + j[1], x + bw + j[2], y + bh + j[3]], float(rng.uniform(0.03, 1.0)))
+        if _image_margin(dict(IDENT, dets=[d]), CATS30, inp_hw) > 1e-5:     # redrawn when a coordinate falls near a half
+            dets.append(d)
+    g3, d3 = _random_image(rng, [last], 2, 12, crowd_p=0.0)
+    images[3] = dict(IDENT, gts=grid[:40] + g3 + grid[40:], dets=dets[:70] + d3 + dets[70:])
+    images[25] = dict(IDENT, gts=[], dets=_random_image(rng, [last, first], 0, 7)[1])
+    images[30] = dict(IDENT, gts=[(last, [5, 5, 30, 30], None, 0)], dets=[])          # in gt, never passed
+    return _pack(images, CATS30, 128, inp_hw, [17, 3, 25, 9])
+
+
+def scenario_wide(seed=141, B=142, K=6):
+    """Many small images: the image rank of the key above its 7 low bits' reach, fed in an order that is not the ids', with scores
+    of one decimal so that the order of ties, across images and inside one, decides."""
+    rng = np.random.default_rng(seed)
+    inp_hw, by_id = (128, 160), sorted(CATS30)
+    pair = [by_id[11], by_id[29]]
+    images = {}
+    for i in rng.permutation(np.arange(500, 500 + 5 * B, 5)):
+        while True:
+            g, d = _random_image(rng, pair, int(rng.integers(2, 4)), int(rng.integers(2, 4)))
+            im = dict(WIDE, gts=g, dets=[(cat, box, float(rng.integers(2, 10)) / 10) for cat, box, _ in d])
+            if _image_margin(im, CATS30, inp_hw) > 1e-5:
+                break
+        images[int(i)] = im
+    return _pack(images, CATS30, K, inp_hw, [int(i) for i in rng.permutation(list(images))])
+
+
+SCENARIOS = {"det_eval_rules": scenario_rules, "det_eval_random": scenario_random, "det_eval_edges": scenario_edges,
+             "det_eval_wide": scenario_wide}
 
 
 def load_fixture(path):
