@@ -4,7 +4,8 @@ table).
 
 Every device entry point of these libraries takes the stream as its last argument and returns 0 on success: ``call`` is that
 convention, ``load`` binds a library with its signatures, ``need_cuda`` / ``workspace`` / ``ptr`` are what the wrappers
-share around a call.  torch is imported where it is used, so a host-pointer wrapper (``nn_utils``) loads without it.
+share around a call, ``call_named`` / ``check_images`` / ``u8`` / ``upload`` what the image modules (``augment``, ``ct_augment``,
+``tless_augment``, ``crop``) share in front of one.  torch is imported where it is used, so a host-pointer wrapper (``nn_utils``) loads without it.
 There is no CPU fallback anywhere behind this module.
 """
 import ctypes
@@ -41,6 +42,42 @@ def call(lib, symbol, dev, *args):
         rc = getattr(lib, symbol)(*args, torch.cuda.current_stream().cuda_stream)
     if rc != 0:
         raise RuntimeError("%s failed (%d)" % (symbol, rc))
+
+
+def call_named(module, lib, symbol, dev, *args):
+    """``call`` for a library that keeps its last error (``pvv_last_error``): a failure names ``clean_pvnet_amd.<module>`` and
+    says what the library recorded."""
+    try:
+        call(lib, symbol, dev, *args)
+    except RuntimeError as e:
+        raise RuntimeError("clean_pvnet_amd.%s: %s: %s" % (module, e, lib.pvv_last_error().decode())) from None
+
+
+def u8(t):
+    """``t`` contiguous, a bool tensor viewed as uint8."""
+    import torch
+    t = t.contiguous()
+    return t.view(torch.uint8) if t.dtype == torch.bool else t
+
+
+def upload(array, dev):
+    """The bytes of the host array as a device tensor: one pinned block, one non-blocking copy."""
+    import torch
+    import numpy as np
+    return torch.from_numpy(np.ascontiguousarray(array).view(np.uint8).reshape(-1)).pin_memory().to(dev, non_blocking=True)
+
+
+def check_images(img, what, module, max_batch=None, max_side=None):
+    """``img`` must be a [B,H,W,3] uint8 CUDA tensor, with limits: B in [1, max_batch] and the sides in [1, max_side]; returns
+    (B, H, W).  Without limits the caller checks them."""
+    import torch
+    need_cuda(img, what, module)
+    if img.dtype != torch.uint8 or img.dim() != 4 or img.shape[3] != 3:
+        raise TypeError("clean_pvnet_amd.%s: %s must be [B,H,W,3] uint8, got %s %s" % (module, what, tuple(img.shape), img.dtype))
+    B, H, W = (int(v) for v in img.shape[:3])
+    if max_batch is not None and not (1 <= B <= max_batch and 1 <= H <= max_side and 1 <= W <= max_side):
+        raise ValueError("clean_pvnet_amd.%s: B must lie in [1, %d] and the sides in [1, %d], got %s" % (module, max_batch, max_side, tuple(img.shape)))
+    return B, H, W
 
 
 def workspace(nbytes, dev):

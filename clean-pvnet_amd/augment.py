@@ -108,27 +108,8 @@ def jitter_params(d, blur_prob, jitter):
     return out
 
 
-def _upload(block, dev):
-    import torch
-    return torch.from_numpy(block.view(np.uint8).reshape(-1)).pin_memory().to(dev, non_blocking=True)
-
-
 def _call(symbol, dev, *args):
-    try:
-        _native.call(_lib, symbol, dev, *args)
-    except RuntimeError as e:
-        raise RuntimeError("clean_pvnet_amd.augment: %s: %s" % (e, _lib.pvv_last_error().decode())) from None
-
-
-def _check_img(img, what="img"):
-    import torch
-    _native.need_cuda(img, what, "augment")
-    if img.dtype != torch.uint8 or img.dim() != 4 or img.shape[3] != 3:
-        raise TypeError("clean_pvnet_amd.augment: %s must be [B,H,W,3] uint8, got %s %s" % (what, tuple(img.shape), img.dtype))
-    B, H, W = (int(v) for v in img.shape[:3])
-    if not (1 <= B <= MAX_BATCH and 1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
-        raise ValueError("clean_pvnet_amd.augment: B must lie in [1, %d] and the sides in [1, %d], got %s" % (MAX_BATCH, MAX_SIDE, tuple(img.shape)))
-    return B, H, W
+    _native.call_named("augment", _lib, symbol, dev, *args)
 
 
 def pvnet_augment(img, mask, kpt_2d, out_size, draws, *, rotate=(-30, 30), overlap_ratio=0.8, resize_ratio=(0.8, 1.2)):
@@ -142,7 +123,7 @@ def pvnet_augment(img, mask, kpt_2d, out_size, draws, *, rotate=(-30, 30), overl
              int32 (0 no foreground, 1 the instance branch, 2 the rotated mask came out empty: the steps of 0 on the
              unrotated image) and ``window`` [B,6] int32 (th, tw, hbeg, wbeg, pad_h, pad_w)."""
     import torch
-    B, H, W = _check_img(img)
+    B, H, W = _native.check_images(img, "img", "augment", MAX_BATCH, MAX_SIDE)
     _native.need_cuda(mask, "mask", "augment")
     _native.need_cuda(kpt_2d, "kpt_2d", "augment")
     if mask.dtype not in (torch.uint8, torch.bool):
@@ -164,13 +145,12 @@ def pvnet_augment(img, mask, kpt_2d, out_size, draws, *, rotate=(-30, 30), overl
     dev = img.device
     K = int(kpt_2d.shape[1])
     im, kp = img.contiguous(), kpt_2d.detach().contiguous()
-    m = mask.contiguous()
-    m = m.view(torch.uint8) if m.dtype == torch.bool else m
+    m = _native.u8(mask)
     out = {"img": torch.empty(B, height, width, 3, dtype=torch.uint8, device=dev),
            "mask": torch.empty(B, height, width, dtype=torch.uint8, device=dev),
            "kpt_2d": torch.empty(B, K, 2, dtype=torch.float64, device=dev),
            "path": torch.empty(B, dtype=torch.int32, device=dev), "window": torch.empty(B, 6, dtype=torch.int32, device=dev)}
-    prm = _upload(block, dev)
+    prm = _native.upload(block, dev)
     mth, mtw = int(block["th"].max()), int(block["tw"].max())                    # the rotated windows lie in the workspace
     nbytes = _lib.pvv_augment_workspace_bytes(B, mth, mtw)
     ws = _native.workspace(nbytes, dev)
@@ -191,7 +171,7 @@ def pvnet_transform(img, draws, *, blur_prob=0.5, jitter=(0.1, 0.1, 0.05, 0.05),
     :param mean, std:  3 floats each, taken as binary64
     :return:           [B,3,h,w] float32"""
     import torch
-    B, h, w = _check_img(img)
+    B, h, w = _native.check_images(img, "img", "augment", MAX_BATCH, MAX_SIDE)
     mean_c, std_c = (ctypes.c_double * 3)(*[float(v) for v in mean]), (ctypes.c_double * 3)(*[float(v) for v in std])
     dev = img.device
     prm, ws, has_blur, has_contrast = None, None, 0, 0
@@ -205,7 +185,7 @@ def pvnet_transform(img, draws, *, blur_prob=0.5, jitter=(0.1, 0.1, 0.05, 0.05),
             raise ValueError("clean_pvnet_amd.augment: the image's sides must be at least %d, got %d x %d" % (MIN_SIDE, h, w))
         block = jitter_params(_check_draws(draws, B), float(blur_prob), jitter)
         has_blur, has_contrast = int((block["k"] > 0).any()), int((block["order"] == 1).any())
-        prm = _upload(block, dev)
+        prm = _native.upload(block, dev)
         ws = _native.workspace(_lib.pvv_transform_workspace_bytes(B, h, w), dev)
     im = img.contiguous()
     out = torch.empty(B, 3, h, w, dtype=torch.float32, device=dev)

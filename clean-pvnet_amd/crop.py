@@ -136,12 +136,9 @@ def uncrop_mask(mask, trans, canvas_size):
     import torch
     _native.need_cuda(mask, "mask", "crop")
     _native.need_cuda(trans, "trans", "crop")
-    if mask.dtype == torch.bool:
-        m = mask.contiguous().view(torch.uint8)
-    elif mask.dtype in (torch.uint8, torch.int64):
-        m = mask.contiguous()
-    else:
+    if mask.dtype not in (torch.uint8, torch.bool, torch.int64):
         raise TypeError("crop: mask has dtype %s, supported are uint8, bool and int64" % mask.dtype)
+    m = _native.u8(mask)
     Wc, Hc = (int(v) for v in canvas_size)
     N, h, w = m.shape
     assert tuple(trans.shape) == (N, 2, 3) and trans.dtype == torch.float64, (trans.shape, trans.dtype)

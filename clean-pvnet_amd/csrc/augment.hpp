@@ -1,8 +1,9 @@
 // augment.hpp -- PVNet's training augmentation and loader transforms for a batch (include/pvnet_vote.h, "Training augmentation").
-// Included at the end of pvnet_vote.hip: built with -ffp-contract=off, every float and double operation below rounds once, in
-// the order written, so that the numpy twin (tests/augment_twin.py) gives the same bits.  sat_rint, invert_affine and the two
-// fixed-point warp rules are those of crop.hpp.  No random numbers and no transcendental function are
-// evaluated here: the host hands over the drawn values, cos and sin included.  Every reduction is over integers.
+// Part of pvnet_vote.hip: built with -ffp-contract=off, every float and double operation below rounds once, in the order
+// written, so that the numpy twin (tests/augment_twin.py) gives the same bits.  sat_rint, invert_affine, the two fixed-point
+// warp rules and the box accumulator are those of warp.hpp, the wave reductions those of
+// vote_common.hpp.  No random numbers and no transcendental function are evaluated here: the host hands over the drawn values,
+// cos and sin included.  Every reduction is over integers.
 //
 // Reference behaviour restated:
 //   P = lib/datasets/linemod/pvnet.py:62-78 (augment)        A = lib/datasets/augmentation.py (rotate_instance :60-69,
@@ -10,10 +11,11 @@
 //   X = lib/datasets/transforms.py:29-99 (ToTensor, Normalize, ColorJitter, RandomBlur, make_transforms)
 #pragma once
 
+#include "warp.hpp"
+
 namespace {
 
 constexpr int kAugMaxSide = 16384;
-constexpr int kAugBig = 1 << 30;
 constexpr int kBlurTile = 16;                     // rows of a blur tile; it is 64 wide
 constexpr int kBlurHalo = 4;                      // the 9-tap table reaches 4 pixels
 
@@ -26,7 +28,7 @@ static_assert(sizeof(AugDraw) == PVV_AUGMENT_PARAM_BYTES, "pvnet_vote.h promises
 
 struct AugState {                 // per sample, in the workspace; zeroed before the first launch
     unsigned long long n, sx, sy; // the foreground's moments
-    int32_t nxmin, xmax1, nymin, ymax1;   // the rotated mask's box as kAugBig - min and max + 1: 0 means no pixel
+    Extent box;                   // the rotated mask's box
     double M[6], inv[6];          // image -> rotated image, and its inverse
     int32_t path, th, tw, hbeg, wbeg, pad_h, pad_w, pad_;
 };
@@ -42,30 +44,12 @@ static_assert(sizeof(AugJitter) == PVV_TRANSFORM_PARAM_BYTES, "pvnet_vote.h prom
 
 struct AugNorm { double mean[3], std[3]; };
 
-__device__ int aug_wave_sum(int v)
-{
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_down(v, s, 64);
-    return v;
-}
-__device__ int aug_wave_max(int v)
-{
-    for (int s = 32; s > 0; s >>= 1) v = max(v, __shfl_down(v, s, 64));
-    return v;
-}
-
 // cv2.getRotationMatrix2D((cx, cy), degree, 1) around the foreground's centre (A:63-64).
 __device__ void aug_matrix(const AugState *s, double a, double b, double *M)
 {
     const double cx = (double)s->sx / (double)s->n, cy = (double)s->sy / (double)s->n;
     M[0] = a, M[1] = b, M[2] = (1. - a) * cx - b * cy;
     M[3] = -b, M[4] = a, M[5] = b * cx + (1. - a) * cy;
-}
-
-// The source pixel of the nearest-neighbour warp for destination (x, y): the rule of k_uncrop_mask.
-__device__ void aug_nearest(const double *I, int x, int y, long long *X, long long *Y)
-{
-    const long long XR = sat_rint((I[1] * y + I[2]) * 1024.) + 512, YR = sat_rint((I[4] * y + I[5]) * 1024.) + 512;
-    *X = (XR + sat_rint(I[0] * x * 1024.)) >> 10, *Y = (YR + sat_rint(I[3] * x * 1024.)) >> 10;
 }
 
 // Launch 1, 8 pixels of the flattened mask per lane: n, sum x, sum y over mask != 0 (A:63).
@@ -82,7 +66,7 @@ __global__ __launch_bounds__(kBlock) void k_aug_moments(const uint8_t *__restric
             n += 1, sx += (int)(i - (long long)y * W), sy += y;
         }
     }
-    n = aug_wave_sum(n), sx = aug_wave_sum(sx), sy = aug_wave_sum(sy);
+    n = wave_sum(n), sx = wave_sum(sx), sy = wave_sum(sy);
     if ((threadIdx.x & 63) == 0 && n) {
         atomicAdd(&st[b].n, (unsigned long long)n);
         atomicAdd(&st[b].sx, (unsigned long long)sx);
@@ -100,27 +84,9 @@ __global__ __launch_bounds__(kBlock) void k_aug_box(const uint8_t *__restrict__ 
     double M[6], I[6];
     aug_matrix(s, dr[b].cs, dr[b].sn, M);
     invert_affine(M, I);
-    bool hit = false;
-    if (x < W && y < H) {
-        long long X, Y;
-        aug_nearest(I, x, y, &X, &Y);
-        hit = X >= 0 && X < W && Y >= 0 && Y < H && mask[((size_t)b * H + (size_t)Y) * W + (size_t)X] != 0;
-    }
-    const int nx = aug_wave_max(hit ? kAugBig - x : 0), x1 = aug_wave_max(hit ? x + 1 : 0);
-    if (threadIdx.x == 0 && x1) {                                           // (a wave is one row: y is the same for its lanes)
-        atomicMax(&s->nxmin, nx);
-        atomicMax(&s->xmax1, x1);
-        atomicMax(&s->nymin, kAugBig - y);
-        atomicMax(&s->ymax1, y + 1);
-    }
-}
-
-// lo + floor(u * (hi - lo)) for hi > lo, lo otherwise (where np.random.randint raises)
-__device__ int aug_randint(int lo, int hi, double u)
-{
-    if (hi <= lo) return lo;
-    const long long k = (long long)floor(u * (double)(hi - lo));
-    return lo + (int)min(k, (long long)(hi - lo) - 1);
+    int v = 0;
+    if (x < W && y < H) sample_nearest<1>(mask + (size_t)b * H * W, H, W, I, x, y, &v);
+    s->box.note(v != 0, x, y);
 }
 
 // Launch 3, one block per sample: the branch (P:68), the window (A:126-144, 157-158 or A:170-176, 188-189) and the keypoints
@@ -133,7 +99,7 @@ __global__ __launch_bounds__(64) void k_aug_window(AugState *__restrict__ st, co
     const int b = blockIdx.x;
     AugState *s = st + b;
     const AugDraw d = dr[b];
-    const int path = s->n == 0 ? 0 : s->xmax1 == 0 ? 2 : 1;
+    const int path = s->n == 0 ? 0 : s->box.empty() ? 2 : 1;
     const int th = path == 1 ? d.th : oh, tw = path == 1 ? d.tw : ow;
     const bool hpad = th >= H, wpad = tw >= W;
     int hlo = 0, hhi = H - th, wlo = 0, whi = W - tw;
@@ -141,13 +107,15 @@ __global__ __launch_bounds__(64) void k_aug_window(AugState *__restrict__ st, co
     if (path == 1) {
         aug_matrix(s, d.cs, d.sn, M);
         invert_affine(M, I);
-        const int hmin = kAugBig - s->nymin, hmax = s->ymax1 - 1, wmin = kAugBig - s->nxmin, wmax = s->xmax1 - 1;
+        int box[4];
+        s->box.decode(box);
+        const int wmin = box[0], hmin = box[1], wmax = box[2], hmax = box[3];
         const double vh = (double)hmin + overlap * (double)(hmax - hmin), vw = (double)wmin + overlap * (double)(wmax - wmin);
         const double h_th = (double)(H - th), w_tw = (double)(W - tw), hl = vh - (double)th, wl = vw - (double)tw;
         hhi = (int)(vh < h_th ? vh : h_th), hlo = (int)(hl > 0. ? hl : 0.);
         whi = (int)(vw < w_tw ? vw : w_tw), wlo = (int)(wl > 0. ? wl : 0.);
     }
-    const int hbeg = hpad ? 0 : aug_randint(hlo, hhi, d.u_h), wbeg = wpad ? 0 : aug_randint(wlo, whi, d.u_w);
+    const int hbeg = hpad ? 0 : uniform_randint(hlo, hhi, d.u_h), wbeg = wpad ? 0 : uniform_randint(wlo, whi, d.u_w);
     const int pad_h = hpad ? (th - H) / 2 : 0, pad_w = wpad ? (tw - W) / 2 : 0;
     if (threadIdx.x == 0) {
         for (int i = 0; i < 6; ++i) s->M[i] = M[i], s->inv[i] = I[i];
@@ -169,28 +137,6 @@ __global__ __launch_bounds__(64) void k_aug_window(AugState *__restrict__ st, co
     }
 }
 
-// The rotated image at the integer position (x, y): 0 outside the image (the window's padding), inside it the 8-bit bilinear
-// warp of k_crop_warp.  Every tap is tested before its address is formed.
-__device__ void aug_rotated_pixel(const uint8_t *__restrict__ base, int H, int W, const double *I, long long x, long long y, int *v)
-{
-    v[0] = v[1] = v[2] = 0;
-    if (x < 0 || x >= W || y < 0 || y >= H) return;
-    const long long X0 = sat_rint((I[1] * (int)y + I[2]) * 1024.) + 16, Y0 = sat_rint((I[4] * (int)y + I[5]) * 1024.) + 16;
-    const long long X = (X0 + sat_rint(I[0] * (int)x * 1024.)) >> 5, Y = (Y0 + sat_rint(I[3] * (int)x * 1024.)) >> 5;
-    const long long sx = X >> 5, sy = Y >> 5;
-    const int a = (int)(X & 31), b = (int)(Y & 31);
-    const int w00 = (32 - a) * (32 - b) * 32, w01 = a * (32 - b) * 32, w10 = (32 - a) * b * 32, w11 = a * b * 32;
-    const bool in_x0 = sx >= 0 && sx < W, in_x1 = sx + 1 >= 0 && sx + 1 < W, in_y0 = sy >= 0 && sy < H, in_y1 = sy + 1 >= 0 && sy + 1 < H;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const int p00 = in_y0 && in_x0 ? base[((size_t)sy * W + sx) * 3 + c] : 0;
-        const int p01 = in_y0 && in_x1 ? base[((size_t)sy * W + sx + 1) * 3 + c] : 0;
-        const int p10 = in_y1 && in_x0 ? base[((size_t)(sy + 1) * W + sx) * 3 + c] : 0;
-        const int p11 = in_y1 && in_x1 ? base[((size_t)(sy + 1) * W + sx + 1) * 3 + c] : 0;
-        v[c] = (p00 * w00 + p01 * w01 + p10 * w10 + p11 * w11 + 16384) >> 15;
-    }
-}
-
 // The two taps of the 8-bit bilinear resize along one axis: `src` pixels onto `dst`, destination index d.
 __device__ void aug_resize_taps(int d, int src, int dst, int *s0, int *s1, int *w0, int *w1)
 {
@@ -205,8 +151,8 @@ __device__ void aug_resize_taps(int d, int src, int dst, int *s0, int *s1, int *
     *w0 = (int)rintf((1.f - f) * 2048.f), *w1 = (int)rintf(f * 2048.f);
 }
 
-// Launch 4, one lane per pixel of the th x tw window, 64 along a row: the rotated image inside the zero-padded window (A:66,
-// 146-165) to win [B,TH,TW,3] in the workspace; samples on paths 0 and 2 write nothing.  (Recomputing the four rotated pixels
+// Launch 4, one lane per pixel of the th x tw window, 64 along a row: the rotated image (the 8-bit bilinear warp) inside the
+// zero-padded window (A:66, 146-165) to win [B,TH,TW,3] in the workspace; samples on paths 0 and 2 write nothing.  (Recomputing the four rotated pixels
 // per resize tap instead, without this image, gives the same bytes and measured 1.5 x slower at 32 x 480 x 640.)
 __global__ __launch_bounds__(kBlock) void k_aug_rotate(const uint8_t *__restrict__ img, int H, int W, const AugState *__restrict__ st, int TH,
                                                        int TW, uint8_t *__restrict__ win)
@@ -214,8 +160,9 @@ __global__ __launch_bounds__(kBlock) void k_aug_rotate(const uint8_t *__restrict
     const int wx = blockIdx.x * 64 + threadIdx.x, wy = blockIdx.y * 4 + threadIdx.y, b = blockIdx.z;
     const AugState *s = st + b;
     if (s->path != 1 || wx >= s->tw || wy >= s->th || wx >= TW || wy >= TH) return;
-    int v[3];
-    aug_rotated_pixel(img + (size_t)b * H * W * 3, H, W, s->inv, (long long)wx + (s->wbeg - s->pad_w), (long long)wy + (s->hbeg - s->pad_h), v);
+    const long long x = (long long)wx + (s->wbeg - s->pad_w), y = (long long)wy + (s->hbeg - s->pad_h);      // window -> image
+    int v[3] = {0, 0, 0};
+    if (x >= 0 && x < W && y >= 0 && y < H) sample_linear<3>(img + (size_t)b * H * W * 3, H, W, s->inv, (int)x, (int)y, v);
     uint8_t *o = win + (((size_t)b * TH + wy) * TW + wx) * 3;
 #pragma unroll
     for (int c = 0; c < 3; ++c) o[c] = (uint8_t)v[c];
@@ -260,11 +207,7 @@ __global__ __launch_bounds__(kBlock) void k_aug_render(const uint8_t *__restrict
         const long long wx = min((long long)floor((double)dx * ((double)s->tw / (double)ow)), (long long)s->tw - 1);
         const long long wy = min((long long)floor((double)dy * ((double)s->th / (double)oh)), (long long)s->th - 1);
         const long long rx = wx + ox, ry = wy + oy;
-        if (rx >= 0 && rx < W && ry >= 0 && ry < H) {
-            long long X, Y;
-            aug_nearest(s->inv, (int)rx, (int)ry, &X, &Y);
-            if (X >= 0 && X < W && Y >= 0 && Y < H) mv = m[(size_t)Y * W + (size_t)X];
-        }
+        if (rx >= 0 && rx < W && ry >= 0 && ry < H) sample_nearest<1>(m, H, W, s->inv, (int)rx, (int)ry, &mv);
     } else {
         const long long x = (long long)dx + ox, y = (long long)dy + oy;
         if (x >= 0 && x < W && y >= 0 && y < H) {
@@ -421,7 +364,7 @@ __global__ __launch_bounds__(kBlock) void k_aug_luma_sum(const uint8_t *__restri
             if (j->order[i] >= 0) aug_enhance(j->order[i], j, 0, v);
         sum += aug_luma(v);
     }
-    sum = aug_wave_sum(sum);
+    sum = wave_sum(sum);
     if (threadIdx.x == 0 && sum) atomicAdd(&sums[b], (unsigned long long)sum);
 }
 
@@ -456,8 +399,6 @@ int aug_check(int B, int H, int W)
     return PVV_OK;
 }
 
-size_t aug_up(size_t n) { return (n + 255) & ~(size_t)255; }
-
 }  // namespace
 
 PVV_EXPORT size_t pvv_augment_workspace_bytes(int B, int max_th, int max_tw)
@@ -467,7 +408,7 @@ PVV_EXPORT size_t pvv_augment_workspace_bytes(int B, int max_th, int max_tw)
         fail(PVV_E_ARG, "augment: max_th and max_tw must lie in [1, 16384]");
         return 0;
     }
-    return aug_up(sizeof(AugState) * (size_t)B) + aug_up((size_t)B * max_th * max_tw * 3);
+    return align_up(sizeof(AugState) * (size_t)B) + align_up((size_t)B * max_th * max_tw * 3);
 }
 
 PVV_EXPORT int pvv_pvnet_augment(const uint8_t *d_img, const uint8_t *d_mask, const void *d_kpt_2d, int kpt_is_f64, int B, int H, int W,
@@ -500,7 +441,7 @@ PVV_EXPORT int pvv_pvnet_augment(const uint8_t *d_img, const uint8_t *d_mask, co
         hipLaunchKernelGGL(k_aug_window<float>, dim3(B), dim3(64), 0, st, state, dr, (const float *)d_kpt_2d, K, H, W, oh, ow, overlap_ratio,
                            d_out_kpt, d_path, d_window);
     if (int e = check_launch("k_aug_window")) return e;
-    uint8_t *win = (uint8_t *)d_workspace + aug_up(sizeof(AugState) * (size_t)B);
+    uint8_t *win = (uint8_t *)d_workspace + align_up(sizeof(AugState) * (size_t)B);
     hipLaunchKernelGGL(k_aug_rotate, dim3((max_tw + 63) / 64, (max_th + 3) / 4, B), dim3(64, 4), 0, st, d_img, H, W, state, max_th, max_tw, win);
     if (int e = check_launch("k_aug_rotate")) return e;
     hipLaunchKernelGGL(k_aug_render, dim3((ow + 63) / 64, (oh + 3) / 4, B), dim3(64, 4), 0, st, d_img, d_mask, H, W, state, oh, ow, win, max_th,
@@ -511,7 +452,7 @@ PVV_EXPORT int pvv_pvnet_augment(const uint8_t *d_img, const uint8_t *d_mask, co
 PVV_EXPORT size_t pvv_transform_workspace_bytes(int B, int h, int w)
 {
     if (aug_check(B, h, w)) return 0;
-    return aug_up(sizeof(unsigned long long) * (size_t)B) + aug_up((size_t)B * h * w * 3);
+    return align_up(sizeof(unsigned long long) * (size_t)B) + align_up((size_t)B * h * w * 3);
 }
 
 PVV_EXPORT int pvv_pvnet_transform(const uint8_t *d_img, int B, int h, int w, const void *d_params, int has_blur, int has_contrast,
@@ -531,7 +472,7 @@ PVV_EXPORT int pvv_pvnet_transform(const uint8_t *d_img, int B, int h, int w, co
     unsigned long long *sums = (unsigned long long *)d_workspace;
     const uint8_t *src = d_img;
     if (prm && has_blur) {
-        uint8_t *blurred = (uint8_t *)d_workspace + aug_up(sizeof(unsigned long long) * (size_t)B);
+        uint8_t *blurred = (uint8_t *)d_workspace + align_up(sizeof(unsigned long long) * (size_t)B);
         hipLaunchKernelGGL(k_aug_blur, dim3((w + 63) / 64, (h + kBlurTile - 1) / kBlurTile, B), dim3(64, 4), 0, st, d_img, h, w, prm, blurred);
         if (int e = check_launch("k_aug_blur")) return e;
         src = blurred;

@@ -1,11 +1,14 @@
 // crop.hpp -- detector heat maps -> boxes, boxes -> PVNet crops, and crop results -> canvas (include/pvnet_vote.h, "Detector
-// decode, crops and the way back").  Included at the end of pvnet_vote.hip: built with -ffp-contract=off, every float and
-// double operation below rounds once, in the order written, so that the numpy twin (tests/crop_twin.py) gives the same bits.
+// decode, crops and the way back").  Part of pvnet_vote.hip: built with -ffp-contract=off, every float and double operation
+// below rounds once, in the order written, so that the numpy twin (tests/crop_twin.py) gives the same bits.  sat_rint,
+// invert_affine, the two fixed-point warp rules, the crop's map and the rectangle of magnify_box are those of warp.hpp.
 //
 // Reference behaviour restated (paths relative to /root/reference):
 //   D = lib/utils/ct/ct_decode.py        U = lib/utils/data_utils.py       R = lib/networks/ct_pvnet/res.py
 //   T = lib/utils/tless/tless_test_utils.py                                E = lib/evaluators/tless_test/pvnet.py
 #pragma once
+
+#include "warp.hpp"
 
 namespace {
 
@@ -159,27 +162,8 @@ static_assert(sizeof(CropBox) == PVV_CROP_WORKSPACE_PER_BOX, "pvnet_vote.h promi
 
 struct CropNorm { float mean[3], std[3]; };
 
-// rint (half to even), saturated to int32; a NaN becomes INT32_MIN
-__device__ long long sat_rint(double v)
-{
-    const double r = rint(v);
-    if (!(r > -2147483648.0)) return -2147483648ll;
-    if (r >= 2147483647.0) return 2147483647ll;
-    return (long long)r;
-}
-
-// The inverse of a 2 x 3 affine map in the operation order of OpenCV's invertAffineTransform; a singular map gives zeros.
-__device__ void invert_affine(const double *M, double *I)
-{
-    double D = M[0] * M[4] - M[1] * M[3];
-    D = D != 0. ? 1. / D : 0.;
-    const double A11 = M[4] * D, A22 = M[0] * D, m1 = M[1] * (-D), m3 = M[3] * (-D);
-    const double b1 = -A11 * M[2] - m1 * M[5], b2 = -m3 * M[2] - A22 * M[5];
-    I[0] = A11, I[1] = m1, I[2] = b1, I[3] = m3, I[4] = A22, I[5] = b2;
-}
-
-// One thread per box: centre and scale (R:16-17, T:58-59), the closed form of get_affine_transform(center, scale, 0, [ow, oh])
-// (U:123-156), its inverse, and the rectangle of magnify_box (T:49-54, 65-67).
+// One thread per box: centre and scale (R:16-17, T:58-59), rounded to float32 as the reference keeps them, the crop's map, its
+// inverse, and the rectangle of magnify_box (T:65-67).
 __global__ void k_crop_prep(const double *__restrict__ boxes, const int32_t *__restrict__ image_index, int N, int B, int ow, int oh,
                             double scale_ratio, int has_box_ratio, double box_ratio, float *__restrict__ center,
                             float *__restrict__ scale, double *__restrict__ trans, uint8_t *__restrict__ valid, CropBox *__restrict__ prm)
@@ -194,29 +178,22 @@ __global__ void k_crop_prep(const double *__restrict__ boxes, const int32_t *__r
     const bool ok = isfinite(x0) && isfinite(y0) && isfinite(x1) && isfinite(y1) && isfinite(cxf) && isfinite(cyf) && isfinite(sf) &&
                     sf > 0.f && img >= 0 && img < B;
     CropBox p;
-    p.rx0 = p.ry0 = 0, p.rx1 = ow - 1, p.ry1 = oh - 1, p.valid = ok, p.img = ok ? img : 0;
+    p.valid = ok, p.img = ok ? img : 0;
     for (int i = 0; i < 6; ++i) p.inv[i] = 0., p.pad_[i] = 0;
     double M[6] = {0., 0., 0., 0., 0., 0.};
+    int32_t r[4] = {0, 0, ow - 1, oh - 1};
     if (ok) {
-        const double a = (double)ow / (double)sf;
-        M[0] = a, M[2] = ow * 0.5 - a * (double)cxf, M[4] = a, M[5] = oh * 0.5 - a * (double)cyf;
+        crop_transform((double)cxf, (double)cyf, (double)sf, ow, oh, M);
         invert_affine(M, p.inv);
-        if (has_box_ratio) {
-            const double px0 = x0 * a + M[2], py0 = y0 * a + M[5], px1 = x1 * a + M[2], py1 = y1 * a + M[5];
-            const double mx = (px0 + px1) / 2., my = (py0 + py1) / 2.;
-            const long long c[4] = {sat_rint((px0 - mx) * box_ratio + mx), sat_rint((py0 - my) * box_ratio + my),
-                                    sat_rint((px1 - mx) * box_ratio + mx), sat_rint((py1 - my) * box_ratio + my)};
-            p.rx0 = (int)min(max(c[0], 0ll), (long long)ow - 1), p.ry0 = (int)min(max(c[1], 0ll), (long long)oh - 1);
-            p.rx1 = (int)min(max(c[2], 0ll), (long long)ow - 1), p.ry1 = (int)min(max(c[3], 0ll), (long long)oh - 1);
-        }
+        if (has_box_ratio) magnify_rect(M, x0, y0, x1, y1, box_ratio, ow, oh, r);
     }
+    p.rx0 = r[0], p.ry0 = r[1], p.rx1 = r[2], p.ry1 = r[3];
     center[2 * n] = ok ? cxf : 0.f, center[2 * n + 1] = ok ? cyf : 0.f, scale[n] = ok ? sf : 0.f, valid[n] = ok;
     for (int i = 0; i < 6; ++i) trans[6 * n + i] = M[i];
     prm[n] = p;
 }
 
-// One thread per crop pixel, 64 along a row: the 8-bit bilinear warp in fixed point (10 fractional bits for the coordinates, 5
-// of them kept as the weights; constant border 0), the blanking, the normalisation of R:25-27, planar stores.
+// One thread per crop pixel, 64 along a row: the 8-bit bilinear warp, the blanking, the normalisation of R:25-27, planar stores.
 __global__ __launch_bounds__(kBlock) void k_crop_warp(const uint8_t *__restrict__ img, int H, int W, const CropBox *__restrict__ prm,
                                                       int ow, int oh, CropNorm nm, float *__restrict__ out)
 {
@@ -224,23 +201,8 @@ __global__ __launch_bounds__(kBlock) void k_crop_warp(const uint8_t *__restrict_
     if (x >= ow || y >= oh) return;
     const CropBox *p = prm + n;
     int v[3] = {0, 0, 0};
-    if (p->valid && x >= p->rx0 && x <= p->rx1 && y >= p->ry0 && y <= p->ry1) {
-        const long long X0 = sat_rint((p->inv[1] * y + p->inv[2]) * 1024.) + 16, Y0 = sat_rint((p->inv[4] * y + p->inv[5]) * 1024.) + 16;
-        const long long X = (X0 + sat_rint(p->inv[0] * x * 1024.)) >> 5, Y = (Y0 + sat_rint(p->inv[3] * x * 1024.)) >> 5;
-        const long long sx = X >> 5, sy = Y >> 5;
-        const int a = (int)(X & 31), b = (int)(Y & 31);
-        const int w00 = (32 - a) * (32 - b) * 32, w01 = a * (32 - b) * 32, w10 = (32 - a) * b * 32, w11 = a * b * 32;
-        const uint8_t *base = img + (size_t)p->img * H * W * 3;
-        const bool in_x0 = sx >= 0 && sx < W, in_x1 = sx + 1 >= 0 && sx + 1 < W, in_y0 = sy >= 0 && sy < H, in_y1 = sy + 1 >= 0 && sy + 1 < H;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int p00 = in_y0 && in_x0 ? base[((size_t)sy * W + sx) * 3 + c] : 0;
-            const int p01 = in_y0 && in_x1 ? base[((size_t)sy * W + sx + 1) * 3 + c] : 0;
-            const int p10 = in_y1 && in_x0 ? base[((size_t)(sy + 1) * W + sx) * 3 + c] : 0;
-            const int p11 = in_y1 && in_x1 ? base[((size_t)(sy + 1) * W + sx + 1) * 3 + c] : 0;
-            v[c] = (p00 * w00 + p01 * w01 + p10 * w10 + p11 * w11 + 16384) >> 15;
-        }
-    }
+    if (p->valid && x >= p->rx0 && x <= p->rx1 && y >= p->ry0 && y <= p->ry1)
+        sample_linear<3>(img + (size_t)p->img * H * W * 3, H, W, p->inv, x, y, v);
 #pragma unroll
     for (int c = 0; c < 3; ++c)
         out[(((size_t)n * 3 + c) * oh + y) * ow + x] = ((float)v[c] / 255.f - nm.mean[c]) / nm.std[c];
@@ -259,7 +221,7 @@ __global__ void k_uncrop_kpt(const T *__restrict__ kpt, const double *__restrict
     out[2 * (size_t)i + 1] = I[3] * x + I[4] * y + I[5];
 }
 
-// One thread per 4 canvas pixels of a row: E:243-245, nearest neighbour in fixed point with `trans` as the canvas -> crop map.
+// One thread per 4 canvas pixels of a row: E:243-245, the nearest rule with `trans` as the canvas -> crop map, its row half once.
 // `vec` (Wc a multiple of 4) stores the four bytes as one word.
 __global__ __launch_bounds__(kBlock) void k_uncrop_mask(const uint8_t *__restrict__ mask, int elem, int h, int w,
                                                         const double *__restrict__ trans, int Hc, int Wc, int vec, uint8_t *__restrict__ out)
@@ -267,13 +229,15 @@ __global__ __launch_bounds__(kBlock) void k_uncrop_mask(const uint8_t *__restric
     const int x4 = (blockIdx.x * kBlock + threadIdx.x) * 4, y = blockIdx.y, n = blockIdx.z;
     if (x4 >= Wc) return;
     const double *T = trans + 6 * (size_t)n;
-    const long long XR = sat_rint((T[1] * y + T[2]) * 1024.) + 512, YR = sat_rint((T[4] * y + T[5]) * 1024.) + 512;
+    long long XR, YR;
+    warp_nearest_row(T, y, &XR, &YR);
     const uint8_t *m = mask + (size_t)n * h * w * elem;
     uint8_t r[4] = {0, 0, 0, 0};
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int x = x4 + i;
-        const long long X = (XR + sat_rint(T[0] * x * 1024.)) >> 10, Y = (YR + sat_rint(T[3] * x * 1024.)) >> 10;
+        long long X, Y;
+        warp_nearest_col(T, x, XR, YR, &X, &Y);
         if (x < Wc && X >= 0 && X < w && Y >= 0 && Y < h) r[i] = m[((size_t)Y * w + X) * elem];     // (little endian: the low byte)
     }
     uint8_t *o = out + ((size_t)n * Hc + y) * Wc + x4;

@@ -1,16 +1,20 @@
 // ct_augment.hpp -- the detector's training batch from cut-outs and a background, and its input preparation (include/pvnet_vote.h,
-// "Detector augmentation").  Included at the end of pvnet_vote.hip after augment.hpp: built with -ffp-contract=off, every float
-// and double operation below rounds once, in the order written, so that the numpy twin (tests/ct_augment_twin.py) gives the
-// same bits.  sat_rint and the two fixed-point warp rules are those of crop.hpp, aug_randint and the wave
-// reductions those of augment.hpp.  No random numbers and no transcendental function are evaluated here: the host hands over
-// the inverse maps, the rounded alphas and the lighting vector.  The grey mean is the only floating-point sum: binary64, per
-// 64 x 4 tile in the tree of train.hpp, then per image in the same tree over slots; every other reduction is over integers.
+// "Detector augmentation").  Part of pvnet_vote.hip: built with -ffp-contract=off, every float and double operation below rounds
+// once, in the order written, so that the numpy twin (tests/ct_augment_twin.py) gives the same bits.  The two fixed-point warp
+// rules, the box accumulator, the placement record and its coverage test are those of warp.hpp, the wave
+// reductions and the block tree those of vote_common.hpp, TrainVec4 that of train.hpp.  No random numbers and no
+// transcendental function are evaluated here: the host hands over the inverse maps, the rounded alphas and the lighting
+// vector.  The grey mean is the only floating-point sum: binary64, per 64 x 4 tile in the block tree, then per image in the
+// same tree over slots; every other reduction is over integers.
 //
 // Reference behaviour restated:
 //   U = lib/utils/tless/tless_utils.py (augment :18-63, cut_and_paste :86-97)
 //   C = lib/datasets/tless/ct.py:58-70 (Dataset.get_bbox)      C' = lib/datasets/tless_train/ct.py:75-76
 //   G = lib/utils/data_utils.py (grayscale :172-173, lighting_ .. contrast_ :176-199, color_aug :202-210)
 #pragma once
+
+#include "train.hpp"
+#include "warp.hpp"
 
 namespace {
 
@@ -31,7 +35,7 @@ struct CtaNorm { float mean[3], std[3]; };
 __device__ void cta_block_max4(int *v, int (*sh)[4])
 {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = aug_wave_max(v[k]);
+    for (int k = 0; k < 4; ++k) v[k] = wave_max(v[k]);
     if ((threadIdx.x & 63) == 0)
         for (int k = 0; k < 4; ++k) sh[threadIdx.x >> 6][k] = v[k];
     __syncthreads();
@@ -48,8 +52,7 @@ __global__ __launch_bounds__(kBlock) void k_cta_place(const uint8_t *__restrict_
     __shared__ int s_r[4][4];
     const int n = blockIdx.x, b = blockIdx.y;
     const size_t inst = (size_t)b * N + n;
-    int32_t *out = place + 6 * inst;
-    int v[4] = {0, 0, 0, 0};                              // kAugBig - x_min, x_max + 1, kAugBig - y_min, y_max + 1: 0 means no pixel
+    Extent e = {{0, 0, 0, 0}};
     if (n < num[b]) {
         const size_t hw = (size_t)h * w;
         const uint8_t *m = mask + inst * hw;
@@ -62,27 +65,20 @@ __global__ __launch_bounds__(kBlock) void k_cta_place(const uint8_t *__restrict_
                 for (int j = 0; j < 4; ++j)
                     if ((q >> (8 * j)) & 255u) {
                         const size_t p = 4 * i + j;
-                        const int y = (int)(p / (size_t)w), x = (int)(p - (size_t)y * w);
-                        v[0] = max(v[0], kAugBig - x), v[1] = max(v[1], x + 1), v[2] = max(v[2], kAugBig - y), v[3] = max(v[3], y + 1);
+                        const int y = (int)(p / (size_t)w);
+                        e.add((int)(p - (size_t)y * w), y);
                     }
             }
         } else {
             for (size_t p = threadIdx.x; p < hw; p += kBlock)
                 if (m[p] != 0) {
-                    const int y = (int)(p / (size_t)w), x = (int)(p - (size_t)y * w);
-                    v[0] = max(v[0], kAugBig - x), v[1] = max(v[1], x + 1), v[2] = max(v[2], kAugBig - y), v[3] = max(v[3], y + 1);
+                    const int y = (int)(p / (size_t)w);
+                    e.add((int)(p - (size_t)y * w), y);
                 }
         }
     }
-    cta_block_max4(v, s_r);
-    if (threadIdx.x != 0) return;
-    if (v[1] == 0) {                                      // beyond num[b], or an empty mask
-        out[0] = 0, out[1] = 0, out[2] = -1, out[3] = -1, out[4] = 0, out[5] = 0;
-        return;
-    }
-    const int x_min = kAugBig - v[0], y_min = kAugBig - v[2], bw = v[1] - 1 - x_min, bh = v[3] - 1 - y_min;
-    out[0] = y_min, out[1] = x_min, out[2] = bh, out[3] = bw;
-    out[4] = aug_randint(0, H - bh, u[2 * inst]), out[5] = aug_randint(0, W - bw, u[2 * inst + 1]);
+    cta_block_max4(e.v, s_r);
+    if (threadIdx.x == 0) place_record(e, H, W, u[2 * inst], u[2 * inst + 1], place + 6 * inst);      // (empty beyond num[b])
 }
 
 // Launch 2 of the composition, one lane per canvas pixel, 64 along a row: the last instance whose mask covers the pixel owns
@@ -99,14 +95,8 @@ __global__ __launch_bounds__(kBlock) void k_cta_paste(const uint8_t *__restrict_
     size_t src = 0;
     for (int n = cnt - 1; n >= 0; --n) {
         const size_t inst = (size_t)b * N + n;
-        const int32_t *p = place + 6 * inst;
-        if (p[2] < 0) continue;
-        const long long y = (long long)Y - p[4] + p[0], x = (long long)X - p[5] + p[1];
-        if (y < p[0] || y > (long long)p[0] + p[2] || x < p[1] || x > (long long)p[1] + p[3]) continue;
-        if (y < 0 || y >= h || x < 0 || x >= w) continue;                     // (the box lies inside the cut-out)
-        const size_t i = (inst * h + (size_t)y) * w + (size_t)x;
-        if (inst_mask[i] != 0) {
-            owner = n + 1, src = i;
+        if (const uint8_t *m = place_covers(place + 6 * inst, inst_mask + inst * h * w, h, w, X, Y)) {
+            owner = n + 1, src = (size_t)(m - inst_mask);
             break;
         }
     }
@@ -115,15 +105,6 @@ __global__ __launch_bounds__(kBlock) void k_cta_paste(const uint8_t *__restrict_
 #pragma unroll
     for (int c = 0; c < 3; ++c) img[o * 3 + c] = s[c];
     label[o] = (uint8_t)owner;
-}
-
-// The source position of destination (x, y) under the 8-bit bilinear rule of k_crop_warp: the integer pixel and the two 5-bit
-// weights.
-__device__ void cta_linear_coords(const double *I, int x, int y, long long *sx, long long *sy, int *a, int *b)
-{
-    const long long X0 = sat_rint((I[1] * y + I[2]) * 1024.) + 16, Y0 = sat_rint((I[4] * y + I[5]) * 1024.) + 16;
-    const long long X = (X0 + sat_rint(I[0] * x * 1024.)) >> 5, Y = (Y0 + sat_rint(I[3] * x * 1024.)) >> 5;
-    *sx = X >> 5, *sy = Y >> 5, *a = (int)(X & 31), *b = (int)(Y & 31);
 }
 
 // G:172-173 on x = (float)u8 / 255.f, channel 0 the blue one
@@ -139,36 +120,16 @@ __global__ __launch_bounds__(kBlock) void k_cta_warp(const uint8_t *__restrict__
     const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y, b = blockIdx.z;
     double g = 0.;
     if (x < iw && y < ih) {
-        const uint8_t *base = img + (size_t)b * H * W * 3;
-        long long sx, sy;
-        int a, bb;
-        cta_linear_coords(prm[b].inv_in, x, y, &sx, &sy, &a, &bb);
-        const int w00 = (32 - a) * (32 - bb) * 32, w01 = a * (32 - bb) * 32, w10 = (32 - a) * bb * 32, w11 = a * bb * 32;
-        const bool in_x0 = sx >= 0 && sx < W, in_x1 = sx + 1 >= 0 && sx + 1 < W, in_y0 = sy >= 0 && sy < H, in_y1 = sy + 1 >= 0 && sy + 1 < H;
         uint8_t *o = orig + (((size_t)b * ih + y) * iw + x) * 3;
         float f[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int p00 = in_y0 && in_x0 ? base[((size_t)sy * W + sx) * 3 + c] : 0;
-            const int p01 = in_y0 && in_x1 ? base[((size_t)sy * W + sx + 1) * 3 + c] : 0;
-            const int p10 = in_y1 && in_x0 ? base[((size_t)(sy + 1) * W + sx) * 3 + c] : 0;
-            const int p11 = in_y1 && in_x1 ? base[((size_t)(sy + 1) * W + sx + 1) * 3 + c] : 0;
-            const int v = (p00 * w00 + p01 * w01 + p10 * w10 + p11 * w11 + 16384) >> 15;
-            o[c] = (uint8_t)v;
-            f[c] = (float)v / 255.f;
-        }
+        sample_linear_to<3>(img + (size_t)b * H * W * 3, H, W, prm[b].inv_in, x, y,
+                            [&](int c, int v) { o[c] = (uint8_t)v, f[c] = (float)v / 255.f; });      // (stored as it comes: a register less)
         if constexpr (GREY) g = (double)cta_grey(f);
     }
     if constexpr (GREY) {
         const int tid = threadIdx.y * 64 + threadIdx.x;
-        s_sum[tid] = g;
-        __syncthreads();
-#pragma unroll
-        for (int s = kBlock / 2; s > 0; s >>= 1) {
-            if (tid < s) s_sum[tid] += s_sum[tid + s];
-            __syncthreads();
-        }
-        if (tid == 0) part[((size_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = s_sum[0];
+        const double sum = block_tree_sum(g, s_sum, tid);
+        if (tid == 0) part[((size_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = sum;
     }
 }
 
@@ -180,14 +141,8 @@ __global__ __launch_bounds__(kBlock) void k_cta_mean(const double *__restrict__ 
     const int b = blockIdx.x, tid = threadIdx.x;
     double s = 0.;
     for (int i = tid; i < tiles; i += kBlock) s += part[(size_t)b * tiles + i];
-    s_sum[tid] = s;
-    __syncthreads();
-#pragma unroll
-    for (int k = kBlock / 2; k > 0; k >>= 1) {
-        if (tid < k) s_sum[tid] += s_sum[tid + k];
-        __syncthreads();
-    }
-    if (tid == 0) mean[b] = (float)(s_sum[0] / (double)count);
+    s = block_tree_sum(s, s_sum, tid);
+    if (tid == 0) mean[b] = (float)(s / (double)count);
 }
 
 // One pixel of launch 3: G:202-210 in the drawn order on x = u8 / 255, then U:56.
@@ -270,11 +225,10 @@ __device__ int cta_label(const uint8_t *__restrict__ lab, int H, int W, long lon
 }
 
 // Launch 4, one lane per pixel of the output map, 64 along a row, all instances at once (C:60-66): the lane's taps, then per
-// instance the wave's extent in x (a wave is one row) and four integer atomics into st[b][i] = (kAugBig - xmin, xmax + 1,
-// kAugBig - ymin, ymax + 1), zeroed before.
+// instance the wave's row into the box st[b][i], zeroed before.  LINEAR: the labels of the taps that carry weight.
 template <bool LINEAR>
 __global__ __launch_bounds__(kBlock) void k_cta_boxes(const uint8_t *__restrict__ label, int H, int W, const CtaParam *__restrict__ prm,
-                                                      int N, int oh, int ow, int32_t *__restrict__ st)
+                                                      int N, int oh, int ow, Extent *__restrict__ st)
 {
     const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y, b = blockIdx.z;
     int lab[4] = {0, 0, 0, 0};
@@ -284,44 +238,36 @@ __global__ __launch_bounds__(kBlock) void k_cta_boxes(const uint8_t *__restrict_
         if constexpr (LINEAR) {
             long long sx, sy;
             int a, bb;
-            cta_linear_coords(I, x, y, &sx, &sy, &a, &bb);
+            warp_linear_coords(I, x, y, &sx, &sy, &a, &bb);
             lab[0] = cta_label(lb, H, W, sx, sy);                                    // (32 - a) * (32 - bb) > 0 always
             if (a) lab[1] = cta_label(lb, H, W, sx + 1, sy);
             if (bb) lab[2] = cta_label(lb, H, W, sx, sy + 1);
             if (a && bb) lab[3] = cta_label(lb, H, W, sx + 1, sy + 1);
         } else {
-            long long X, Y;
-            aug_nearest(I, x, y, &X, &Y);
-            lab[0] = cta_label(lb, H, W, X, Y);
+            sample_nearest<1>(lb, H, W, I, x, y, lab);
         }
     }
     for (int i = 0; i < N; ++i) {
         const int id = i + 1;
         const bool hit = lab[0] == id || lab[1] == id || lab[2] == id || lab[3] == id;
         if (__ballot(hit) == 0) continue;                                            // the same for the wave's lanes
-        const int nx = aug_wave_max(hit ? kAugBig - x : 0), x1 = aug_wave_max(hit ? x + 1 : 0);
-        if (threadIdx.x == 0) {
-            int32_t *s = st + 4 * ((size_t)b * N + i);
-            atomicMax(&s[0], nx);
-            atomicMax(&s[1], x1);
-            atomicMax(&s[2], kAugBig - y);
-            atomicMax(&s[3], y + 1);
-        }
+        st[(size_t)b * N + i].note(hit, x, y);
     }
 }
 
 // Launch 5, one lane per instance: cv2.boundingRect as (x, y, x + w, y + h), then C:67-68.
-__global__ __launch_bounds__(kBlock) void k_cta_box_finish(const int32_t *__restrict__ st, int count, int oh, int ow, int32_t *__restrict__ boxes)
+__global__ __launch_bounds__(kBlock) void k_cta_box_finish(const Extent *__restrict__ st, int count, int oh, int ow, int32_t *__restrict__ boxes)
 {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= count) return;
-    const int32_t *s = st + 4 * (size_t)i;
     int32_t *o = boxes + 4 * (size_t)i;
-    if (s[1] == 0) {
+    if (st[i].empty()) {
         o[0] = o[1] = o[2] = o[3] = 0;
         return;
     }
-    o[0] = kAugBig - s[0], o[1] = kAugBig - s[2], o[2] = min(s[1], ow - 1), o[3] = min(s[3], oh - 1);
+    int box[4];
+    st[i].decode(box);
+    o[0] = box[0], o[1] = box[1], o[2] = min(box[2] + 1, ow - 1), o[3] = min(box[3] + 1, oh - 1);
 }
 
 int cta_check(int B, int H, int W, const char *what)
@@ -338,9 +284,9 @@ CtaLayout cta_layout(int B, int N, int ih, int iw)
     CtaLayout L;
     L.tx = (iw + 63) / 64, L.ty = (ih + 3) / 4;
     L.boxes = 0;
-    L.part = aug_up(sizeof(int32_t) * 4 * (size_t)B * N);
-    L.mean = L.part + aug_up(sizeof(double) * (size_t)B * L.tx * L.ty);
-    L.total = L.mean + aug_up(sizeof(float) * (size_t)B);
+    L.part = align_up(sizeof(Extent) * (size_t)B * N);
+    L.mean = L.part + align_up(sizeof(double) * (size_t)B * L.tx * L.ty);
+    L.total = L.mean + align_up(sizeof(float) * (size_t)B);
     return L;
 }
 
@@ -394,7 +340,7 @@ PVV_EXPORT int pvv_ct_augment(const uint8_t *d_img, const uint8_t *d_label, int 
     if (workspace_bytes < L.total) return fail(PVV_E_WORKSPACE, "ct_augment: workspace smaller than pvv_ct_augment_workspace_bytes()");
     hipStream_t st = (hipStream_t)stream;
     const CtaParam *prm = (const CtaParam *)d_params;
-    int32_t *box_state = (int32_t *)((uint8_t *)d_workspace + L.boxes);
+    Extent *box_state = (Extent *)((uint8_t *)d_workspace + L.boxes);
     double *part = (double *)((uint8_t *)d_workspace + L.part);
     float *gs_mean = (float *)((uint8_t *)d_workspace + L.mean);
     const dim3 grid_in(L.tx, L.ty, B), block(64, 4);
@@ -416,7 +362,7 @@ PVV_EXPORT int pvv_ct_augment(const uint8_t *d_img, const uint8_t *d_label, int 
         hipLaunchKernelGGL(k_cta_colour<false>, grid_in, block, 0, st, d_orig, ih, iw, colour, gs_mean, nm, d_inp);
     if (int e = check_launch("k_cta_colour")) return e;
     if (!d_label) return PVV_OK;
-    if (hipMemsetAsync(box_state, 0, sizeof(int32_t) * 4 * (size_t)B * N, st) != hipSuccess) return fail(PVV_E_ARG, "ct_augment: hipMemsetAsync failed");
+    if (hipMemsetAsync(box_state, 0, sizeof(Extent) * (size_t)B * N, st) != hipSuccess) return fail(PVV_E_ARG, "ct_augment: hipMemsetAsync failed");
     const dim3 grid_out((ow + 63) / 64, (oh + 3) / 4, B);
     if (boxes_mode == PVV_CT_BOXES_LINEAR)
         hipLaunchKernelGGL(k_cta_boxes<true>, grid_out, block, 0, st, d_label, H, W, prm, N, oh, ow, box_state);

@@ -450,6 +450,9 @@ PVV_EXPORT int pvv_count_inliers(const float *d_direct, const float *d_coords, c
     return launch_count(a, st);
 }
 
+// crop.hpp, augment.hpp, ct_augment.hpp and tless_augment.hpp include what they share (warp.hpp, train.hpp, ct_augment.hpp): their
+// place in this list carries no meaning.
+
 // ---- detector decode, crops and the way back (ABI v8, additive) --------------------------
 #include "crop.hpp"
 

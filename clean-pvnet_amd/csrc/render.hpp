@@ -284,8 +284,8 @@ RcLayout rc_layout(int B, int M, int Nmax, int H, int W)
 {
     RcLayout L;
     L.vtx = 0;
-    L.keys = aug_up(sizeof(raster::Vtx) * (size_t)B * M * Nmax);
-    L.total = L.keys + aug_up(sizeof(unsigned long long) * (size_t)B * H * W);
+    L.keys = align_up(sizeof(raster::Vtx) * (size_t)B * M * Nmax);
+    L.total = L.keys + align_up(sizeof(unsigned long long) * (size_t)B * H * W);
     return L;
 }
 

@@ -1,11 +1,12 @@
 // tless_augment.hpp -- the T-LESS PVNet loader's training sample from rotated cut-outs and a background, and its crop around the
-// target (include/pvnet_vote.h, "T-LESS PVNet augmentation").  Included at the end of pvnet_vote.hip after ct_augment.hpp: built
-// with -ffp-contract=off, every float and double operation below rounds once, in the order written, so that the numpy twin
-// (tests/tless_augment_twin.py) gives the same bits.  sat_rint, invert_affine and the two fixed-point warp rules are those of
-// crop.hpp, aug_randint, aug_nearest and the wave reductions those of augment.hpp, the linear coordinates,
-// the grey level, the mean and the colour kernels those of ct_augment.hpp.  No random numbers and no transcendental function are
-// evaluated here: the host hands over the rotation matrices with their inverses and bounds, the drawn factors and the colour
-// records.  Everything is a gather: a pixel has one owner, and the only atomics are integer ones on per-sample accumulators.
+// target (include/pvnet_vote.h, "T-LESS PVNet augmentation").  Part of pvnet_vote.hip: built with -ffp-contract=off, every float
+// and double operation below rounds once, in the order written, so that the numpy twin (tests/tless_augment_twin.py) gives the
+// same bits.  The two fixed-point warp rules, the box accumulator, the placement record with its coverage test, the crop's map
+// and the rectangle of magnify_box are those of warp.hpp, the wave reductions and the block tree those
+// of vote_common.hpp; the colour step is the detector's: CtaParam, the grey level, the mean and the colour kernels are those
+// of ct_augment.hpp.  No random numbers and no transcendental function are evaluated here: the host hands over the rotation
+// matrices with their inverses and bounds, the drawn factors and the colour records.  Everything is a gather: a pixel has one
+// owner, and the only atomics are integer ones on per-sample accumulators.
 //
 // Reference behaviour restated:
 //   T = lib/utils/tless/tless_train_utils.py (cut_and_paste :94-120, get_fused_image :123-136, rotate_image :153-172)
@@ -13,6 +14,9 @@
 //   D = lib/datasets/tless_train/pvnet.py (read_data :60-69, get_training_img :73-105, __getitem__ :113-116)
 //   V = lib/utils/tless/tless_pvnet_utils.py (magnify_box :13-18, augment :21-73)
 #pragma once
+
+#include "ct_augment.hpp"
+#include "warp.hpp"
 
 namespace {
 
@@ -26,7 +30,7 @@ struct TlaCut {                   // PVV_TLESS_CUT_BYTES per cut-out, built by t
 static_assert(sizeof(TlaCut) == PVV_TLESS_CUT_BYTES, "pvnet_vote.h promises this size");
 
 struct TlaStat {                  // per cut-out, in the workspace; zeroed before the first launch
-    int32_t nxmin, xmax1, nymin, ymax1;   // the rotated mask's box as kAugBig - min and max + 1: 0 means no pixel
+    Extent box;                   // the rotated mask's box
     unsigned long long sum;       // the sum of the rotated mask's values (D:74)
 };
 
@@ -34,34 +38,6 @@ struct TlaPrep {                  // per sample, in the workspace
     double inv[6];                // input image -> canvas
     int32_t rx0, ry0, rx1, ry1;   // the rectangle magnify_box keeps, inclusive
 };
-
-// One pixel of a rotated cut-out: src [h,w,C] uint8 at the rotated position (x, y) through the inverse matrix, zero border;
-// the 8-bit bilinear rule of k_crop_warp or the nearest rule of k_uncrop_mask.
-template <int C>
-__device__ void tla_sample(const uint8_t *__restrict__ src, int h, int w, const double *I, int x, int y, int nearest, int *out)
-{
-    if (nearest) {
-        long long X, Y;
-        aug_nearest(I, x, y, &X, &Y);
-        const bool in = X >= 0 && X < w && Y >= 0 && Y < h;
-#pragma unroll
-        for (int c = 0; c < C; ++c) out[c] = in ? src[((size_t)Y * w + (size_t)X) * C + c] : 0;
-        return;
-    }
-    long long sx, sy;
-    int a, b;
-    cta_linear_coords(I, x, y, &sx, &sy, &a, &b);
-    const int w00 = (32 - a) * (32 - b) * 32, w01 = a * (32 - b) * 32, w10 = (32 - a) * b * 32, w11 = a * b * 32;
-    const bool in_x0 = sx >= 0 && sx < w, in_x1 = sx + 1 >= 0 && sx + 1 < w, in_y0 = sy >= 0 && sy < h, in_y1 = sy + 1 >= 0 && sy + 1 < h;
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        const int p00 = in_y0 && in_x0 ? src[((size_t)sy * w + sx) * C + c] : 0;
-        const int p01 = in_y0 && in_x1 ? src[((size_t)sy * w + sx + 1) * C + c] : 0;
-        const int p10 = in_y1 && in_x0 ? src[((size_t)(sy + 1) * w + sx) * C + c] : 0;
-        const int p11 = in_y1 && in_x1 ? src[((size_t)(sy + 1) * w + sx + 1) * C + c] : 0;
-        out[c] = (p00 * w00 + p01 * w01 + p10 * w10 + p11 * w11 + 16384) >> 15;
-    }
-}
 
 // The rotated mask of G cut-outs per sample, one lane per pixel of the D x D plane, 64 along a row; grid (tiles, G, B).  Plane
 // (b, g) reads record cut[b * stride + first + g].  Outside bound_w x bound_h the plane is zero.  With stat: the box of != 0 and
@@ -77,21 +53,18 @@ __global__ __launch_bounds__(kBlock) void k_tla_rotate_mask(const uint8_t *__res
     const TlaCut *c = cut + r;
     int v = 0;
     if (x < D && y < D) {
-        if (x < c->bw && y < c->bh) tla_sample<1>(mask + p * h * w, h, w, c->inv, x, y, nearest, &v);
+        if (x < c->bw && y < c->bh) {
+            if (nearest) sample_nearest<1>(mask + p * h * w, h, w, c->inv, x, y, &v);
+            else sample_linear<1>(mask + p * h * w, h, w, c->inv, x, y, &v);
+        }
         rot[(p * D + y) * D + x] = (uint8_t)v;
     }
     if (!stat) return;
     const bool hit = v != 0;
     if (__ballot(hit) == 0) return;                                         // the same for the wave's lanes
-    const int nx = aug_wave_max(hit ? kAugBig - x : 0), x1 = aug_wave_max(hit ? x + 1 : 0), sum = aug_wave_sum(v);
-    if (threadIdx.x == 0) {                                                 // (a wave is one row: y is the same for its lanes)
-        TlaStat *s = stat + r;
-        atomicMax(&s->nxmin, nx);
-        atomicMax(&s->xmax1, x1);
-        atomicMax(&s->nymin, kAugBig - y);
-        atomicMax(&s->ymax1, y + 1);
-        atomicAdd(&s->sum, (unsigned long long)sum);
-    }
+    stat[r].box.note(hit, x, y);
+    const int sum = wave_sum(v);
+    if (threadIdx.x == 0) atomicAdd(&stat[r].sum, (unsigned long long)sum);
 }
 
 // The rotated image of P cut-outs [P,h,w,3] -> [P,D,D,3], zero outside the bound; grid (tiles, 1, P).
@@ -103,25 +76,16 @@ __global__ __launch_bounds__(kBlock) void k_tla_rotate_img(const uint8_t *__rest
     if (x >= D || y >= D) return;
     const TlaCut *c = cut + p;
     int v[3] = {0, 0, 0};
-    if (x < c->bw && y < c->bh) tla_sample<3>(img + p * h * w * 3, h, w, c->inv, x, y, nearest, v);
+    if (x < c->bw && y < c->bh) {
+        if (nearest) sample_nearest<3>(img + p * h * w * 3, h, w, c->inv, x, y, v);
+        else sample_linear<3>(img + p * h * w * 3, h, w, c->inv, x, y, v);
+    }
     uint8_t *o = rot + ((p * D + y) * D + x) * 3;
 #pragma unroll
     for (int k = 0; k < 3; ++k) o[k] = (uint8_t)v[k];
 }
 
-// U:87-93 from the accumulators: (y_min, x_min, h, w, dst_y, dst_x); (0, 0, -1, -1, 0, 0) without a pixel.
-__device__ void tla_place(const TlaStat *s, int H, int W, double uy, double ux, int32_t *out)
-{
-    if (s->xmax1 == 0) {
-        out[0] = 0, out[1] = 0, out[2] = -1, out[3] = -1, out[4] = 0, out[5] = 0;
-        return;
-    }
-    const int x_min = kAugBig - s->nxmin, y_min = kAugBig - s->nymin, bw = s->xmax1 - 1 - x_min, bh = s->ymax1 - 1 - y_min;
-    out[0] = y_min, out[1] = x_min, out[2] = bh, out[3] = bw;
-    out[4] = aug_randint(0, H - bh, uy), out[5] = aug_randint(0, W - bw, ux);
-}
-
-// One block per sample: the placements of the 1 + N cut-outs, and the keypoints through the target's matrix (D:66) and its
+// One block per sample: the placements of the 1 + N cut-outs (U:87-93), and the keypoints through the target's matrix (D:66) and its
 // shift (D:80-82).
 __global__ __launch_bounds__(64) void k_tla_place(const TlaStat *__restrict__ stat, const TlaCut *__restrict__ cut, const double *__restrict__ u,
                                                   const double *__restrict__ kpt, int K, int N, int H, int W, int32_t *__restrict__ place,
@@ -130,11 +94,11 @@ __global__ __launch_bounds__(64) void k_tla_place(const TlaStat *__restrict__ st
     const size_t r0 = (size_t)blockIdx.x * (1 + N);
     for (int j = threadIdx.x; j <= N; j += 64) {
         int32_t rec[6];
-        tla_place(stat + r0 + j, H, W, u[2 * (r0 + j)], u[2 * (r0 + j) + 1], rec);
+        place_record(stat[r0 + j].box, H, W, u[2 * (r0 + j)], u[2 * (r0 + j) + 1], rec);
         for (int i = 0; i < 6; ++i) place[6 * (r0 + j) + i] = rec[i];
     }
     int32_t t[6];
-    tla_place(stat + r0, H, W, u[2 * r0], u[2 * r0 + 1], t);
+    place_record(stat[r0].box, H, W, u[2 * r0], u[2 * r0 + 1], t);
     const double *M = cut[r0].M;
     for (int k = threadIdx.x; k < K; k += 64) {
         const size_t i = (size_t)blockIdx.x * K + k;
@@ -143,16 +107,6 @@ __global__ __launch_bounds__(64) void k_tla_place(const TlaStat *__restrict__ st
         out_kpt[2 * i] = (rx - (double)t[1]) + (double)t[5];
         out_kpt[2 * i + 1] = (ry - (double)t[0]) + (double)t[4];
     }
-}
-
-// Does the placed cut-out cover canvas pixel (X, Y)?  rot is its D x D rotated mask.
-__device__ bool tla_hit(const int32_t *__restrict__ p, const uint8_t *__restrict__ rot, int D, int X, int Y)
-{
-    if (p[2] < 0) return false;
-    const long long y = (long long)Y - p[4] + p[0], x = (long long)X - p[5] + p[1];
-    if (y < p[0] || y > (long long)p[0] + p[2] || x < p[1] || x > (long long)p[1] + p[3]) return false;
-    if (y < 0 || y >= D || x < 0 || x >= D) return false;                    // (the box lies inside the plane)
-    return rot[(size_t)y * D + (size_t)x] != 0;
 }
 
 // One lane per canvas pixel, 64 along a row: the coverage byte (bit 7: the target; the low bits: the last distractor over the
@@ -166,10 +120,10 @@ __global__ __launch_bounds__(kBlock) void k_tla_cover(const uint8_t *__restrict_
     int owner = 0;
     if (X < W && Y < H) {
         const size_t r0 = (size_t)b * (1 + N);
-        t = tla_hit(place + 6 * r0, rot_t + (size_t)b * Dt * Dt, Dt, X, Y);
+        t = place_covers(place + 6 * r0, rot_t + (size_t)b * Dt * Dt, Dt, Dt, X, Y) != nullptr;
         const int cnt = num ? min(max(num[b], 0), N) : N;
         for (int n = cnt - 1; n >= 0; --n)
-            if (tla_hit(place + 6 * (r0 + 1 + n), rot_o + ((size_t)b * N + n) * Do * Do, Do, X, Y)) {
+            if (place_covers(place + 6 * (r0 + 1 + n), rot_o + ((size_t)b * N + n) * Do * Do, Do, Do, X, Y)) {
                 owner = n + 1;
                 break;
             }
@@ -182,7 +136,7 @@ __global__ __launch_bounds__(kBlock) void k_tla_cover(const uint8_t *__restrict_
 // D:93-100: 0 on top by draw, 1 occluded and kept, 2 occluded below the ratio and put on top, 3 no target.
 __device__ int tla_path(const TlaStat *target, unsigned long long visible, int top, double ratio)
 {
-    if (target->xmax1 == 0) return 3;
+    if (target->box.empty()) return 3;
     if (top) return 0;
     return (double)visible / (double)target->sum < ratio ? 2 : 1;
 }
@@ -194,7 +148,7 @@ __global__ __launch_bounds__(kBlock) void k_tla_resolve(const uint8_t *__restric
                                                         const TlaStat *__restrict__ stat, const unsigned long long *__restrict__ visible,
                                                         const int32_t *__restrict__ flags, const uint8_t *__restrict__ cover, int N, int H, int W,
                                                         int nearest, double ratio, uint8_t *__restrict__ out_img, uint8_t *__restrict__ out_mask,
-                                                        int32_t *__restrict__ box)
+                                                        Extent *__restrict__ box)
 {
     const int X = blockIdx.x * 64 + threadIdx.x, Y = blockIdx.y * 4 + threadIdx.y, b = blockIdx.z;
     bool m = false;
@@ -213,43 +167,39 @@ __global__ __launch_bounds__(kBlock) void k_tla_resolve(const uint8_t *__restric
         } else {
             const int32_t *p = place + 6 * (r0 + j);
             const int x = X - p[5] + p[1], y = Y - p[4] + p[0];
-            if (j == 0) tla_sample<3>(img_t + (size_t)b * ht * wt * 3, ht, wt, cut[r0].inv, x, y, nearest, v);
-            else tla_sample<3>(img_o + ((size_t)b * N + j - 1) * ho * wo * 3, ho, wo, cut[r0 + j].inv, x, y, nearest, v);
+            auto sample = [&](const uint8_t *src, int h, int w) {                      // (the sides stay uniform in either branch)
+                if (nearest) sample_nearest<3>(src, h, w, cut[r0 + j].inv, x, y, v);
+                else sample_linear<3>(src, h, w, cut[r0 + j].inv, x, y, v);
+            };
+            if (j == 0) sample(img_t + (size_t)b * ht * wt * 3, ht, wt);
+            else sample(img_o + ((size_t)b * N + j - 1) * ho * wo * 3, ho, wo);
         }
 #pragma unroll
         for (int c = 0; c < 3; ++c) out_img[o * 3 + c] = (uint8_t)v[c];
         out_mask[o] = m ? 1 : 0;
     }
     if (__ballot(m) == 0) return;
-    const int nx = aug_wave_max(m ? kAugBig - X : 0), x1 = aug_wave_max(m ? X + 1 : 0);
-    if (threadIdx.x == 0) {
-        int32_t *s = box + 4 * (size_t)b;
-        atomicMax(&s[0], nx);
-        atomicMax(&s[1], x1);
-        atomicMax(&s[2], kAugBig - Y);
-        atomicMax(&s[3], Y + 1);
-    }
+    box[b].note(m, X, Y);
 }
 
 // One lane per sample: D:102-103 as (x, y, x + w - 1, y + h - 1), the whole canvas for an empty mask; the branch; (visible, pixel_num).
-__global__ __launch_bounds__(kBlock) void k_tla_finish(const int32_t *__restrict__ box, const TlaStat *__restrict__ stat,
+__global__ __launch_bounds__(kBlock) void k_tla_finish(const Extent *__restrict__ box, const TlaStat *__restrict__ stat,
                                                        const unsigned long long *__restrict__ visible, const int32_t *__restrict__ flags, int B, int N,
                                                        int H, int W, double ratio, int32_t *__restrict__ bbox, int32_t *__restrict__ path,
                                                        long long *__restrict__ vis)
 {
     const int b = blockIdx.x * kBlock + threadIdx.x;
     if (b >= B) return;
-    const int32_t *s = box + 4 * (size_t)b;
     int32_t *o = bbox + 4 * (size_t)b;
-    if (s[1] == 0) o[0] = 0, o[1] = 0, o[2] = W - 1, o[3] = H - 1;
-    else o[0] = kAugBig - s[0], o[1] = kAugBig - s[2], o[2] = s[1] - 1, o[3] = s[3] - 1;
+    if (box[b].empty()) o[0] = 0, o[1] = 0, o[2] = W - 1, o[3] = H - 1;
+    else box[b].decode(o);
     const TlaStat *t = stat + (size_t)b * (1 + N);
     path[b] = tla_path(t, visible[b], flags[2 * b], ratio);
     vis[2 * b] = (long long)visible[b], vis[2 * b + 1] = (long long)t->sum;
 }
 
-// One block per sample: scale, centre (V:25-33), the closed form of get_affine_transform(center, scale, 0, [iw, ih]) in binary64
-// as k_crop_prep has it, its inverse, the rectangle of magnify_box (V:13-18, 52-55) and the keypoints (D:115).
+// One block per sample: scale (float32), centre (binary64) (V:25-33), the crop's map, its inverse, the rectangle of magnify_box
+// (V:13-18, 52-55) and the keypoints (D:115).
 __global__ __launch_bounds__(64) void k_tla_prep(const int32_t *__restrict__ bbox, const float *__restrict__ factor,
                                                  const double *__restrict__ box_ratio, const double *__restrict__ kpt, int K, int iw, int ih,
                                                  double *__restrict__ center, float *__restrict__ scale, double *__restrict__ trans,
@@ -261,21 +211,16 @@ __global__ __launch_bounds__(64) void k_tla_prep(const int32_t *__restrict__ bbo
     const float s = (float)(bw > bh ? bw : bh) * factor[b];
     const double cx = (double)((long long)x0 + x1) / 2., cy = (double)((long long)y0 + y1) / 2.;
     double M[6] = {0., 0., 0., 0., 0., 0.}, I[6];
-    long long c[4] = {0, 0, 0, 0};
+    int32_t r[4] = {0, 0, 0, 0};
     if (s > 0.f && isfinite(s)) {
-        const double a = (double)iw / (double)s;
-        M[0] = a, M[2] = iw * 0.5 - a * cx, M[4] = a, M[5] = ih * 0.5 - a * cy;
-        const double px0 = x0 * a + M[2], py0 = y0 * a + M[5], px1 = x1 * a + M[2], py1 = y1 * a + M[5];
-        const double mx = (px0 + px1) / 2., my = (py0 + py1) / 2., r = box_ratio[b];
-        c[0] = sat_rint((px0 - mx) * r + mx), c[1] = sat_rint((py0 - my) * r + my);
-        c[2] = sat_rint((px1 - mx) * r + mx), c[3] = sat_rint((py1 - my) * r + my);
+        crop_transform(cx, cy, (double)s, iw, ih, M);
+        magnify_rect(M, (double)x0, (double)y0, (double)x1, (double)y1, box_ratio[b], iw, ih, r);
     }
     invert_affine(M, I);
     if (threadIdx.x == 0) {
         TlaPrep p;
         for (int i = 0; i < 6; ++i) p.inv[i] = I[i], trans[6 * (size_t)b + i] = M[i];
-        p.rx0 = (int)min(max(c[0], 0ll), (long long)iw - 1), p.ry0 = (int)min(max(c[1], 0ll), (long long)ih - 1);
-        p.rx1 = (int)min(max(c[2], 0ll), (long long)iw - 1), p.ry1 = (int)min(max(c[3], 0ll), (long long)ih - 1);
+        p.rx0 = r[0], p.ry0 = r[1], p.rx1 = r[2], p.ry1 = r[3];
         prm[b] = p;
         box[4 * b] = p.rx0, box[4 * b + 1] = p.ry0, box[4 * b + 2] = p.rx1, box[4 * b + 3] = p.ry1;
         center[2 * b] = cx, center[2 * b + 1] = cy, scale[2 * b] = s, scale[2 * b + 1] = s;
@@ -301,9 +246,9 @@ __global__ __launch_bounds__(kBlock) void k_tla_warp(const uint8_t *__restrict__
         const TlaPrep *p = prm + b;
         int v[3] = {0, 0, 0};
         if (x >= p->rx0 && x <= p->rx1 && y >= p->ry0 && y <= p->ry1)
-            tla_sample<3>(img + (size_t)b * H * W * 3, H, W, p->inv, x, y, 0, v);
+            sample_linear<3>(img + (size_t)b * H * W * 3, H, W, p->inv, x, y, v);
         int mv;
-        tla_sample<1>(mask + (size_t)b * H * W, H, W, p->inv, x, y, 1, &mv);
+        sample_nearest<1>(mask + (size_t)b * H * W, H, W, p->inv, x, y, &mv);
         const size_t o = ((size_t)b * ih + y) * iw + x;
         float f[3];
 #pragma unroll
@@ -312,14 +257,8 @@ __global__ __launch_bounds__(kBlock) void k_tla_warp(const uint8_t *__restrict__
         g = (double)cta_grey(f);
     }
     const int tid = threadIdx.y * 64 + threadIdx.x;
-    s_sum[tid] = g;
-    __syncthreads();
-#pragma unroll
-    for (int s = kBlock / 2; s > 0; s >>= 1) {
-        if (tid < s) s_sum[tid] += s_sum[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) part[((size_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = s_sum[0];
+    const double sum = block_tree_sum(g, s_sum, tid);
+    if (tid == 0) part[((size_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = sum;
 }
 
 int tla_sides(int B, int H, int W, const char *what)
@@ -345,12 +284,12 @@ TlaLayout tla_layout(int B, int N, int H, int W, int Dt, int Do)
 {
     TlaLayout L;
     L.stat = 0;                                                             // stat, visible and box are zeroed by one fill
-    L.visible = L.stat + aug_up(sizeof(TlaStat) * (size_t)B * (1 + N));
-    L.box = L.visible + aug_up(sizeof(unsigned long long) * (size_t)B);
-    L.cover = L.box + aug_up(sizeof(int32_t) * 4 * (size_t)B);
-    L.rot_t = L.cover + aug_up((size_t)B * H * W);
-    L.rot_o = L.rot_t + aug_up((size_t)B * Dt * Dt);
-    L.total = L.rot_o + aug_up((size_t)B * N * Do * Do);
+    L.visible = L.stat + align_up(sizeof(TlaStat) * (size_t)B * (1 + N));
+    L.box = L.visible + align_up(sizeof(unsigned long long) * (size_t)B);
+    L.cover = L.box + align_up(sizeof(Extent) * (size_t)B);
+    L.rot_t = L.cover + align_up((size_t)B * H * W);
+    L.rot_o = L.rot_t + align_up((size_t)B * Dt * Dt);
+    L.total = L.rot_o + align_up((size_t)B * N * Do * Do);
     return L;
 }
 
@@ -361,9 +300,9 @@ TlaAugLayout tla_aug_layout(int B, int ih, int iw)
     TlaAugLayout L;
     L.tx = (iw + 63) / 64, L.ty = (ih + 3) / 4;
     L.prep = 0;
-    L.part = aug_up(sizeof(TlaPrep) * (size_t)B);
-    L.mean = L.part + aug_up(sizeof(double) * (size_t)B * L.tx * L.ty);
-    L.total = L.mean + aug_up(sizeof(float) * (size_t)B);
+    L.part = align_up(sizeof(TlaPrep) * (size_t)B);
+    L.mean = L.part + align_up(sizeof(double) * (size_t)B * L.tx * L.ty);
+    L.total = L.mean + align_up(sizeof(float) * (size_t)B);
     return L;
 }
 
@@ -435,7 +374,7 @@ PVV_EXPORT int pvv_tless_compose(const uint8_t *d_bg, const uint8_t *d_fused_bg,
     uint8_t *ws = (uint8_t *)d_workspace;
     TlaStat *stat = (TlaStat *)(ws + L.stat);
     unsigned long long *visible = (unsigned long long *)(ws + L.visible);
-    int32_t *box = (int32_t *)(ws + L.box);
+    Extent *box = (Extent *)(ws + L.box);
     uint8_t *cover = ws + L.cover, *rot_t = ws + L.rot_t, *rot_o = ws + L.rot_o;
     const TlaCut *cut = (const TlaCut *)d_cuts;
     if (hipMemsetAsync(ws, 0, L.cover, st) != hipSuccess) return fail(PVV_E_ARG, "tless_compose: hipMemsetAsync failed");

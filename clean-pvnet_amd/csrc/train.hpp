@@ -41,20 +41,12 @@ TrainLayout train_layout(int B, int tiles)
     return L;
 }
 
-// The order of block_sum (eval_common.hpp): slot j += slot j + s for s = 128, 64, ..., 1.
+// The order of block_sum (eval_common.hpp): the tree of vote_common.hpp, behind a barrier because sh is used again and again.
 template <typename T>
 __device__ T train_block_sum(T v, T *sh)
 {
-    const int tid = threadIdx.x;
     __syncthreads();
-    sh[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = kBlock / 2; s > 0; s >>= 1) {
-        if (tid < s) sh[tid] += sh[tid + s];
-        __syncthreads();
-    }
-    return sh[0];
+    return block_tree_sum(v, sh, (int)threadIdx.x);
 }
 
 template <typename T>

@@ -164,6 +164,22 @@ __device__ __forceinline__ T block_sum(T v, T *red)
     return red[0] + red[1] + red[2] + red[3];
 }
 
+// Sum over the 256 slots of sh in one fixed tree, for sums whose order is part of the result: thread tid stores v in slot
+// tid, then slot j += slot j + s for s = 128, 64, ..., 1.  Ends with a barrier, result valid in every thread; a caller that
+// uses sh again puts a barrier in front.
+template <typename T>
+__device__ T block_tree_sum(T v, T *sh, int tid)
+{
+    sh[tid] = v;
+    __syncthreads();
+#pragma unroll
+    for (int s = kBlock / 2; s > 0; s >>= 1) {
+        if (tid < s) sh[tid] += sh[tid + s];
+        __syncthreads();
+    }
+    return sh[0];
+}
+
 // Counter-based RNG: splitmix64 finaliser over (seed, stream, a, b).  Used when no
 // idxs / selection tensors are injected; statistical parity with torch's Philox only.
 __device__ __forceinline__ uint64_t mix64(uint64_t z)

@@ -119,7 +119,7 @@ def affine(cx, cy, scale, rot, dw, dh):
 
 
 def invert_affine(M):
-    """[2][3] -> 6 floats in the operation order of OpenCV's ``invertAffineTransform`` (csrc/crop.hpp); a singular map gives zeros."""
+    """[2][3] -> 6 floats in the operation order of OpenCV's ``invertAffineTransform`` (csrc/warp.hpp); a singular map gives zeros."""
     m = [float(v) for row in M for v in row]
     D = m[0] * m[4] - m[1] * m[3]
     D = 1. / D if D != 0 else 0.
@@ -164,33 +164,12 @@ def host_block(d, H, W, *, train=True, input_size=(416, 512), down_ratio=4, scal
     return block, meta
 
 
-def _upload(array, dev):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(array).view(np.uint8).reshape(-1)).pin_memory().to(dev, non_blocking=True)
-
-
 def _call(symbol, dev, *args):
-    try:
-        _native.call(_lib, symbol, dev, *args)
-    except RuntimeError as e:
-        raise RuntimeError("clean_pvnet_amd.ct_augment: %s: %s" % (e, _lib.pvv_last_error().decode())) from None
+    _native.call_named("ct_augment", _lib, symbol, dev, *args)
 
 
 def _check_img(img, what):
-    import torch
-    _native.need_cuda(img, what, "ct_augment")
-    if img.dtype != torch.uint8 or img.dim() != 4 or img.shape[3] != 3:
-        raise TypeError("clean_pvnet_amd.ct_augment: %s must be [B,H,W,3] uint8, got %s %s" % (what, tuple(img.shape), img.dtype))
-    B, H, W = (int(v) for v in img.shape[:3])
-    if not (1 <= B <= MAX_BATCH and 1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
-        raise ValueError("clean_pvnet_amd.ct_augment: B must lie in [1, %d] and the sides in [1, %d], got %s" % (MAX_BATCH, MAX_SIDE, tuple(img.shape)))
-    return B, H, W
-
-
-def _u8(t):
-    import torch
-    t = t.contiguous()
-    return t.view(torch.uint8) if t.dtype == torch.bool else t
+    return _native.check_images(img, what, "ct_augment", MAX_BATCH, MAX_SIDE)
 
 
 def ct_compose(bg, inst_img, inst_mask, num, draws):
@@ -220,10 +199,10 @@ def ct_compose(bg, inst_img, inst_mask, num, draws):
         raise ValueError("clean_pvnet_amd.ct_augment: num must be [B = %d], got %s" % (B, tuple(num.shape)))
     d = _check_draws(draws, B, N)
     dev = bg.device
-    b_, ii, im, nm = bg.contiguous(), inst_img.contiguous(), _u8(inst_mask), num.to(torch.int32).contiguous()
+    b_, ii, im, nm = bg.contiguous(), inst_img.contiguous(), _native.u8(inst_mask), num.to(torch.int32).contiguous()
     out = {"img": torch.empty(B, H, W, 3, dtype=torch.uint8, device=dev), "label": torch.empty(B, H, W, dtype=torch.uint8, device=dev),
            "place": torch.empty(B, N, 6, dtype=torch.int32, device=dev)}
-    u = _upload(d[:, N_SAMPLE:N_SAMPLE + 2 * N], dev)
+    u = _native.upload(d[:, N_SAMPLE:N_SAMPLE + 2 * N], dev)
     _call("pvv_ct_compose", dev, b_.data_ptr(), ii.data_ptr(), im.data_ptr(), nm.data_ptr(), u.data_ptr(), B, H, W, N, h, w,
           out["img"].data_ptr(), out["label"].data_ptr(), out["place"].data_ptr())
     return out
@@ -278,7 +257,7 @@ def ct_augment(img, label, draws, *, train=True, input_size=(416, 512), down_rat
     out = {"inp": torch.empty(B, 3, ih, iw, dtype=torch.float32, device=dev), "orig_img": torch.empty(B, ih, iw, 3, dtype=torch.uint8, device=dev)}
     if lb is not None:
         out["boxes"] = torch.empty(B, N, 4, dtype=torch.int32, device=dev)
-    prm = _upload(block, dev)
+    prm = _native.upload(block, dev)
     nbytes = _lib.pvv_ct_augment_workspace_bytes(B, N, ih, iw)
     if nbytes == 0:
         raise ValueError("clean_pvnet_amd.ct_augment: %s" % _lib.pvv_last_error().decode())

@@ -137,16 +137,7 @@ def _upload(parts, dev):
 
 
 def _call(symbol, dev, *args):
-    try:
-        _native.call(_lib, symbol, dev, *args)
-    except RuntimeError as e:
-        raise RuntimeError("clean_pvnet_amd.tless_augment: %s: %s" % (e, _lib.pvv_last_error().decode())) from None
-
-
-def _u8(t):
-    import torch
-    t = t.contiguous()
-    return t.view(torch.uint8) if t.dtype == torch.bool else t
+    _native.call_named("tless_augment", _lib, symbol, dev, *args)
 
 
 def _interp(interp):
@@ -161,11 +152,7 @@ def _sides(what, *sides):
 
 
 def _check_img(img, what):
-    import torch
-    _native.need_cuda(img, what, "tless_augment")
-    if img.dtype != torch.uint8 or img.dim() != 4 or img.shape[3] != 3:
-        raise TypeError("clean_pvnet_amd.tless_augment: %s must be [B,H,W,3] uint8, got %s %s" % (what, tuple(img.shape), img.dtype))
-    B, H, W = (int(v) for v in img.shape[:3])
+    B, H, W = _native.check_images(img, what, "tless_augment")
     if not 1 <= B <= MAX_BATCH:
         raise ValueError("clean_pvnet_amd.tless_augment: B must lie in [1, %d], got %d" % (MAX_BATCH, B))
     _sides(what, H, W)
@@ -199,7 +186,7 @@ def rotate_image(img, deg, interp="linear"):
     rec = cut_records(h, w, deg)
     D = rotate_side(h, w)
     dev = img.device
-    src = _u8(img)
+    src = _native.u8(img)
     out = torch.empty(lead + ((D, D, 3) if channels == 3 else (D, D)), dtype=torch.uint8, device=dev)
     block, (cuts,) = _upload([rec], dev)
     _call("pvv_tless_rotate", dev, src.data_ptr(), cuts, P, h, w, channels, D, nearest, out.data_ptr())
@@ -262,7 +249,7 @@ def tless_compose(bg, img, mask, kpt_2d, other_img, other_mask, draws, fused_bg=
     d = _check_draws(draws, B, N)
     cuts, u, flags = host_block(d, N, ht, wt, ho, wo, rot_max)
     dev = bg.device
-    keep = [bg.contiguous(), img.contiguous(), _u8(mask), kpt_2d.to(torch.float64).contiguous(), other_img.contiguous(), _u8(other_mask),
+    keep = [bg.contiguous(), img.contiguous(), _native.u8(mask), kpt_2d.to(torch.float64).contiguous(), other_img.contiguous(), _native.u8(other_mask),
             None if fused_bg is None else fused_bg.contiguous(), None if num is None else num.to(torch.int32).contiguous()]
     out = {"img": torch.empty(B, H, W, 3, dtype=torch.uint8, device=dev), "mask": torch.empty(B, H, W, dtype=torch.uint8, device=dev),
            "kpt_2d": torch.empty(B, K, 2, dtype=torch.float64, device=dev), "bbox": torch.empty(B, 4, dtype=torch.int32, device=dev),
@@ -344,7 +331,7 @@ def tless_pvnet_augment(img, mask, kpt_2d, bbox, draws, input_size=(256, 256), s
             colour["order"][b], colour["a"][b], colour["oma"][b], colour["light"][b] = colour_params(d[b], eig_val, eig_vec)
     K = int(kpt_2d.shape[1])
     dev = img.device
-    keep = [img.contiguous(), _u8(mask), kpt_2d.to(torch.float64).contiguous(), bbox.contiguous()]
+    keep = [img.contiguous(), _native.u8(mask), kpt_2d.to(torch.float64).contiguous(), bbox.contiguous()]
     out = {"inp": torch.empty(B, 3, ih, iw, dtype=torch.float32, device=dev), "orig_img": torch.empty(B, ih, iw, 3, dtype=torch.uint8, device=dev),
            "mask": torch.empty(B, ih, iw, dtype=torch.uint8, device=dev), "kpt_2d": torch.empty(B, K, 2, dtype=torch.float64, device=dev),
            "trans_input": torch.empty(B, 2, 3, dtype=torch.float64, device=dev), "center": torch.empty(B, 2, dtype=torch.float64, device=dev),

@@ -1,5 +1,5 @@
 """numpy twins of the four contracts of ``clean_pvnet_amd.crop`` (include/pvnet_vote.h, the last section): every operation in
-the order the kernels of clean-pvnet_amd/csrc/crop.hpp perform it, one IEEE rounding each, so that the device must give the
+the order the kernels of clean-pvnet_amd/csrc/crop.hpp (the warp rules: csrc/warp.hpp) perform it, one IEEE rounding each, so that the device must give the
 same bits.  Plus ``bilinear_f64``, a plain binary64 bilinear sampler that the fixed-point warp is held against, the inputs the
 CPU and the GPU tests share, and the regeneration of the heat maps of tests/golden/crop_*.npz from their seeds."""
 import numpy as np

@@ -96,6 +96,13 @@ def test_a_rotation_equals_the_twin(pkg, gpu):
     assert a["trans_input"][0, 0, 1] != 0 and a["boxes"].any()
 
 
+def test_a_rotation_with_nearest_boxes_equals_the_twin(pkg, gpu):
+    """``boxes='nearest'`` where one sample's output map looks past all four sides of the canvas (three of these five do): the
+    other nearest cases reach every side, but never all four in one sample."""
+    _c, a = _check_chain(gpu, twin.batch(5, 62), "rot=30 nearest", input_size=(44, 72), rot=30.0, boxes="nearest")
+    assert a["boxes"].any()
+
+
 def test_identity_without_the_twin(pkg, gpu):
     """Unit scale (50 on a 30 x 50 canvas at input_size (30, 50)), the centre in the middle, alphas of 1, no lighting,
     down_ratio 1: orig_img is the canvas, inp its normalisation, and every box is its instance's visible rectangle."""
