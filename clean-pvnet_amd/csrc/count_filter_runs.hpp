@@ -1,7 +1,7 @@
 // count_filter_runs.hpp -- stage 3, second launch of the staged count (ransac_voting_layer_v3; the estimate when forced), round 4:
 // work items that OWN A RUN of an (image, keypoint)'s remaining chunks, with progressive elimination inside the run.
 // Part of the single translation unit pvnet_vote.hip (included inside its anonymous namespace, after count_bf16.hpp);
-// see that file for the numerical contract and the matrix-core prefilter, count_prune.hpp for the bound L*.
+// see that file for the numerical contract, count_tile.hpp for the matrix-core prefilter, count_prune.hpp for the bound L*.
 #pragma once
 
 // ---------------------------------------------------------------------------------------------
@@ -55,20 +55,6 @@ constexpr int kRunSlots = kBfMaxHt * 32;          // 512 staging slots
 #define PVV_FS_ADD(i, n) do { } while (0)
 #define PVV_FS_OUT() do { } while (0)
 #endif
-
-// B operand of slot i (see stage_hypothesis): the counters are NOT touched.
-__device__ __forceinline__ int stage_hypothesis_b(bf16x8 *sB, int i, float2 hp, float2 org)
-{
-    __bf16 qx[3], qy[3];
-    split3(hp.x - org.x, qx);
-    split3(hp.y - org.y, qy);
-    const __bf16 one = (__bf16)1.f, zero = (__bf16)0.f;
-    const bf16x8 lo8 = {qx[0], qy[0], qx[1], qx[2], qx[0], qy[1], qy[2], qy[0]};
-    const bf16x8 hi8 = {qx[0], qy[0], qx[1], qy[1], one, one, one, zero};
-    sB[(i >> 5) * 64 + (i & 31)] = lo8;
-    sB[(i >> 5) * 64 + 32 + (i & 31)] = hi8;
-    return !(fabsf(hp.x) < 1e15f && fabsf(hp.y) < 1e15f);
-}
 
 template <uint32_t FIRST>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5, 5))) void k_count_filter_runs(
@@ -150,9 +136,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5, 5))) 
     const int gpi = __builtin_amdgcn_readfirstlane(s_gpi), ngr = (nhg + gpi - 1) / gpi;   // groups per item, group ranges per keypoint
     const int per_run = K * ngr;
     const int total = __builtin_amdgcn_readfirstlane(s_runs) * per_run;
-    const int col = lane & 31, kslice = lane >> 5;
-    const int ebase = kslice * 4;                                // this lane's pixels of a tile: ebase + e%4 + 8*(e/4)
-    const float16v zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
     for (int item = blockIdx.x; item < total; item += gridDim.x) {
         const int grun = item / per_run, rem_i = item - grun * per_run;
@@ -173,14 +156,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5, 5))) 
         const int j0 = (int)((long long)r_img * nrest / nruns), j1 = (int)((long long)(r_img + 1) * nrest / nruns);
         const int R_rem = stage_pixels<REST>(tn, nch, PC);  // pixels of the image the first launch did not count
         // L* = the larger of the leaders' lower bounds (k_lead)
-        int lstar;
-        {
-            const int lead_p = sa.lead[(size_t)bk * 8 + (lane & 3)], lead_r = sa.lead[(size_t)bk * 8 + 4 + (lane & 3)];
-            int full = lead_p >= 0 ? lead_p + lead_r : -1;
-            full = max(full, PVV_DPP(full, full, 0xB1, 0xf, false));   // quad_perm [1,0,3,2]
-            full = max(full, PVV_DPP(full, full, 0x4E, 0xf, false));   // quad_perm [2,3,0,1]
-            lstar = stage_bound(__builtin_amdgcn_readfirstlane(full), tn, sa.sub_tenth);
-        }
+        const int lstar = leaders_bound(sa.lead[(size_t)bk * 8 + (lane & 3)], sa.lead[(size_t)bk * 8 + 4 + (lane & 3)], tn, sa.sub_tenth);
 
         // ---- the ORDER of the chunks (round 5, the estimate: sa.mean).  Which pixels a hypothesis misses is not uniform: one that
         //      lies d px off the keypoint misses the pixels within ~7 d of it (the angle its offset subtends there exceeds the
@@ -214,35 +190,22 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5, 5))) 
             __syncthreads();                                     // the previous pass / item is done with sCnt, sPrev, s_keep
             for (; g < g_end && g - gp0 < 63; ++g) {             // (a slot's hypothesis index relative to the pass: 15 bits)
                 bool keep[2];
-                int slack[2];
-                unsigned long long m[2];
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
                     const int i = (int)threadIdx.x + q * kBlock, h = g * GH + i;
                     const int c = h < hn ? cnt_k[h] : 0;
                     const int m0 = h < hn ? miss_k[h] : 0;       // what other runs have already proven (>= 0, only grows)
-                    slack[q] = c + R_rem - lstar - m0;
-                    keep[q] = h < hn && slack[q] >= 0;
-                    m[q] = __ballot(keep[q]);
-                    if (lane == 0) s_keep[q * 4 + wave] = __popcll(m[q]);
+                    keep[q] = h < hn && c + R_rem - lstar - m0 >= 0;
                 }
-                __syncthreads();
-                int tot = 0, base[2] = {0, 0};
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int v = s_keep[j];
-                    tot += v;
-                    if (j < wave) base[0] += v;
-                    if (j < 4 + wave) base[1] += v;
-                }
+                int slot[2];
+                const int tot = compact_kept(s_keep, keep, lane, wave, slot);   // (one barrier)
                 const bool fits = ns + tot <= kRunSlots;          // (block-uniform; a group alone always fits)
                 if (fits) {
 #pragma unroll
                     for (int q = 0; q < 2; ++q)
                         if (keep[q]) {
-                            const int slot = ns + base[q] + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m[q] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m[q], 0u));
-                            sCnt[slot] = ((g - gp0) * GH + (int)threadIdx.x + q * kBlock) << 16;
-                            sPrev[slot] = 0;
+                            sCnt[ns + slot[q]] = ((g - gp0) * GH + (int)threadIdx.x + q * kBlock) << 16;
+                            sPrev[ns + slot[q]] = 0;
                         }
                     ns += tot;
                 }
@@ -279,31 +242,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5, 5))) 
                     const int i = tid + q * kBlock;
                     hp[q] = i < ns ? hyp_k[gp0 * GH + (int)((unsigned)sCnt[i] >> 16)] : make_float2(0.f, 0.f);
                 }
-                // ---- per pixel: the f32 unit normal (v_rsq_f32, see k_count_bf16) and the translated coordinates
-                float c1 = 0.f;
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    const int pl = tid + q * kBlock, p = pb + pl;
-                    float4 rec = make_float4(__builtin_nanf(""), 0.f, 0.f, 0.f);
-                    if (p < tn) {
-                        const float2 c = pc[q], d = pd[q];
-                        const float cx = c.x - org.x, cy = c.y - org.y;  // exact (integers)
-                        c1 = fmaxf(c1, fabsf(cx) + fabsf(cy));
-                        const float dd = d.x * d.x + d.y * d.y;
-                        if (dd >= kDdAlive && dd < INFINITY) {
-                            const float rinv = __builtin_amdgcn_rsqf(dd);
-                            rec = make_float4(d.x * rinv, d.y * rinv, cx, cy);
-                        }
-                    }
-                    sP[pl] = rec;
-                }
-                c1 = wave_max(c1);
-                if (lane == 0) sRed[wave] = c1;
+                // ---- per pixel: the f32 unit normal and the translated coordinates in sP, the waves' c1 in sRed
+                pixel_records(sP, sRed, pc, pd, org, tid, pb, tn, lane, wave);
                 int far = 0;
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
                     const int i = tid + q * kBlock;
-                    if (i < ns_pad) far |= stage_hypothesis_b(sB, i, hp[q], org);
+                    if (i < ns_pad) far |= stage_b_operand(sB, i, hp[q], org);   // (the slots' counters run on: sCnt is the run's)
                 }
                 far = __syncthreads_or(far);
                 PVV_FS(3);                                       // phase 3: the chunk's loads, pixel records, B staging, barrier
@@ -315,134 +260,18 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5, 5))) 
                 const int npx = min(tn - pb, PC);
                 const int ntile_c = (npx + 15) >> 4;              // tiles of the chunk with at least one pixel (1..32)
                 const int ntile_w = (ntile_c - wave + 3) >> 2;    // this wave's share (0..8)
-                // ---- A operands (k_count_bf16: lanes l and l+32 share the split of a row through v_permlane32_swap)
                 bf16x8 A[8];
-                if (ntile_w > 0) {
-                    const int form = (lane >> 4) & 1, prow = lane & 15;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const int jt = kslice * 4 + i;
-                        const float4 rec = sP[(jt * 4 + wave) * 16 + prow];
-                        const bool dead = rec.x != rec.x;
-                        float rx = form ? -fc.kappa * rec.y : rec.x;
-                        float ry = form ? fc.kappa * rec.x : rec.y;
-                        float rz = -(rec.z * rx + rec.w * ry);
-                        if (dead) { rx = 0.f; ry = 0.f; rz = form ? 0.f : -1e30f; }
-                        __bf16 vx[3], vy[3], cv[3];
-                        split3(rx, vx);
-                        split3(ry, vy);
-                        split3(rz, cv);
-                        const __bf16 zero = (__bf16)0.f;
-                        const bf16x8 lo8 = {vx[0], vy[0], vx[0], vx[0], vx[1], vy[0], vy[0], vy[1]};
-                        const bf16x8 hi8 = {vx[2], vy[2], vx[1], vy[1], cv[0], cv[1], cv[2], zero};
-                        uint4 x = __builtin_bit_cast(uint4, lo8), y = __builtin_bit_cast(uint4, hi8);
-                        {
-                            const auto r0 = __builtin_amdgcn_permlane32_swap(x.x, y.x, false, false);
-                            const auto r1 = __builtin_amdgcn_permlane32_swap(x.y, y.y, false, false);
-                            const auto r2 = __builtin_amdgcn_permlane32_swap(x.z, y.z, false, false);
-                            const auto r3 = __builtin_amdgcn_permlane32_swap(x.w, y.w, false, false);
-                            x = make_uint4(r0[0], r1[0], r2[0], r3[0]);
-                            y = make_uint4(r0[1], r1[1], r2[1], r3[1]);
-                        }
-                        A[i] = __builtin_bit_cast(bf16x8, x);
-                        A[4 + i] = __builtin_bit_cast(bf16x8, y);
-                    }
-                }
+                build_a_operands(sP, fc, wave, lane, ntile_w, A);
                 const int nht = ns_pad >> 5, nslot = ns;
                 const float2 *hyp_p = hyp_k + gp0 * GH;           // slot s holds hypothesis hyp_p[sCnt[s] >> 16]
+                const auto hyp_of = [&](int slot) -> float2 { return hyp_p[(unsigned)sCnt[slot] >> 16]; };
                 PVV_FS(4);                                       // phase 4: A operands
                 PVV_FS_ADD(13, nht * ntile_w);
 
-                if (__builtin_expect(far, 0)) {
-                    // some survivor is non-finite / astronomically far: exact loop (K:100-125)
-                    for (int ht = 0; ht < nht; ++ht) {
-                        const int slot = ht * 32 + col;
-                        if (slot >= nslot) continue;
-                        const float2 hq = hyp_p[(unsigned)sCnt[slot] >> 16];
-                        int inl = 0;
-                        for (int p = pb + wave * 2 + kslice; p < min(tn, pb + PC); p += 8) {
-                            const float2 c = crd[p], d = dir_k[p];
-                            inl += vote_exact(c.x, c.y, hq.x, hq.y, d.x, d.y, thresh) ? 1 : 0;
-                        }
-                        if (inl) atomicAdd(&sCnt[slot], inl);
-                    }
-                } else if (ntile_w > 0) {
-                    // ---- the matrix-core loop of k_count_bf16 (see there for every step), slots instead of hypotheses
-                    for (int ht = 0; ht < nht; ++ht) {
-                        const bf16x8 Bop = sB[ht * 64 + lane];
-                        unsigned flagged = 0u;
-                        const unsigned q01 = __builtin_bit_cast(uint4, Bop).x;
-                        const float wband = __builtin_fmaf(fc.beta * 1.02f,
-                                                           fabsf(__uint_as_float(q01 << 16)) + fabsf(__uint_as_float(q01 & 0xffff0000u)),
-                                                           epsw);
-                        unsigned qs[2] = {0u, 0u};
-                        unsigned mb[2] = {0u, 0u};
-                        int ntw = ntile_w;
-                        asm volatile("" : "+s"(ntw));
-#pragma unroll
-                        for (int jt = 0; jt < 8; ++jt) {
-                            if (jt < ntw) {
-                                const float16v acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[jt], Bop, zero16, 0, 0, 0);
-                                float tmin = INFINITY;
-                                float t[8];
-#pragma unroll
-                                for (int e = 0; e < 8; ++e) {
-                                    t[e] = acc[e] - fabsf(acc[8 + e]);
-                                    qs[jt >> 2] = __builtin_amdgcn_alignbit(qs[jt >> 2], __float_as_uint(t[e]), 31);
-                                    tmin = fminf(tmin, fabsf(t[e]));
-                                }
-                                if (__builtin_expect(__ballot(tmin <= wband) != 0, 0)) {
-                                    unsigned out_of_band = 0u;
-#pragma unroll
-                                    for (int e = 0; e < 8; ++e)
-                                        out_of_band = __builtin_amdgcn_alignbit(
-                                            out_of_band, __float_as_uint(eps - __builtin_fmaf(-fc.beta, acc[e], fabsf(t[e]))), 31);
-                                    mb[jt >> 2] |= (~out_of_band & 0xffu) << (8 * (jt & 3));
-                                    flagged |= 1u << jt;
-                                }
-                            }
-                        }
-                        int inl = 8 * ntile_w - __popc(qs[0]) - __popc(qs[1]);   // sign bit set = not an inlier
-                        if (__builtin_expect(flagged != 0u, 0) && __any((mb[0] | mb[1]) != 0u)) {
-                            const int slot = ht * 32 + col;
-                            const float2 hq = slot < nslot ? hyp_p[(unsigned)sCnt[slot] >> 16] : make_float2(0.f, 0.f);
-                            do {
-                                const int jt = __builtin_ctz(flagged);
-                                flagged &= flagged - 1;
-                                const unsigned m = mb[jt >> 2] >> (8 * (jt & 3));
-                                if (!__any((m & 0xffu) != 0u)) continue;
-                                const int after = min(ntile_w - (jt & 4), 4) - 1 - (jt & 3);
-                                const unsigned sgn = qs[jt >> 2] >> (8 * after);
-#pragma unroll
-                                for (int e = 0; e < 8; ++e) {
-                                    const bool marked = (m >> (7 - e)) & 1u;
-                                    if (!__any(marked)) continue;
-                                    const int prow = (jt * 4 + wave) * 16 + ebase + (e & 3) + 8 * (e >> 2);
-                                    const int p = pb + prow;
-                                    const int fast = ((sgn >> (7 - e)) & 1u) ? 0 : 1;
-                                    const float4 rec = sP[prow];
-                                    const float dx = hq.x - (rec.z + org.x), dy = hq.y - (rec.w + org.y);
-                                    const float a2 = __builtin_fmaf(dx, rec.x, dy * rec.y);
-                                    const float b2 = __builtin_fmaf(dx, -fc.kappa * rec.y, dy * (fc.kappa * rec.x));
-                                    const float t2 = a2 - fabsf(b2);
-                                    int decided = t2 > 0.f ? 1 : 0;
-                                    const bool unsure = marked && (!(__builtin_fmaf(-fc.beta2, a2, fabsf(t2)) > fc.eps0) || rec.x != rec.x);
-                                    if (__any(unsure)) {
-                                        int exact = 0;
-                                        if (unsure && p < tn) {
-                                            const float2 c = crd[p], d = dir_k[p];
-                                            exact = vote_exact(c.x, c.y, hq.x, hq.y, d.x, d.y, thresh) ? 1 : 0;
-                                        }
-                                        if (unsure) decided = exact;
-                                    }
-                                    if (p >= tn) decided = 0;
-                                    if (marked) inl += decided - fast;
-                                }
-                            } while (flagged != 0u);
-                        }
-                        if (inl) atomicAdd(&sCnt[ht * 32 + col], inl);    // LDS: 2 lanes x 4 waves per slot
-                    }
-                }
+                if (__builtin_expect(far, 0))   // some survivor is non-finite / astronomically far: exact loop (K:100-125)
+                    count_group_exact(sCnt, nht, nslot, wave, lane, pb, tn, crd, dir_k, thresh, hyp_of);
+                else if (ntile_w > 0)           // the matrix-core loop, slots instead of hypotheses
+                    count_tiles(sB, sP, sCnt, A, fc, eps, epsw, nht, nslot, ntile_w, wave, lane, pb, tn, org, crd, dir_k, thresh, hyp_of);
                 PVV_FS(5);                                       // phase 5: the matrix-core loop (wave 0's own)
                 __syncthreads();                                 // the chunk's counts are complete; sB / sP are free
                 PVV_FS(6);                                       // phase 6: waiting for the other waves' loops
@@ -458,7 +287,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5, 5))) 
                     const bool last = it + 1 >= nmine;
                     bool keep[2];
                     int w[2];
-                    unsigned long long m[2];
 #pragma unroll
                     for (int q = 0; q < 2; ++q) {
                         const int i = (int)threadIdx.x + q * kBlock;
@@ -476,26 +304,16 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5, 5))) 
                                 keep[q] = cnt_k[h] + R_rem - lstar - seen >= 0;        // (cnt_k[h] >= partial(h): other runs may have flushed)
                             }
                         }
-                        m[q] = __ballot(keep[q]);
-                        if (lane == 0) s_keep[q * 4 + wave] = __popcll(m[q]);
                     }
                     if (!last) {
-                        __syncthreads();                         // (also: every thread has read its slots)
-                        int tot = 0, base[2] = {0, 0};
-#pragma unroll
-                        for (int jj = 0; jj < 8; ++jj) {
-                            const int v = s_keep[jj];
-                            tot += v;
-                            if (jj < wave) base[0] += v;
-                            if (jj < 4 + wave) base[1] += v;
-                        }
+                        int slot[2];
+                        const int tot = compact_kept(s_keep, keep, lane, wave, slot);   // (its barrier also: every thread has read its slots)
                         if (((tot + 31) >> 5) < ((ns + 31) >> 5)) {  // (block-uniform) a tile less: move the survivors down
 #pragma unroll
                             for (int q = 0; q < 2; ++q)
                                 if (keep[q]) {
-                                    const int slot = base[q] + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m[q] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m[q], 0u));
-                                    sCnt[slot] = w[q];
-                                    sPrev[slot] = (unsigned short)(w[q] & 0xffff);
+                                    sCnt[slot[q]] = w[q];
+                                    sPrev[slot[q]] = (unsigned short)(w[q] & 0xffff);
                                 }
                             ns = tot;
                         }

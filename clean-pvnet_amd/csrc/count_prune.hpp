@@ -13,8 +13,9 @@
 // counts their SURE inliers over every pixel the first launch did not count (see the loop below: a lower bound of the exact
 // count, without its square roots and divisions).  lead[b,k,0..3] = the leaders' partial counts (-1: none),
 // lead[b,k,4..7] = their sure inliers in the rest: lower bounds of two FULL counts, whose maximum L* bounds the winner's
-// count from below.  The second launch (k_count_bf16<kCountFilter>) then only counts hypotheses with  partial + R >= L*
-// (count_bf16.hpp).
+// count from below.  The second launch (k_count_filter_runs, count_filter_runs.hpp; k_count_bf16<kCountFilter> when the stage
+// hint predicts runs of one chunk, host_count.hpp) then only counts hypotheses with  partial + R >= L*  (leaders_bound,
+// count_tile.hpp).
 //
 // Grid (K * nsplit, B): the remaining pixels of an (image, keypoint) are cut into nsplit shares so that the whole batch is
 // ONE generation of blocks (<= 8 per CU); a thread sees ~10 pixels, both leaders per pixel, and all its loads are in
@@ -112,8 +113,8 @@ __global__ __launch_bounds__(kBlock) void k_lead(LeadArgs a)
     //      the pixels of the rest that are inliers BEYOND DOUBT is one (<= its exact full count <= the maximum), and it needs
     //      neither the correctly rounded square roots and divisions of the exact vote (~50 VALU instructions per pixel and
     //      leader: two leaders made this kernel VALU-bound at 15 us) nor a fallback.  The test is the count kernel's second
-    //      level (count_bf16.hpp: t = a - kappa |d x nh| against a guard band) with the unit normal from
-    //      v_rsq_f32 (components within 4u, what that band assumes of an f32 normal: count_bf16.hpp) and TWICE its band: |t| - 2 beta2 a > 2 eps0
+    //      level (count_tile.hpp: t = a - kappa |d x nh| against a guard band) with the unit normal from
+    //      v_rsq_f32 (components within 4u, what that band assumes of an f32 normal: count_tile.hpp) and TWICE its band: |t| - 2 beta2 a > 2 eps0
     //      and t > 0.  Pixels the exact vote rejects outright (K:121: norm1 < 1e-6, non-finite directions) have dd <= 4e-12
     //      or dd = inf/NaN and are not counted; what the band excludes (a few 1e-5 of the pixels) only lowers the bound.
     int inl[kLead];

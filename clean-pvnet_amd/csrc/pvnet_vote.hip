@@ -38,6 +38,7 @@ constexpr int kPixPerWave = 64;      // pixels one wave walks per work item of t
 #include "vote_common.hpp"
 #include "compaction.hpp"
 #include "count_exact.hpp"
+#include "count_tile.hpp"
 #include "count_bf16.hpp"
 #include "count_filter_runs.hpp"
 #include "count_prune.hpp"

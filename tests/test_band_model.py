@@ -54,7 +54,7 @@ def rsq_unit_normal(nx, ny, seed):
         return nx * r, ny * r, dd
 
 
-DD_ALIVE = np.array([0x2b8cbcce], dtype=np.uint32).view(f32)[0]     # count_bf16.hpp: kDdAlive
+DD_ALIVE = np.array([0x2b8cbcce], dtype=np.uint32).view(f32)[0]     # count_tile.hpp: kDdAlive
 
 
 def test_dead_pixel_threshold_is_the_exact_reject():
@@ -62,7 +62,7 @@ def test_dead_pixel_threshold_is_the_exact_reject():
     be the smallest binary32 the exact test lets through (and the constant in the source must be this one)."""
     import os
     import re
-    src = open(os.path.join(os.path.dirname(__file__), "..", "clean-pvnet_amd", "csrc", "count_bf16.hpp")).read()
+    src = open(os.path.join(os.path.dirname(__file__), "..", "clean-pvnet_amd", "csrc", "count_tile.hpp")).read()
     m = re.search(r"#define kDdAlive __uint_as_float\(0x([0-9a-f]+)u\)", src)
     assert m and int(m.group(1), 16) == 0x2b8cbcce
     below = np.nextafter(DD_ALIVE, f32(0))

@@ -327,10 +327,11 @@ def test_auto_stages_dense_crops_by_their_real_work(synth, pkg, gpu):
             assert (ms[0][5] > 0) == first and (ms[1][5] > 0) == want_staged, (Bn, ms)     # (each call completes before the next decides)
 
 
-def test_auto_follows_the_stage_hint(synth, pkg, gpu):
+def test_auto_follows_the_stage_hint(oracle, synth, pkg, gpu):
     """PVV_COUNT_AUTO stages a v3 call only if the winner ratios the last completed calls left in the per-device hint
     reach the problem's threshold (pvv_stage_hint_query): after calls on a clean field the next calls are staged, after
-    calls on a field with 35 % outlier pixels they are not -- and either way the results are those of the full pass."""
+    calls on a field with 35 % outlier pixels they are not -- and either way the results are those of the full pass.  Last, on
+    the clean batch's hint, a batch whose every hypothesis of one keypoint survives the filter, non-finite ones included."""
     from clean_pvnet_amd import ransac_voting as ext
     c = {**synth.CONFIGS["cfg3"], "B": 16}                        # 2.3e10: large enough for AUTO to consider staging
     hn = c["hn"]
@@ -356,6 +357,45 @@ def test_auto_follows_the_stage_hint(synth, pkg, gpu):
         # the explicit modes ignore the hint
         assert all(r[5] > 0 for r in ext.stage_ms_in_pipeline([d["mask"]], [d["vertex"]], hn, 0.99, 5, 30000, 5, 2, ext.COUNT_STAGED))
         assert all(r[5] < 0 for r in ext.stage_ms_in_pipeline([d["mask"]], [d["vertex"]], hn, 0.99, 5, 30000, 5, 2, ext.COUNT_FULL))
+
+    # The far-group loop of k_count_bf16<kCountFilter>.  That kernel is AUTO's second launch here (16 images x 9 remaining
+    # chunks x 9 keypoints = 1296 items: runs of one chunk) and nothing above hands it a non-finite hypothesis.  So: the clean
+    # batch again, with keypoint 0 of image 0 given random directions on every second foreground pixel and NaN / inf /
+    # 1e25-scaled ones on every tenth.  The winner of that keypoint then explains no more pixels than the first launch leaves
+    # uncounted (R): partial(h) + R >= R >= L* for EVERY hypothesis, the non-finite ones included -- all of them are staged, and
+    # their one group takes the exact loop in each of its items.
+    dm, dv = clean["mask"].clone(), clean["vertex"].clone()
+    ys, xs = torch.nonzero(dm[0], as_tuple=True)
+    n0 = ys.numel()
+    assert n0 >= 8 * 512 - 511                                    # image 0 is staged
+    odd = torch.arange(1, n0, 2, device=gpu)
+    ang = (2 * np.pi * torch.rand(odd.numel(), generator=torch.Generator().manual_seed(23))).to(gpu)
+    dv[0, ys[odd], xs[odd], 0, :] = torch.stack([torch.cos(ang), torch.sin(ang)], -1)
+    pick = torch.arange(0, n0, 10, device=gpu)
+    dv[0, ys[pick[0::3]], xs[pick[0::3]], 0, 0] = float("nan")
+    dv[0, ys[pick[1::3]], xs[pick[1::3]], 0, 1] = float("inf")
+    dv[0, ys[pick[2::3]], xs[pick[2::3]], 0, :] *= 1e25
+    tn_all = [int(x) for x in (dm != 0).sum((1, 2))]
+    idxs = synth.make_idxs(tn_all, hn, c["K"], seed=24)
+    det = []
+    oracle.ransac_voting_layer_v3(_np(dm[:1]), _np(dv[:1]), hn, 0.99, idxs=_np(idxs[:1]), singular="zero", details=det)
+    rest = sum(min(512, n0 - 512 * ch) for ch in range((n0 + 511) // 512) if ch % 8 not in (1, 5))
+    assert int(det[0]["win_counts"][0]) <= rest, (det[0]["win_counts"], rest, n0)
+    i_d = idxs.to(gpu)
+
+    def v3i(k):
+        return ext.ransac_voting_v3(dm, dv, hn, 0.99, 5, 30000, i_d, None, 0, ext.SINGULAR_ZERO, count_kernel=k)
+
+    v3(clean, ext.COUNT_AUTO)                                     # the hint: the clean batch's ratios, as after the loop
+    torch.cuda.synchronize()
+    ms = ext.stage_ms_in_pipeline([dm], [dv], hn, 0.99, 5, 30000, 5, 1, ext.COUNT_AUTO)
+    assert ms[0][5] > 0, ms                                       # on that hint AUTO stages this batch: the first launch's mark
+    v3(clean, ext.COUNT_AUTO)                                     # (the hint again: the call above left its own)
+    torch.cuda.synchronize()
+    got, ref = v3i(ext.COUNT_AUTO), v3i(ext.COUNT_FULL)
+    for a_, b_, nm in zip(got[:3], ref[:3], ("keypoints", "winner counts", "tn")):
+        assert torch.equal(a_, b_), nm
+    assert int(got[1][0, 0]) == int(det[0]["win_counts"][0])
 
 
 @pytest.mark.parametrize("B,H,W,K,hn,fg,outlier,what", [

@@ -370,7 +370,7 @@ def test_count_kernel_isa_guard(tmp_path):
     unit to gfx950 ISA with the shipped flags and assert, for ALL instantiations (full, staged-first, staged-filter) and for
     k_count_filter_runs, 8 matrix-core
     instructions, at most 96 VGPRs, and no scratch access between the first and the last of them (a spill inside the hot
-    loop would not fail any parity test, only the clock)."""
+    loop would not fail any parity test, only the clock); no spilled VGPR and no scratch at all outside round 3's filter kernel."""
     import re
     import shutil
     from importlib import util
@@ -398,9 +398,15 @@ def test_count_kernel_isa_guard(tmp_path):
         assert vg <= 96, (frag, vg)
         lds = int(re.search(r"\.group_segment_fixed_size:\s+(\d+)", meta).group(1))
         assert lds <= 32768, (frag, lds)                                # 5 blocks per CU in 160 KB
-        # spilled registers are tolerated in the per-item prologue and the rare exact path only: every scratch access
-        # lies before the first or after the last matrix-core instruction (checked above), and there are few of them
-        assert int(re.search(r"\.vgpr_spill_count:\s+(\d+)", meta).group(1)) <= 16, frag
+        # spilled registers are tolerated in round 3's filter kernel only (at most 9 of them, 40 bytes of scratch), in its
+        # per-item prologue and the rare exact path: every scratch access lies before the first or after the last
+        # matrix-core instruction (checked above).  The other five instantiations spill nothing and own no scratch.
+        spills = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", meta).group(1))
+        scratch = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", meta).group(1))
+        if "k_count_bf16ILi2E" in frag:
+            assert spills <= 9 and scratch <= 40, (frag, spills, scratch)
+        else:
+            assert spills == 0 and scratch == 0, (frag, spills, scratch)
 
 
 def test_stage_hint_thresholds_and_no_data_without_a_gpu():

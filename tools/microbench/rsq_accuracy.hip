@@ -1,7 +1,7 @@
 // rsq_accuracy.hip -- v_rsq_f32 on gfx950 against the correctly rounded 1/sqrt(x), EXHAUSTIVELY over every positive normal
 // binary32 input: the largest error in units of the last place of the correctly rounded result, how many inputs are not
 // correctly rounded, and the largest error of the unit-normal component  nx = fl(dx * rsq(fl(dx^2 + dy^2)))  against the
-// true dx / |d| on a dense set of directions -- the number the guard bands of count_bf16.hpp / count_prune.hpp assume
+// true dx / |d| on a dense set of directions -- the number the guard bands of count_tile.hpp / count_prune.hpp assume
 // ("f32 unit normal").
 #include <hip/hip_runtime.h>
 #include <cmath>
