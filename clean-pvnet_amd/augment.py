@@ -26,13 +26,12 @@ import numpy as np
 from . import _native
 from ._native import DOUBLE, INT, PTR, SIZE
 
-_lib = _native.load("augment", "libpvnet_vote.so", {
-    "pvv_last_error": (ctypes.c_char_p, []),
+_lib = _native.bind("augment", "libpvnet_vote.so", {
     "pvv_augment_workspace_bytes": (SIZE, [INT, INT, INT]),
     "pvv_pvnet_augment": (INT, [PTR, PTR, PTR, INT, INT, INT, INT, INT, INT, INT, DOUBLE, PTR, INT, INT, PTR, SIZE, PTR, PTR, PTR, PTR, PTR, PTR]),
     "pvv_transform_workspace_bytes": (SIZE, [INT, INT, INT]),
     "pvv_pvnet_transform": (INT, [PTR, INT, INT, INT, PTR, INT, INT, PTR, PTR, PTR, SIZE, PTR, PTR]),
-})
+}, last_error="pvv_last_error")
 
 N_DRAWS = 12
 COLUMNS = ("degree", "ratio", "hbeg", "wbeg", "blur", "blur_size", "brightness", "contrast", "saturation", "hue", "order", "unused")
@@ -109,7 +108,7 @@ def jitter_params(d, blur_prob, jitter):
 
 
 def _call(symbol, dev, *args):
-    _native.call_named("augment", _lib, symbol, dev, *args)
+    _lib.call(symbol, dev, *args)
 
 
 def pvnet_augment(img, mask, kpt_2d, out_size, draws, *, rotate=(-30, 30), overlap_ratio=0.8, resize_ratio=(0.8, 1.2)):
@@ -152,8 +151,7 @@ def pvnet_augment(img, mask, kpt_2d, out_size, draws, *, rotate=(-30, 30), overl
            "path": torch.empty(B, dtype=torch.int32, device=dev), "window": torch.empty(B, 6, dtype=torch.int32, device=dev)}
     prm = _native.upload(block, dev)
     mth, mtw = int(block["th"].max()), int(block["tw"].max())                    # the rotated windows lie in the workspace
-    nbytes = _lib.pvv_augment_workspace_bytes(B, mth, mtw)
-    ws = _native.workspace(nbytes, dev)
+    ws, _ = _lib.workspace("pvv_augment_workspace_bytes", dev, B, mth, mtw)
     _call("pvv_pvnet_augment", dev, im.data_ptr(), m.data_ptr(), kp.data_ptr() if K else None, int(kp.dtype == torch.float64), B, H, W, K,
           height, width, float(overlap_ratio), prm.data_ptr(), mth, mtw, ws.data_ptr(), ws.numel(), out["img"].data_ptr(), out["mask"].data_ptr(),
           out["kpt_2d"].data_ptr() if K else None, out["path"].data_ptr(), out["window"].data_ptr())
@@ -186,7 +184,7 @@ def pvnet_transform(img, draws, *, blur_prob=0.5, jitter=(0.1, 0.1, 0.05, 0.05),
         block = jitter_params(_check_draws(draws, B), float(blur_prob), jitter)
         has_blur, has_contrast = int((block["k"] > 0).any()), int((block["order"] == 1).any())
         prm = _native.upload(block, dev)
-        ws = _native.workspace(_lib.pvv_transform_workspace_bytes(B, h, w), dev)
+        ws, _ = _lib.workspace("pvv_transform_workspace_bytes", dev, B, h, w)
     im = img.contiguous()
     out = torch.empty(B, 3, h, w, dtype=torch.float32, device=dev)
     _call("pvv_pvnet_transform", dev, im.data_ptr(), B, h, w, _native.ptr(prm), has_blur, has_contrast, mean_c, std_c, _native.ptr(ws),

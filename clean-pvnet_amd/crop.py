@@ -16,15 +16,14 @@ import ctypes
 from . import _native
 from ._native import DOUBLE, INT, PTR, SIZE
 
-_lib = _native.load("crop", "libpvnet_vote.so", {
-    "pvv_last_error": (ctypes.c_char_p, []),
+_lib = _native.bind("crop", "libpvnet_vote.so", {
     "pvv_ct_workspace_bytes": (SIZE, [INT] * 5),
     "pvv_ct_decode": (INT, [PTR, PTR, INT, INT, INT, INT, INT, INT, PTR, SIZE, PTR, PTR, PTR, PTR]),
     "pvv_crop_boxes": (INT, [PTR, INT, INT, INT, PTR, PTR, INT, INT, INT, DOUBLE, INT, DOUBLE, PTR, PTR, PTR, SIZE, PTR, PTR, PTR,
                              PTR, PTR, PTR]),
     "pvv_uncrop_keypoints": (INT, [PTR, INT, PTR, INT, INT, PTR, PTR]),
     "pvv_uncrop_mask": (INT, [PTR, INT, INT, INT, PTR, INT, INT, INT, PTR, PTR]),
-})
+}, last_error="pvv_last_error", prefix="crop", plain_calls=True)
 
 MAX_K = 256                        # PVV_CT_MAX_K
 _WORKSPACE_PER_BOX = 96            # PVV_CROP_WORKSPACE_PER_BOX
@@ -56,12 +55,9 @@ def decode_ct_hm(ct_hm, wh, K=100, clip=True):
     det = torch.empty(B, K, 6, dtype=torch.float32, device=dev)
     count = torch.empty(B, dtype=torch.int32, device=dev)
     if B:
-        nbytes = _lib.pvv_ct_workspace_bytes(B, C, H, W, K)
-        if nbytes == 0:
-            raise ValueError("crop: %s" % _lib.pvv_last_error().decode())
-        ws = _native.workspace(nbytes, dev)
-        _native.call(_lib, "pvv_ct_decode", dev, hm.data_ptr(), whc.data_ptr(), B, C, H, W, K, int(bool(clip)), ws.data_ptr(),
-                     ws.numel(), ct.data_ptr(), det.data_ptr(), count.data_ptr())
+        ws, _ = _lib.workspace("pvv_ct_workspace_bytes", dev, B, C, H, W, K)
+        _lib.call("pvv_ct_decode", dev, hm.data_ptr(), whc.data_ptr(), B, C, H, W, K, int(bool(clip)), ws.data_ptr(),
+                  ws.numel(), ct.data_ptr(), det.data_ptr(), count.data_ptr())
     return ct, det, count
 
 
@@ -101,10 +97,10 @@ def crop_boxes(img, boxes, image_index, out_size, *, scale_ratio, box_ratio=None
     for lo in range(0, N, _MAX_BOXES):
         n = min(N - lo, _MAX_BOXES)
         ws = _native.workspace(n * _WORKSPACE_PER_BOX, dev)
-        _native.call(_lib, "pvv_crop_boxes", dev, im.data_ptr(), B, H, W, bx[lo:].data_ptr(), ix[lo:].data_ptr(), n, ow, oh,
-                     float(scale_ratio), int(box_ratio is not None), float(box_ratio or 0.0), mean_c, std_c, ws.data_ptr(), ws.numel(),
-                     out["inp"][lo:].data_ptr(), out["center"][lo:].data_ptr(), out["scale"][lo:].data_ptr(),
-                     out["trans"][lo:].data_ptr(), out["valid"][lo:].data_ptr())
+        _lib.call("pvv_crop_boxes", dev, im.data_ptr(), B, H, W, bx[lo:].data_ptr(), ix[lo:].data_ptr(), n, ow, oh,
+                  float(scale_ratio), int(box_ratio is not None), float(box_ratio or 0.0), mean_c, std_c, ws.data_ptr(), ws.numel(),
+                  out["inp"][lo:].data_ptr(), out["center"][lo:].data_ptr(), out["scale"][lo:].data_ptr(),
+                  out["trans"][lo:].data_ptr(), out["valid"][lo:].data_ptr())
     return out
 
 
@@ -122,8 +118,7 @@ def uncrop_keypoints(kpt_2d, trans):
     kp, tr = kpt_2d.contiguous(), trans.contiguous()
     out = torch.empty(N, K, 2, dtype=torch.float64, device=kp.device)
     if N and K:
-        _native.call(_lib, "pvv_uncrop_keypoints", kp.device, kp.data_ptr(), int(kp.dtype == torch.float64), tr.data_ptr(), N, K,
-                     out.data_ptr())
+        _lib.call("pvv_uncrop_keypoints", kp.device, kp.data_ptr(), int(kp.dtype == torch.float64), tr.data_ptr(), N, K, out.data_ptr())
     return out
 
 
@@ -146,6 +141,5 @@ def uncrop_mask(mask, trans, canvas_size):
     out = torch.empty(N, Hc, Wc, dtype=torch.uint8, device=m.device)
     for lo in range(0, N, _MAX_BOXES):
         n = min(N - lo, _MAX_BOXES)
-        _native.call(_lib, "pvv_uncrop_mask", m.device, m[lo:].data_ptr(), m.element_size(), h, w, tr[lo:].data_ptr(), n, Hc, Wc,
-                     out[lo:].data_ptr())
+        _lib.call("pvv_uncrop_mask", m.device, m[lo:].data_ptr(), m.element_size(), h, w, tr[lo:].data_ptr(), n, Hc, Wc, out[lo:].data_ptr())
     return out

@@ -1,6 +1,8 @@
 // ct_train.hpp -- the detector's heat-map targets and training loss (include/pvnet_vote.h, "Detector training: heat-map
 // targets and the detector loss").  Included at the end of pvnet_vote.hip after train.hpp, whose tile constants, block sum and
-// 16-byte accessors it shares: built with -ffp-contract=off, so every operation below rounds once, in the order written.
+// 16-byte accessors it shares, and on the host side its workspace layout (loss_layout), workspace check (train_ws) and out_state
+// check (loss_state); CTT_LAUNCH picks a kernel's 16-byte or scalar form.  Built with -ffp-contract=off, so every operation
+// below rounds once, in the order written.
 // The numpy twin (tests/ct_train_twin.py) follows the same order.
 //
 // Reference behaviour restated (paths relative to the reference's root):
@@ -25,20 +27,7 @@ struct CttShape {
 };
 
 // Workspace: per (image, tile) {P, Q} binary64 and num_pos int64, then per image {P, Q, S, M} binary64 and {num_pos, bad} int64.
-struct CttLayout { size_t part, cnt, img, imgcnt, total; };
-
-CttLayout ctt_layout(int B, int tiles)
-{
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    CttLayout L;
-    const size_t bt = (size_t)B * tiles;
-    L.part = 0;
-    L.cnt = up(L.part + bt * 2 * sizeof(double));
-    L.img = up(L.cnt + bt * sizeof(long long));
-    L.imgcnt = up(L.img + (size_t)B * 4 * sizeof(double));
-    L.total = up(L.imgcnt + (size_t)B * 2 * sizeof(long long));
-    return L;
-}
+LossLayout ctt_layout(int B, int tiles) { return loss_layout(B, tiles, 2, 1, 4, 2); }
 
 __device__ __forceinline__ double ctt_box_at(const void *__restrict__ boxes, int kind, size_t e)
 {
@@ -412,12 +401,12 @@ int ctt_inputs(CttShape &s, const CttArgs &a, long long hp_stride, long long wp_
     return PVV_OK;
 }
 
-int ctt_state(const void *state)
-{
-    if (!state) return fail(PVV_E_ARG, "ct_train: NULL device pointer");
-    if ((uintptr_t)state % 8 != 0) return fail(PVV_E_ARG, "ct_train: out_state must be 8-byte aligned");
-    return PVV_OK;
-}
+// k<VEC>, the 16-byte or the scalar form of a kernel, on a grid of kBlock-lane workgroups.
+#define CTT_LAUNCH(k, vec, grid, st, ...)                                                      \
+    do {                                                                                       \
+        if (vec) hipLaunchKernelGGL(k<true>, grid, dim3(kBlock), 0, st, __VA_ARGS__);          \
+        else hipLaunchKernelGGL(k<false>, grid, dim3(kBlock), 0, st, __VA_ARGS__);             \
+    } while (0)
 
 }  // namespace
 
@@ -435,12 +424,8 @@ PVV_EXPORT int pvv_ct_targets(const void *d_boxes, int box_kind, const void *d_c
     hipLaunchKernelGGL(k_ctt_objects, dim3(B), dim3(kBlock), 0, st, s, d_boxes, box_kind, d_cls, cls_is_i64, d_num, num_is_i64, d_wh, d_ct_cls,
                        d_ct_ind, d_ct_01, d_ct_num);
     if (int e = check_launch("k_ctt_objects")) return e;
-    if (s.E % 4 == 0 && train_aligned(d_ct_hm, 0))
-        hipLaunchKernelGGL(k_ctt_heatmap<true>, dim3(s.tiles, B), dim3(kBlock), 0, st, s, d_boxes, box_kind, d_cls, cls_is_i64, d_num, num_is_i64,
-                           d_ct_hm);
-    else
-        hipLaunchKernelGGL(k_ctt_heatmap<false>, dim3(s.tiles, B), dim3(kBlock), 0, st, s, d_boxes, box_kind, d_cls, cls_is_i64, d_num, num_is_i64,
-                           d_ct_hm);
+    CTT_LAUNCH(k_ctt_heatmap, s.E % 4 == 0 && train_aligned(d_ct_hm, 0), dim3(s.tiles, B), st, s, d_boxes, box_kind, d_cls, cls_is_i64, d_num,
+               num_is_i64, d_ct_hm);
     return check_launch("k_ctt_heatmap");
 }
 
@@ -462,15 +447,14 @@ PVV_EXPORT int pvv_ct_loss_forward(const float *d_hm_pred, long long hp_image_st
     bool vec = false;
     if (int e = ctt_inputs(s, a, hp_image_stride, wp_image_stride, hm_image_stride, vec)) return e;
     if (!d_out_losses) return fail(PVV_E_ARG, "ct_train: NULL device pointer");
-    if (int e = ctt_state(d_out_state)) return e;
-    const CttLayout L = ctt_layout(B, s.tiles);
+    if (int e = loss_state(d_out_state, "ct_train")) return e;
+    const LossLayout L = ctt_layout(B, s.tiles);
     if (int e = train_ws(workspace, workspace_bytes, L.total)) return e;
     hipStream_t st = (hipStream_t)stream;
     unsigned char *ws = (unsigned char *)workspace;
     double *part = (double *)(ws + L.part), *img = (double *)(ws + L.img);
     long long *cnt = (long long *)(ws + L.cnt), *imgcnt = (long long *)(ws + L.imgcnt);
-    if (vec) hipLaunchKernelGGL(k_ctt_focal_tiles<true>, dim3(s.tiles, B), dim3(kBlock), 0, st, s, a.hp, a.hm, part, cnt);
-    else hipLaunchKernelGGL(k_ctt_focal_tiles<false>, dim3(s.tiles, B), dim3(kBlock), 0, st, s, a.hp, a.hm, part, cnt);
+    CTT_LAUNCH(k_ctt_focal_tiles, vec, dim3(s.tiles, B), st, s, a.hp, a.hm, part, cnt);
     if (int e = check_launch("k_ctt_focal_tiles")) return e;
     hipLaunchKernelGGL(k_ctt_loss_images, dim3(B), dim3(kBlock), 0, st, s, (const double *)part, (const long long *)cnt, a.wp, a.wh, a.ind,
                        ind_is_i64, a.w01, img, imgcnt);
@@ -491,19 +475,13 @@ PVV_EXPORT int pvv_ct_loss_backward(const float *d_hm_pred, long long hp_image_s
     bool vec = false;
     if (int e = ctt_inputs(s, a, hp_image_stride, wp_image_stride, hm_image_stride, vec)) return e;
     if (!d_grad_losses || !d_grad_hm || !d_grad_wh) return fail(PVV_E_ARG, "ct_train: NULL device pointer");
-    if (int e = ctt_state(d_out_state)) return e;
+    if (int e = loss_state(d_out_state, "ct_train")) return e;
     hipStream_t st = (hipStream_t)stream;
     const long long *state = (const long long *)d_out_state;
-    if (vec && train_aligned(d_grad_hm, 0))
-        hipLaunchKernelGGL(k_ctt_focal_backward<true>, dim3(s.tiles, B), dim3(kBlock), 0, st, s, a.hp, a.hm, state, d_grad_losses, d_grad_hm);
-    else
-        hipLaunchKernelGGL(k_ctt_focal_backward<false>, dim3(s.tiles, B), dim3(kBlock), 0, st, s, a.hp, a.hm, state, d_grad_losses, d_grad_hm);
+    CTT_LAUNCH(k_ctt_focal_backward, vec && train_aligned(d_grad_hm, 0), dim3(s.tiles, B), st, s, a.hp, a.hm, state, d_grad_losses, d_grad_hm);
     if (int e = check_launch("k_ctt_focal_backward")) return e;
     const int E2 = 2 * s.HW, tiles2 = (int)((2ll * s.HW + kTrainTile - 1) / kTrainTile);
-    if (E2 % 4 == 0 && train_aligned(d_grad_wh, 0))
-        hipLaunchKernelGGL(k_ctt_wh_fill<true>, dim3(tiles2, B), dim3(kBlock), 0, st, E2, state, d_grad_wh);
-    else
-        hipLaunchKernelGGL(k_ctt_wh_fill<false>, dim3(tiles2, B), dim3(kBlock), 0, st, E2, state, d_grad_wh);
+    CTT_LAUNCH(k_ctt_wh_fill, E2 % 4 == 0 && train_aligned(d_grad_wh, 0), dim3(tiles2, B), st, E2, state, d_grad_wh);
     if (int e = check_launch("k_ctt_wh_fill")) return e;
     hipLaunchKernelGGL(k_ctt_wh_backward, dim3(B), dim3(kBlock), 0, st, s, a.wp, a.wh, a.ind, ind_is_i64, a.w01, state, d_grad_losses, d_grad_wh);
     return check_launch("k_ctt_wh_backward");

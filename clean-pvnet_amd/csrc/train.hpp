@@ -10,6 +10,10 @@
 // Every sum is binary64 in one order that the launch does not choose: lane, tile (a workgroup), image, batch.  No float
 // atomics: per-tile partials go to the workspace and two small launches sum them.  The target field is recomputed per
 // pixel from the mask and the keypoints (KPT) or read (the field form); the backward pass recomputes d and the softmax.
+//
+// Host side: what this loss and the detector's (ct_train.hpp) have in common is stated here once -- the workspace layout
+// (loss_layout, each loss names its four multipliers), the out_state check (loss_state, by message prefix) and the workspace
+// check (train_ws).  Every entry point picks its kernel's template form through TRAIN_DISPATCH / TRAIN_DISPATCH_VEC.
 #pragma once
 
 namespace {
@@ -25,21 +29,24 @@ struct TrainShape {
     long long vp_stride, sp_stride, tg_stride;        // elements between two images of vertex_pred / seg_pred / target
 };
 
-// Workspace: per (image, tile) the two binary64 partials and the two integer counts, then the same per image.
-struct TrainLayout { size_t part, cnt, img, imgcnt, total; };
+// The workspace of a fused loss (this one and ct_train.hpp's): per (image, tile) part_f64 binary64 partials and part_i64 integer
+// counts, then per image img_f64 and img_i64 of them; every section starts on a 256-byte boundary.
+struct LossLayout { size_t part, cnt, img, imgcnt, total; };
 
-TrainLayout train_layout(int B, int tiles)
+LossLayout loss_layout(int B, int tiles, int part_f64, int part_i64, int img_f64, int img_i64)
 {
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    TrainLayout L;
+    LossLayout L;
     const size_t bt = (size_t)B * tiles;
     L.part = 0;
-    L.cnt = up(L.part + bt * 2 * sizeof(double));
-    L.img = up(L.cnt + bt * 2 * sizeof(long long));
-    L.imgcnt = up(L.img + (size_t)B * 2 * sizeof(double));
-    L.total = up(L.imgcnt + (size_t)B * 2 * sizeof(long long));
+    L.cnt = align_up(L.part + bt * part_f64 * sizeof(double));
+    L.img = align_up(L.cnt + bt * part_i64 * sizeof(long long));
+    L.imgcnt = align_up(L.img + (size_t)B * img_f64 * sizeof(double));
+    L.total = align_up(L.imgcnt + (size_t)B * img_i64 * sizeof(long long));
     return L;
 }
+
+// Here: two partials and two counts per (image, tile), the same per image.
+LossLayout train_layout(int B, int tiles) { return loss_layout(B, tiles, 2, 2, 2, 2); }
 
 // The order of block_sum (eval_common.hpp): the tree of vote_common.hpp, behind a barrier because sh is used again and again.
 template <typename T>
@@ -390,13 +397,19 @@ struct TrainArgs {
     const float *target;
 };
 
+int train_mask_kind(int kind)
+{
+    if (kind != PVV_MASK_U8 && kind != PVV_MASK_I32 && kind != PVV_MASK_I64)
+        return fail(PVV_E_ARG, "train: mask_kind must be PVV_MASK_U8, PVV_MASK_I32 or PVV_MASK_I64");
+    return PVV_OK;
+}
+
 // The checks forward and backward share on their inputs; fills the strides of s and whether the 16-byte form applies.
 int train_inputs(TrainShape &s, const TrainArgs &a, long long vp_stride, long long sp_stride, long long tg_stride, bool &vec)
 {
     if (!a.vp || !a.sp || !a.mask) return fail(PVV_E_ARG, "train: NULL device pointer");
     if ((a.kpt != nullptr) == (a.target != nullptr)) return fail(PVV_E_ARG, "train: exactly one of kpt_2d and target must be given");
-    if (a.mask_kind != PVV_MASK_U8 && a.mask_kind != PVV_MASK_I32 && a.mask_kind != PVV_MASK_I64)
-        return fail(PVV_E_ARG, "train: mask_kind must be PVV_MASK_U8, PVV_MASK_I32 or PVV_MASK_I64");
+    if (int e = train_mask_kind(a.mask_kind)) return e;
     if (vp_stride < 2ll * s.K * s.HW || sp_stride < (long long)s.C * s.HW || (a.target && tg_stride < 2ll * s.K * s.HW))
         return fail(PVV_E_ARG, "train: an image stride is smaller than its image");
     s.vp_stride = vp_stride, s.sp_stride = sp_stride, s.tg_stride = a.target ? tg_stride : 0;
@@ -411,6 +424,15 @@ int train_ws(const void *ws, size_t ws_bytes, size_t need)
     if ((uintptr_t)ws % 256 != 0) return fail(PVV_E_ARG, "train: workspace must be 256-byte aligned");
     if (ws_bytes < need) return fail(PVV_E_WORKSPACE, "train: workspace too small");
     return PVV_OK;
+}
+
+// The out_state of a fused loss (this one and ct_train.hpp's), which the forward pass writes and the backward pass reads.
+int loss_state(const void *state, const char *prefix)
+{
+    char msg[96];
+    if (state && (uintptr_t)state % 8 == 0) return PVV_OK;
+    snprintf(msg, sizeof(msg), state ? "%s: out_state must be 8-byte aligned" : "%s: NULL device pointer", prefix);
+    return fail(PVV_E_ARG, msg);
 }
 
 template <bool KPT, bool VEC, typename MaskT>
@@ -428,19 +450,27 @@ void train_launch_backward(const TrainShape &s, const TrainArgs &a, const long l
                        (const MaskT *)a.mask, a.kpt, a.kpt_is_f64, a.target, state, go, gv, gs);
 }
 
-// f<KPT, VEC, MaskT>(args...) for the form the call has: one set of kernels, three template parameters.
-#define TRAIN_DISPATCH(f, kpt, vec, kind, ...)                                                  \
-    do {                                                                                        \
-        if (kind == PVV_MASK_U8) TRAIN_DISPATCH_2(f, kpt, vec, unsigned char, __VA_ARGS__);     \
-        else if (kind == PVV_MASK_I32) TRAIN_DISPATCH_2(f, kpt, vec, int, __VA_ARGS__);         \
-        else TRAIN_DISPATCH_2(f, kpt, vec, long long, __VA_ARGS__);                             \
+// f<KPT, VEC, MaskT>(args...), or f<VEC, MaskT>(args...) where there is no target field to choose, for the form the call has:
+// one set of kernels, the template parameters from run-time values.  kind has passed train_mask_kind.
+#define TRAIN_DISPATCH(f, kpt, vec, kind, ...) TRAIN_BY_MASK(TRAIN_KPT_VEC, kind, f, kpt, vec, __VA_ARGS__)
+#define TRAIN_DISPATCH_VEC(f, vec, kind, ...) TRAIN_BY_MASK(TRAIN_VEC, kind, f, vec, __VA_ARGS__)
+#define TRAIN_BY_MASK(FORM, kind, ...)                                       \
+    do {                                                                     \
+        if (kind == PVV_MASK_U8) FORM(unsigned char, __VA_ARGS__);           \
+        else if (kind == PVV_MASK_I32) FORM(int, __VA_ARGS__);               \
+        else FORM(long long, __VA_ARGS__);                                   \
     } while (0)
-#define TRAIN_DISPATCH_2(f, kpt, vec, T, ...)                      \
+#define TRAIN_KPT_VEC(T, f, kpt, vec, ...)                         \
     do {                                                           \
         if (kpt && vec) f<true, true, T>(__VA_ARGS__);             \
         else if (kpt) f<true, false, T>(__VA_ARGS__);              \
         else if (vec) f<false, true, T>(__VA_ARGS__);              \
         else f<false, false, T>(__VA_ARGS__);                      \
+    } while (0)
+#define TRAIN_VEC(T, f, vec, ...)                                  \
+    do {                                                           \
+        if (vec) f<true, T>(__VA_ARGS__);                          \
+        else f<false, T>(__VA_ARGS__);                             \
     } while (0)
 
 template <bool VEC, typename MaskT>
@@ -457,20 +487,9 @@ PVV_EXPORT int pvv_vertex_target(const void *d_mask, int mask_kind, const void *
     TrainShape s;
     if (int e = train_shape(s, B, K, 1, H, W)) return e;
     if (!d_mask || !d_kpt_2d || !d_out) return fail(PVV_E_ARG, "train: NULL device pointer");
-    hipStream_t st = (hipStream_t)stream;
+    if (int e = train_mask_kind(mask_kind)) return e;
     const bool vec = s.HW % 4 == 0 && train_aligned(d_mask, 0) && train_aligned(d_out, 0);
-    if (mask_kind == PVV_MASK_U8) {
-        if (vec) train_launch_target<true, unsigned char>(s, d_mask, d_kpt_2d, kpt_is_f64, d_out, st);
-        else train_launch_target<false, unsigned char>(s, d_mask, d_kpt_2d, kpt_is_f64, d_out, st);
-    } else if (mask_kind == PVV_MASK_I32) {
-        if (vec) train_launch_target<true, int>(s, d_mask, d_kpt_2d, kpt_is_f64, d_out, st);
-        else train_launch_target<false, int>(s, d_mask, d_kpt_2d, kpt_is_f64, d_out, st);
-    } else if (mask_kind == PVV_MASK_I64) {
-        if (vec) train_launch_target<true, long long>(s, d_mask, d_kpt_2d, kpt_is_f64, d_out, st);
-        else train_launch_target<false, long long>(s, d_mask, d_kpt_2d, kpt_is_f64, d_out, st);
-    } else {
-        return fail(PVV_E_ARG, "train: mask_kind must be PVV_MASK_U8, PVV_MASK_I32 or PVV_MASK_I64");
-    }
+    TRAIN_DISPATCH_VEC(train_launch_target, vec, mask_kind, s, d_mask, d_kpt_2d, kpt_is_f64, d_out, (hipStream_t)stream);
     return check_launch("k_train_vertex_target");
 }
 
@@ -491,9 +510,9 @@ PVV_EXPORT int pvv_pvnet_loss_forward(const float *d_vertex_pred, long long vp_i
     const TrainArgs a = {d_vertex_pred, d_seg_pred, d_mask, d_kpt_2d, mask_kind, kpt_is_f64, d_target};
     bool vec = false;
     if (int e = train_inputs(s, a, vp_image_stride, sp_image_stride, tg_image_stride, vec)) return e;
-    if (!d_out_losses || !d_out_state) return fail(PVV_E_ARG, "train: NULL device pointer");
-    if ((uintptr_t)d_out_state % 8 != 0) return fail(PVV_E_ARG, "train: out_state must be 8-byte aligned");
-    const TrainLayout L = train_layout(B, s.tiles);
+    if (!d_out_losses) return fail(PVV_E_ARG, "train: NULL device pointer");
+    if (int e = loss_state(d_out_state, "train")) return e;
+    const LossLayout L = train_layout(B, s.tiles);
     if (int e = train_ws(workspace, workspace_bytes, L.total)) return e;
     hipStream_t st = (hipStream_t)stream;
     unsigned char *ws = (unsigned char *)workspace;
@@ -520,8 +539,8 @@ PVV_EXPORT int pvv_pvnet_loss_backward(const float *d_vertex_pred, long long vp_
     const TrainArgs a = {d_vertex_pred, d_seg_pred, d_mask, d_kpt_2d, mask_kind, kpt_is_f64, d_target};
     bool vec = false;
     if (int e = train_inputs(s, a, vp_image_stride, sp_image_stride, tg_image_stride, vec)) return e;
-    if (!d_out_state || !d_grad_losses || !d_grad_vertex || !d_grad_seg) return fail(PVV_E_ARG, "train: NULL device pointer");
-    if ((uintptr_t)d_out_state % 8 != 0) return fail(PVV_E_ARG, "train: out_state must be 8-byte aligned");
+    if (!d_grad_losses || !d_grad_vertex || !d_grad_seg) return fail(PVV_E_ARG, "train: NULL device pointer");
+    if (int e = loss_state(d_out_state, "train")) return e;
     vec = vec && train_aligned(d_grad_vertex, 0) && train_aligned(d_grad_seg, 0);
     const bool kpt = d_kpt_2d != nullptr;
     TRAIN_DISPATCH(train_launch_backward, kpt, vec, mask_kind, s, a, (const long long *)d_out_state, d_grad_losses, d_grad_vertex, d_grad_seg,

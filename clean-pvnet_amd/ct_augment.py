@@ -28,12 +28,11 @@ import numpy as np
 from . import _native
 from ._native import INT, PTR, SIZE
 
-_lib = _native.load("ct_augment", "libpvnet_vote.so", {
-    "pvv_last_error": (ctypes.c_char_p, []),
+_lib = _native.bind("ct_augment", "libpvnet_vote.so", {
     "pvv_ct_compose": (INT, [PTR] * 5 + [INT] * 6 + [PTR] * 4),
     "pvv_ct_augment_workspace_bytes": (SIZE, [INT] * 4),
     "pvv_ct_augment": (INT, [PTR, PTR] + [INT] * 10 + [PTR, PTR, PTR, PTR, SIZE, PTR, PTR, PTR, PTR]),
-})
+}, last_error="pvv_last_error")
 
 # per sample, then (place_y, place_x) per instance
 COLUMNS = ("scale", "center_x", "center_y", "order", "alpha_0", "alpha_1", "alpha_2", "normal_0", "normal_1", "normal_2", "rot")
@@ -165,7 +164,7 @@ def host_block(d, H, W, *, train=True, input_size=(416, 512), down_ratio=4, scal
 
 
 def _call(symbol, dev, *args):
-    _native.call_named("ct_augment", _lib, symbol, dev, *args)
+    _lib.call(symbol, dev, *args)
 
 
 def _check_img(img, what):
@@ -258,10 +257,7 @@ def ct_augment(img, label, draws, *, train=True, input_size=(416, 512), down_rat
     if lb is not None:
         out["boxes"] = torch.empty(B, N, 4, dtype=torch.int32, device=dev)
     prm = _native.upload(block, dev)
-    nbytes = _lib.pvv_ct_augment_workspace_bytes(B, N, ih, iw)
-    if nbytes == 0:
-        raise ValueError("clean_pvnet_amd.ct_augment: %s" % _lib.pvv_last_error().decode())
-    ws = _native.workspace(nbytes, dev)
+    ws, _ = _lib.workspace("pvv_ct_augment_workspace_bytes", dev, B, N, ih, iw)
     _call("pvv_ct_augment", dev, im.data_ptr(), _native.ptr(lb), B, H, W, N, ih, iw, oh, ow, int(bool(train)), BOXES[boxes], prm.data_ptr(),
           mean_c, std_c, ws.data_ptr(), ws.numel(), out["orig_img"].data_ptr(), out["inp"].data_ptr(), _native.ptr(out.get("boxes")))
     for k in ("center", "scale", "trans_input", "trans_output"):

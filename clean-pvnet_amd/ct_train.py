@@ -10,46 +10,24 @@ once.  Radii, indices and boxes equal the reference's bit for bit, the wh gradie
 sum is binary64 in a fixed order (tests/ct_train_twin.py is the contract in numpy, tests/golden/ct_train_*.npz the reference's own
 results).  CUDA float32 tensors, the current stream, nothing read back, no CPU fallback.
 """
-import ctypes
-
 import torch
 from torch import nn
-from torch.autograd.function import once_differentiable
 
 from . import _native
+from ._loss import FusedLoss
 from ._native import INT, LONGLONG, PTR, SIZE
-from .train import _per_image
 
 MAX_N = 512                          # PVV_CT_TRAIN_MAX_N
 BOX_KINDS = {torch.float32: 0, torch.int32: 1, torch.int64: 2}        # PVV_BOX_F32, PVV_BOX_I32, PVV_BOX_I64
 _INTS = (torch.int32, torch.int64)
 
 _INPUTS = [PTR, LONGLONG, PTR, LONGLONG, PTR, LONGLONG, PTR, PTR, INT, PTR] + [INT] * 5
-_lib = _native.load("ct_train", "libpvnet_vote.so", {
-    "pvv_last_error": (ctypes.c_char_p, []),
+_lib = _native.bind("ct_train", "libpvnet_vote.so", {
     "pvv_ct_targets": (INT, [PTR, INT, PTR, INT, PTR, INT] + [INT] * 5 + [PTR] * 7),
     "pvv_ct_loss_workspace_bytes": (SIZE, [INT] * 4),
     "pvv_ct_loss_forward": (INT, _INPUTS + [PTR, SIZE, PTR, PTR, PTR]),
     "pvv_ct_loss_backward": (INT, _INPUTS + [PTR, PTR, PTR, PTR, PTR]),
-})
-
-
-def _call(symbol, dev, *args):
-    try:
-        _native.call(_lib, symbol, dev, *args)
-    except RuntimeError as e:
-        raise RuntimeError("clean_pvnet_amd.ct_train: %s: %s" % (e, _lib.pvv_last_error().decode())) from None
-
-
-def _check(named, dtypes):
-    """Device, then dtype, of every tensor; shapes come after."""
-    for what, t in named:
-        _native.need_cuda(t, what, "ct_train")
-    for what, t in named:
-        allowed = dtypes[what]
-        if t.dtype not in allowed:
-            raise RuntimeError("clean_pvnet_amd.ct_train: %s must be %s, got %s"
-                               % (what, " or ".join(str(d).replace("torch.", "") for d in allowed), t.dtype))
+}, last_error="pvv_last_error")
 
 
 def ct_targets(boxes, cls, num, num_classes, height, width):
@@ -66,7 +44,7 @@ def ct_targets(boxes, cls, num, num_classes, height, width):
     to the batch's largest ``ct_num``; that number lives on the device, so the width here is N.  Both losses are unchanged by
     the zero-weight padding: a padded row has ``ct_01 == 0``, so it adds +0 to the wh sum and to its divisor, and the heat map
     does not know the rows."""
-    _check([("boxes", boxes), ("cls", cls), ("num", num)], {"boxes": tuple(BOX_KINDS), "cls": _INTS, "num": _INTS})
+    _native.check_tensors([("boxes", boxes), ("cls", cls), ("num", num)], {"boxes": tuple(BOX_KINDS), "cls": _INTS, "num": _INTS}, "ct_train")
     if boxes.dim() != 3 or boxes.shape[2] != 4:
         raise ValueError("clean_pvnet_amd.ct_train: boxes must be [B, N, 4], got %s" % (tuple(boxes.shape),))
     B, N = boxes.shape[:2]
@@ -86,9 +64,9 @@ def ct_targets(boxes, cls, num, num_classes, height, width):
     ct_ind = torch.empty(B, N, dtype=torch.int64, device=dev)
     ct_01 = torch.empty(B, N, dtype=torch.float32, device=dev)
     ct_num = torch.empty(B, dtype=torch.int64, device=dev)
-    _call("pvv_ct_targets", dev, bx.data_ptr(), BOX_KINDS[bx.dtype], cl.data_ptr(), int(cl.dtype == torch.int64), nm.data_ptr(),
-          int(nm.dtype == torch.int64), B, N, C, H, W, ct_hm.data_ptr(), wh.data_ptr(), ct_cls.data_ptr(), ct_ind.data_ptr(),
-          ct_01.data_ptr(), ct_num.data_ptr())
+    _lib.call("pvv_ct_targets", dev, bx.data_ptr(), BOX_KINDS[bx.dtype], cl.data_ptr(), int(cl.dtype == torch.int64), nm.data_ptr(),
+              int(nm.dtype == torch.int64), B, N, C, H, W, ct_hm.data_ptr(), wh.data_ptr(), ct_cls.data_ptr(), ct_ind.data_ptr(),
+              ct_01.data_ptr(), ct_num.data_ptr())
     return ct_hm, wh, ct_cls, ct_ind, ct_01, ct_num
 
 
@@ -96,7 +74,7 @@ def _problem(ct_hm_pred, wh_pred, ct_hm, wh, ct_ind, ct_01):
     """The checked arguments of both entry points: (tensors kept alive, the leading ctypes arguments, sizes)."""
     named = [("ct_hm_pred", ct_hm_pred), ("wh_pred", wh_pred), ("ct_hm", ct_hm), ("wh", wh), ("ct_ind", ct_ind), ("ct_01", ct_01)]
     f32 = (torch.float32,)
-    _check(named, {"ct_hm_pred": f32, "wh_pred": f32, "ct_hm": f32, "wh": f32, "ct_ind": _INTS, "ct_01": f32})
+    _native.check_tensors(named, {"ct_hm_pred": f32, "wh_pred": f32, "ct_hm": f32, "wh": f32, "ct_ind": _INTS, "ct_01": f32}, "ct_train")
     for what, t in named[2:]:
         if t.requires_grad:
             raise RuntimeError("clean_pvnet_amd.ct_train: %s requires grad; gradients go to ct_hm_pred and wh_pred only" % what)
@@ -117,43 +95,21 @@ def _problem(ct_hm_pred, wh_pred, ct_hm, wh, ct_ind, ct_01):
         raise ValueError("clean_pvnet_amd.ct_train: N must lie in [1, %d], got %d" % (MAX_N, N))
     if B == 0 or C * H * W == 0:
         raise ValueError("clean_pvnet_amd.ct_train: an empty batch has no loss")
-    hp, hp_stride = _per_image(ct_hm_pred.detach(), "ct_hm_pred", C, H, W)
-    wp, wp_stride = _per_image(wh_pred.detach(), "wh_pred", 2, H, W)
-    hm, hm_stride = _per_image(ct_hm, "ct_hm", C, H, W)
+    hp, hp_stride = _native.per_image(ct_hm_pred.detach(), "ct_hm_pred", C, H, W)
+    wp, wp_stride = _native.per_image(wh_pred.detach(), "wh_pred", 2, H, W)
+    hm, hm_stride = _native.per_image(ct_hm, "ct_hm", C, H, W)
     tg, ind, w01 = wh.contiguous(), ct_ind.contiguous(), ct_01.contiguous()
     args = (hp.data_ptr(), hp_stride, wp.data_ptr(), wp_stride, hm.data_ptr(), hm_stride, tg.data_ptr(), ind.data_ptr(),
             int(ind.dtype == torch.int64), w01.data_ptr(), B, N, C, H, W)
     return (hp, wp, hm, tg, ind, w01), args, (B, N, C, H, W)
 
 
-class _CtLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, ct_hm_pred, wh_pred, ct_hm, wh, ct_ind, ct_01):
-        keep, args, (B, N, C, H, W) = _problem(ct_hm_pred, wh_pred, ct_hm, wh, ct_ind, ct_01)
-        dev = ct_hm_pred.device
-        nbytes = _lib.pvv_ct_loss_workspace_bytes(B, C, H, W)
-        if nbytes == 0:
-            raise ValueError("clean_pvnet_amd.ct_train: %s" % _lib.pvv_last_error().decode())
-        ws = _native.workspace(nbytes, dev)
-        losses = torch.empty(2, dtype=torch.float32, device=dev)
-        state = torch.empty(4, dtype=torch.int64, device=dev)
-        _call("pvv_ct_loss_forward", dev, *args, ws.data_ptr(), nbytes, losses.data_ptr(), state.data_ptr())
-        ctx.keep, ctx.args, ctx.sizes, ctx.state = keep, args, (B, N, C, H, W), state
-        return losses[0], losses[1]
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, go_ct, go_wh):
-        B, N, C, H, W = ctx.sizes
-        dev = ctx.state.device
-        zero = None
-        if go_ct is None or go_wh is None:                         # an unused loss: its upstream gradient counts as zero
-            zero = torch.zeros((), dtype=torch.float32, device=dev)
-        go = torch.stack([zero if go_ct is None else go_ct.to(torch.float32), zero if go_wh is None else go_wh.to(torch.float32)])
-        grad_hm = torch.empty(B, C, H, W, dtype=torch.float32, device=dev)
-        grad_wh = torch.empty(B, 2, H, W, dtype=torch.float32, device=dev)
-        _call("pvv_ct_loss_backward", dev, *ctx.args, ctx.state.data_ptr(), go.data_ptr(), grad_hm.data_ptr(), grad_wh.data_ptr())
-        return grad_hm, grad_wh, None, None, None, None
+class _CtLoss(FusedLoss):
+    lib, workspace_query, state_len = _lib, "pvv_ct_loss_workspace_bytes", 4
+    forward_symbol, backward_symbol = "pvv_ct_loss_forward", "pvv_ct_loss_backward"
+    problem = staticmethod(lambda *inputs: _problem(*inputs))
+    workspace_sizes = staticmethod(lambda B, N, C, H, W: (B, C, H, W))
+    grad_shapes = staticmethod(lambda B, N, C, H, W: ((B, C, H, W), (B, 2, H, W)))
 
 
 def ct_loss(ct_hm_pred, wh_pred, ct_hm, wh, ct_ind, ct_01):

@@ -9,7 +9,6 @@ are sampled into LDS and never written out.  The result equals the numpy twin (t
 parity with the reference's compiled kernels is unpinned.  Forward only: inference, as ``ct_pvnet`` runs
 the detector (lib/networks/ct_pvnet/res.py:71).  CUDA float32 tensors, the current stream, nothing read back, no CPU fallback.
 """
-import ctypes
 import math
 
 import torch
@@ -18,11 +17,10 @@ from torch import nn
 from . import _native
 from ._native import INT, LONGLONG, PTR
 
-_lib = _native.load("dcn", "libpvnet_vote.so", {
-    "pvv_last_error": (ctypes.c_char_p, []),
+_lib = _native.bind("dcn", "libpvnet_vote.so", {
     "pvv_dcn_forward": (INT, [PTR, PTR, PTR, PTR, LONGLONG, PTR, LONGLONG] + [INT] * 14 + [PTR, PTR]),
     "pvv_dcn_columns": (INT, [PTR, PTR, LONGLONG, PTR, LONGLONG] + [INT] * 13 + [PTR, PTR]),
-})
+}, last_error="pvv_last_error")
 
 MAX_COLUMNS = 1 << 28              # elements ``columns`` agrees to write
 
@@ -39,25 +37,10 @@ def _out_size(n, k, s, p, d):
 
 
 def _check(named, forward_only=True):
-    for what, t in named:
-        _native.need_cuda(t, what, "dcn")
-    for what, t in named:
-        if t.dtype != torch.float32:
-            raise RuntimeError("clean_pvnet_amd.dcn: %s must be float32, got %s" % (what, t.dtype))
+    _native.check_tensors(named, (torch.float32,), "dcn")
     if forward_only and torch.is_grad_enabled() and any(t.requires_grad for _, t in named):
         raise RuntimeError("clean_pvnet_amd.dcn: forward only -- there is no backward pass; call under torch.no_grad() "
                            "or with tensors that do not require grad")
-
-
-def _per_image(t, what, channels, Ho, Wo):
-    """``t`` [B, channels, Ho, Wo] as (tensor, element stride between images): a view whose images are contiguous is taken as
-    it is, by its stride."""
-    if t.dim() != 4 or tuple(t.shape[1:]) != (channels, Ho, Wo):
-        raise RuntimeError("clean_pvnet_amd.dcn: %s must be [B, %d, %d, %d], got %s" % (what, channels, Ho, Wo, tuple(t.shape)))
-    image = channels * Ho * Wo
-    if not t[:1].is_contiguous() or (t.shape[0] > 1 and t.stride(0) < image):
-        t = t.contiguous()
-    return t, (t.stride(0) if t.shape[0] > 1 else image)
 
 
 def _problem(input, offset, mask, kernel, stride, padding, dilation, dg):
@@ -69,8 +52,8 @@ def _problem(input, offset, mask, kernel, stride, padding, dilation, dg):
     Ho, Wo = _out_size(H, kh, sh, ph, dh), _out_size(W, kw, sw, pw, dw)
     if offset.shape[0] != B or mask.shape[0] != B:
         raise RuntimeError("clean_pvnet_amd.dcn: input, offset and mask differ in batch size")
-    off, off_stride = _per_image(offset, "offset", 2 * dg * kh * kw, Ho, Wo)
-    msk, msk_stride = _per_image(mask, "mask", dg * kh * kw, Ho, Wo)
+    off, off_stride = _native.per_image(offset, "offset", 2 * dg * kh * kw, Ho, Wo, module="dcn")
+    msk, msk_stride = _native.per_image(mask, "mask", dg * kh * kw, Ho, Wo, module="dcn")
     return (B, C, H, W, Ho, Wo), off, off_stride, msk, msk_stride, (kh, kw, sh, sw, ph, pw, dh, dw, dg)
 
 
@@ -98,11 +81,8 @@ def dcn_v2_conv(input, offset, mask, weight, bias, stride, padding, dilation, de
     out = torch.empty(B, M, max(Ho, 0), max(Wo, 0), dtype=torch.float32, device=x.device)
     if B == 0 or M == 0:
         return out
-    try:
-        _native.call(_lib, "pvv_dcn_forward", x.device, x.data_ptr(), wt.data_ptr(), _native.ptr(bs), off.data_ptr(), off_stride,
-                     msk.data_ptr(), msk_stride, B, C, H, W, M, *geo, out.data_ptr())
-    except RuntimeError as e:
-        raise RuntimeError("clean_pvnet_amd.dcn: %s: %s" % (e, _lib.pvv_last_error().decode())) from None
+    _lib.call("pvv_dcn_forward", x.device, x.data_ptr(), wt.data_ptr(), _native.ptr(bs), off.data_ptr(), off_stride,
+              msk.data_ptr(), msk_stride, B, C, H, W, M, *geo, out.data_ptr())
     return out
 
 
@@ -120,11 +100,8 @@ def columns(input, offset, mask, kernel_size, stride, padding, dilation, deforma
     col = torch.empty(B, K, P, dtype=torch.float32, device=x.device)
     if col.numel() == 0:
         return col
-    try:
-        _native.call(_lib, "pvv_dcn_columns", x.device, x.data_ptr(), off.data_ptr(), off_stride, msk.data_ptr(), msk_stride,
-                     B, C, H, W, *geo, col.data_ptr())
-    except RuntimeError as e:
-        raise RuntimeError("clean_pvnet_amd.dcn: %s: %s" % (e, _lib.pvv_last_error().decode())) from None
+    _lib.call("pvv_dcn_columns", x.device, x.data_ptr(), off.data_ptr(), off_stride, msk.data_ptr(), msk_stride,
+              B, C, H, W, *geo, col.data_ptr())
     return col
 
 

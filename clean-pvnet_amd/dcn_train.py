@@ -11,19 +11,16 @@ reference checkpoint loads unchanged; ``convert`` swaps them into a model.  ``cl
 ``lib.csrc.dcn_v2._ext`` keep refusing a backward pass: they are the inference surface, and this module is the training one.
 CUDA float32 tensors, the current stream, nothing read back, no CPU fallback, no silent cast.
 """
-import ctypes
-
 import torch
 from torch.autograd.function import once_differentiable
 
 from . import _native, dcn
 from ._native import INT, LONGLONG, PTR, SIZE
 
-_lib = _native.load("dcn_train", "libpvnet_vote.so", {
-    "pvv_last_error": (ctypes.c_char_p, []),
+_lib = _native.bind("dcn_train", "libpvnet_vote.so", {
     "pvv_dcn_backward_workspace_bytes": (LONGLONG, [INT] * 15),
     "pvv_dcn_backward": (INT, [PTR, PTR, PTR, LONGLONG, PTR, LONGLONG, PTR] + [INT] * 14 + [PTR] * 6 + [SIZE, PTR]),
-})
+}, last_error="pvv_last_error")
 
 SLAB = 512                         # PVV_DCN_SLAB: pixels of one grad_weight chain
 
@@ -46,15 +43,10 @@ def _backward(input, offset, mask, weight, grad_output, stride, padding, dilatio
         return tuple(grads)
     if B == 0 or M == 0 or Ho <= 0 or Wo <= 0:
         return tuple(None if g is None else g.zero_() for g in grads)
-    nbytes = _lib.pvv_dcn_backward_workspace_bytes(B, C, H, W, M, *geo, 0 if chunk_images is None else int(chunk_images))
-    if nbytes < 0:
-        raise RuntimeError("clean_pvnet_amd.dcn_train: %s" % _lib.pvv_last_error().decode())
-    ws = _native.workspace(nbytes, x.device)
-    try:
-        _native.call(_lib, "pvv_dcn_backward", x.device, x.data_ptr(), wt.data_ptr(), off.data_ptr(), off_stride, msk.data_ptr(),
-                     msk_stride, go.data_ptr(), B, C, H, W, M, *geo, *(_native.ptr(g) for g in grads), ws.data_ptr(), nbytes)
-    except RuntimeError as e:
-        raise RuntimeError("clean_pvnet_amd.dcn_train: %s: %s" % (e, _lib.pvv_last_error().decode())) from None
+    ws, nbytes = _lib.workspace("pvv_dcn_backward_workspace_bytes", x.device, B, C, H, W, M, *geo,
+                                0 if chunk_images is None else int(chunk_images), refused=lambda n: n < 0, error=RuntimeError)
+    _lib.call("pvv_dcn_backward", x.device, x.data_ptr(), wt.data_ptr(), off.data_ptr(), off_stride, msk.data_ptr(),
+              msk_stride, go.data_ptr(), B, C, H, W, M, *geo, *(_native.ptr(g) for g in grads), ws.data_ptr(), nbytes)
     return tuple(grads)
 
 

@@ -21,14 +21,13 @@ from . import _native
 from ._native import INT, LONGLONG, PTR, SIZE
 from .ct_augment import affine, invert_affine
 
-_lib = _native.load("det_eval", "libpvnet_vote.so", {
-    "pvv_last_error": (ctypes.c_char_p, []),
+_lib = _native.bind("det_eval", "libpvnet_vote.so", {
     "pvv_det_box_iou": (INT, [PTR, INT, PTR, PTR, INT, PTR, PTR]),
     "pvv_det_map": (INT, [PTR, PTR, PTR, INT, INT, INT, ctypes.c_float, PTR, PTR, PTR, PTR, PTR, PTR, PTR]),
     "pvv_det_match": (INT, [PTR, PTR, PTR, PTR, PTR, INT, PTR, INT, INT, PTR, PTR, PTR, PTR, INT, INT, PTR, PTR, PTR, PTR, PTR, PTR]),
     "pvv_det_accumulate_workspace_bytes": (SIZE, [LONGLONG]),
     "pvv_det_accumulate": (INT, [PTR, PTR, PTR, LONGLONG, PTR, INT, PTR, PTR, PTR, SIZE, PTR, PTR, PTR, PTR]),
-})
+}, last_error="pvv_last_error", prefix="det_eval", plain_calls=True)
 
 T, R, A, M = 10, 101, 4, 3         # PVV_DET_T, _R, _A, _M
 MAX_K = 128                        # PVV_DET_MAX_K
@@ -149,7 +148,7 @@ def box_iou(dt, gt, iscrowd):
     assert tuple(dt.shape) == (D, 4) and tuple(gt.shape) == (G, 4) and tuple(iscrowd.shape) == (G,), (dt.shape, gt.shape, iscrowd.shape)
     d, g, c = dt.contiguous(), gt.contiguous(), (iscrowd != 0).to(torch.int32).contiguous()
     out = torch.empty(D, G, dtype=torch.float64, device=dt.device)
-    _native.call(_lib, "pvv_det_box_iou", dt.device, d.data_ptr(), D, g.data_ptr(), c.data_ptr(), G, out.data_ptr())
+    _lib.call("pvv_det_box_iou", dt.device, d.data_ptr(), D, g.data_ptr(), c.data_ptr(), G, out.data_ptr())
     return out
 
 
@@ -162,9 +161,9 @@ def map_detections(detection, block, label_to_cat, down_ratio, err):
     out = {"box": torch.empty(B * K, 4, dtype=torch.float64, device=dev), "score": torch.empty(B * K, dtype=torch.float64, device=dev),
            "area": torch.empty(B * K, dtype=torch.float64, device=dev), "n": torch.empty(B * K, dtype=torch.int32, device=dev),
            "cat": torch.empty(B * K, dtype=torch.int32, device=dev)}
-    _native.call(_lib, "pvv_det_map", dev, detection.data_ptr(), block.data_ptr(), label_to_cat.data_ptr(), label_to_cat.numel(), B, K,
-                 float(down_ratio), out["box"].data_ptr(), out["score"].data_ptr(), out["area"].data_ptr(), out["n"].data_ptr(),
-                 out["cat"].data_ptr(), err.data_ptr())
+    _lib.call("pvv_det_map", dev, detection.data_ptr(), block.data_ptr(), label_to_cat.data_ptr(), label_to_cat.numel(), B, K,
+              float(down_ratio), out["box"].data_ptr(), out["score"].data_ptr(), out["area"].data_ptr(), out["n"].data_ptr(),
+              out["cat"].data_ptr(), err.data_ptr())
     return out
 
 
@@ -175,11 +174,11 @@ def match_detections(mapped, num, block, gt_dev, B, K, tables, npig):
     dev = block.device
     keys = torch.empty(B * K, dtype=torch.int64, device=dev)
     words = torch.empty(B * K, A, dtype=torch.int32, device=dev)
-    _native.call(_lib, "pvv_det_match", dev, mapped["box"].data_ptr(), mapped["area"].data_ptr(), mapped["n"].data_ptr(),
-                 mapped["cat"].data_ptr(), _native.ptr(num), int(num is not None and num.dtype == torch.int64), block.data_ptr(), B, K,
-                 gt_dev["box"].data_ptr(), gt_dev["area"].data_ptr(), gt_dev["crowd"].data_ptr(), gt_dev["off"].data_ptr(),
-                 gt_dev["I"], gt_dev["C"], tables["iou"].data_ptr(), tables["area"].data_ptr(), keys.data_ptr(), words.data_ptr(),
-                 npig.data_ptr())
+    _lib.call("pvv_det_match", dev, mapped["box"].data_ptr(), mapped["area"].data_ptr(), mapped["n"].data_ptr(),
+              mapped["cat"].data_ptr(), _native.ptr(num), int(num is not None and num.dtype == torch.int64), block.data_ptr(), B, K,
+              gt_dev["box"].data_ptr(), gt_dev["area"].data_ptr(), gt_dev["crowd"].data_ptr(), gt_dev["off"].data_ptr(),
+              gt_dev["I"], gt_dev["C"], tables["iou"].data_ptr(), tables["area"].data_ptr(), keys.data_ptr(), words.data_ptr(),
+              npig.data_ptr())
     return keys, words
 
 
@@ -188,13 +187,10 @@ def accumulate(keys_sorted, perm, words, npig, C, rec_thrs, precision, recall, s
     (float64 device tensors the caller has filled with -1)."""
     N = keys_sorted.numel()
     dev = npig.device
-    nbytes = _lib.pvv_det_accumulate_workspace_bytes(N)
-    if N and nbytes == 0:
-        raise ValueError("det_eval: %s" % _lib.pvv_last_error().decode())
-    ws = _native.workspace(nbytes, dev)
+    ws, _ = _lib.workspace("pvv_det_accumulate_workspace_bytes", dev, N, refused=lambda nbytes: N and nbytes == 0)
     caps = (ctypes.c_int32 * M)(*MAX_DETS)
-    _native.call(_lib, "pvv_det_accumulate", dev, keys_sorted.data_ptr(), perm.data_ptr(), words.data_ptr(), N, npig.data_ptr(), C,
-                 rec_thrs.data_ptr(), caps, ws.data_ptr(), ws.numel(), precision.data_ptr(), recall.data_ptr(), scores.data_ptr())
+    _lib.call("pvv_det_accumulate", dev, keys_sorted.data_ptr(), perm.data_ptr(), words.data_ptr(), N, npig.data_ptr(), C,
+              rec_thrs.data_ptr(), caps, ws.data_ptr(), ws.numel(), precision.data_ptr(), recall.data_ptr(), scores.data_ptr())
 
 
 class DetEvaluator:
@@ -221,7 +217,7 @@ class DetEvaluator:
         self._keys, self._words = [], []
         self.last = None
 
-    def _upload(self, dev):
+    def _put_gt(self, dev):
         import torch
         g = self._gt
         put = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)   # noqa: E731
@@ -268,7 +264,7 @@ class DetEvaluator:
             return
         dev = detection.device
         if self._dev is None:
-            self._upload(dev)
+            self._put_gt(dev)
         block = np.zeros((B, 8), np.float64)
         for b in range(B):
             block[b, :6] = inverse_transform(center[b], scale[b], inp_hw)

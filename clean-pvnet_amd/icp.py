@@ -14,7 +14,7 @@ from . import _native
 from . import vsd as _vsd
 from ._native import DOUBLE, INT, PTR, SIZE
 
-_lib = _native.load("icp", "libpvnet_icp.so", {
+_lib = _native.bind("icp", "libpvnet_icp.so", {
     "pvi_workspace_bytes": (SIZE, [INT] * 4),
     "pvi_refine_batched": (INT, [PTR, PTR, INT, DOUBLE, INT, PTR, INT, INT, INT, PTR, PTR, INT, PTR, PTR, PTR, INT, DOUBLE, INT,
                                  INT, DOUBLE, DOUBLE, PTR, PTR, PTR, INT, INT, INT, PTR]),
@@ -93,12 +93,12 @@ def refine(depth, pose, K, pts, faces, *, mask=None, depth_only=False, no_depth=
     info = torch.empty(P, len(INFO), dtype=torch.int32, device=dev)
     if P:
         flags = (1 if depth_only else 0) | (2 if no_depth else 0)
-        ws = _native.workspace(_lib.pvi_workspace_bytes(P, H, W, n_max), dev)
-        _native.call(_lib, "pvi_refine_batched", dev, render.data_ptr(), dt.data_ptr(), kind, float(depth_scale), P // dt.shape[0],
-                     _native.ptr(m), mkind, per_mask, int(min_mask_pixels), ps.data_ptr(), Km.data_ptr(), int(Km.dim() == 3),
-                     _native.ptr(idx_syn), _native.ptr(idx_real), _native.ptr(words), flags, float(max_mean_dist_factor), n_max,
-                     max_iterations, float(tolerance), math.cos(float(angle_limit_deg) * math.pi / 180.), out.data_ptr(),
-                     info.data_ptr(), ws.data_ptr(), P, H, W)
+        ws, _ = _lib.workspace("pvi_workspace_bytes", dev, P, H, W, n_max)
+        _lib.call("pvi_refine_batched", dev, render.data_ptr(), dt.data_ptr(), kind, float(depth_scale), P // dt.shape[0],
+                  _native.ptr(m), mkind, per_mask, int(min_mask_pixels), ps.data_ptr(), Km.data_ptr(), int(Km.dim() == 3),
+                  _native.ptr(idx_syn), _native.ptr(idx_real), _native.ptr(words), flags, float(max_mean_dist_factor), n_max,
+                  max_iterations, float(tolerance), math.cos(float(angle_limit_deg) * math.pi / 180.), out.data_ptr(),
+                  info.data_ptr(), ws.data_ptr(), P, H, W)
     if return_info:
         return out, {k: info[:, i] for i, k in enumerate(INFO)}
     return out

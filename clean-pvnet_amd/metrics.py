@@ -11,7 +11,7 @@ the reference's hit counts on the device and reads back once, in ``summarize()``
 from . import _native
 from ._native import INT, LONGLONG, PTR, SIZE
 
-_lib = _native.load("metrics", "libpvnet_metrics.so", {
+_lib = _native.bind("metrics", "libpvnet_metrics.so", {
     "pvm_adds_slabs": (INT, [INT] * 2),
     "pvm_workspace_bytes": (SIZE, [INT] * 3),
     "pvm_pose_metrics_batched": (INT, [PTR] * 8 + [INT] * 4 + [PTR]),
@@ -60,9 +60,9 @@ def pose_metrics(pose_pred, pose_gt, model, K, *, symmetric=False, return_idx=Fa
     metrics = torch.empty(b, 5, dtype=torch.float64, device=dev)
     idx = torch.empty(b, n, dtype=torch.int32, device=dev) if return_idx else None
     if b:
-        ws = _native.workspace(_lib.pvm_workspace_bytes(b, n, int(slabs)), dev)
-        _native.call(_lib, "pvm_pose_metrics_batched", dev, pp.data_ptr(), pg.data_ptr(), md.data_ptr(), Km.data_ptr(),
-                     _native.ptr(sym), metrics.data_ptr(), _native.ptr(idx), ws.data_ptr(), b, n, int(Km.dim() == 3), int(slabs))
+        ws, _ = _lib.workspace("pvm_workspace_bytes", dev, b, n, int(slabs))
+        _lib.call("pvm_pose_metrics_batched", dev, pp.data_ptr(), pg.data_ptr(), md.data_ptr(), Km.data_ptr(),
+                  _native.ptr(sym), metrics.data_ptr(), _native.ptr(idx), ws.data_ptr(), b, n, int(Km.dim() == 3), int(slabs))
     out = {k: metrics[:, i] for i, k in enumerate(COLUMNS)}
     if return_idx:
         out["adds_idx"] = idx
@@ -99,8 +99,7 @@ def mask_counts(mask_pred, mask_gt):
     inter = torch.empty(b, dtype=torch.int64, device=dev)
     union = torch.empty(b, dtype=torch.int64, device=dev)
     if b:
-        _native.call(_lib, "pvm_mask_iou_batched", dev, mp.data_ptr(), mg.data_ptr(), sp, sg, ep, eg, inter.data_ptr(),
-                     union.data_ptr(), b, h, w)
+        _lib.call("pvm_mask_iou_batched", dev, mp.data_ptr(), mg.data_ptr(), sp, sg, ep, eg, inter.data_ptr(), union.data_ptr(), b, h, w)
     return inter, union
 
 

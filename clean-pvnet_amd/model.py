@@ -8,7 +8,6 @@ kernels: the indices equal the reference's ``farthest_point_sampling.cpp`` and t
 bit (the numpy twin is tests/model_twin.py, the reference's own results are tests/golden/model_*.npz).  ``lib/csrc/fps/fps_utils.py``
 is the reference's import path on top of this module.  CUDA tensors, the current stream, nothing read back, no CPU fallback.
 """
-import ctypes
 import numbers
 import random
 
@@ -22,21 +21,18 @@ ONE_BLOCK_MAX = 8192                 # PVV_FPS_ONE_BLOCK_MAX
 TILE = 1024                          # PVV_MODEL_TILE
 MAX_N = 1 << 20                      # PVV_MODEL_MAX_N
 
-_lib = _native.load("model", "libpvnet_vote.so", {
-    "pvv_last_error": (ctypes.c_char_p, []),
+_lib = _native.bind("model", "libpvnet_vote.so", {
     "pvv_fps_workspace_bytes": (SIZE, [INT] * 4),
     "pvv_fps": (INT, [PTR, PTR, PTR, INT, INT, INT, INT, PTR, SIZE, PTR, PTR]),
     "pvv_model_workspace_bytes": (SIZE, [INT] * 2),
     "pvv_model_bounds": (INT, [PTR, INT, PTR, INT, INT, PTR, SIZE, PTR, PTR, PTR]),
     "pvv_model_diameter": (INT, [PTR, INT, PTR, INT, INT, PTR, SIZE, PTR, PTR]),
-})
+}, last_error="pvv_last_error")
 
 
 def _clouds(points, dtypes):
     """``points`` as a contiguous [B, N, 3] tensor and whether it came as [N, 3]."""
-    _native.need_cuda(points, "points", "model")
-    if points.dtype not in dtypes:
-        raise RuntimeError("clean_pvnet_amd.model: points must be %s, got %s" % (" or ".join(str(d) for d in dtypes), points.dtype))
+    _native.check_tensors([("points", points)], dtypes, "model", {"points": " or ".join(str(d) for d in dtypes)})
     single = points.dim() == 2
     p = points[None] if single else points
     if p.dim() != 3 or p.shape[2] != 3 or p.shape[0] < 1 or p.shape[1] < 1:
@@ -56,20 +52,6 @@ def _lengths(n, B, N, dev):
     if any(v < 1 or v > N for v in n):
         raise ValueError("clean_pvnet_amd.model: every entry of n must lie in [1, N = %d], got %s" % (N, n))
     return n, torch.tensor(n, dtype=torch.int32, device=dev)
-
-
-def _call(symbol, dev, *args):
-    try:
-        _native.call(_lib, symbol, dev, *args)
-    except RuntimeError as e:
-        raise RuntimeError("clean_pvnet_amd.model: %s: %s" % (e, _lib.pvv_last_error().decode())) from None
-
-
-def _workspace(query, dev, *sizes):
-    nbytes = query(*sizes)
-    if nbytes == 0:
-        raise ValueError("clean_pvnet_amd.model: %s" % _lib.pvv_last_error().decode())
-    return _native.workspace(nbytes, dev), nbytes
 
 
 def farthest_point_sampling(points, sn, init_center=True, start=None, n=None, path=AUTO):
@@ -106,9 +88,9 @@ def farthest_point_sampling(points, sn, init_center=True, start=None, n=None, pa
         if any(s < 0 or s >= v for s, v in zip(start, lens)):
             raise ValueError("clean_pvnet_amd.model: every start must lie in [0, n_b), got %s for lengths %s" % (start, lens))
         d_start = torch.tensor(start, dtype=torch.int32, device=p.device)
-    ws, nbytes = _workspace(_lib.pvv_fps_workspace_bytes, p.device, B, N, sn, path)
+    ws, nbytes = _lib.workspace("pvv_fps_workspace_bytes", p.device, B, N, sn, path)
     idx = torch.empty(B, sn, dtype=torch.int32, device=p.device)
-    _call("pvv_fps", p.device, p.data_ptr(), _native.ptr(d_n), _native.ptr(d_start), B, N, sn, path, ws.data_ptr(), nbytes, idx.data_ptr())
+    _lib.call("pvv_fps", p.device, p.data_ptr(), _native.ptr(d_n), _native.ptr(d_start), B, N, sn, path, ws.data_ptr(), nbytes, idx.data_ptr())
     return idx[0] if single else idx
 
 
@@ -117,10 +99,10 @@ def bounds(points, n=None):
     p, _ = _clouds(points, (torch.float32, torch.float64))
     B, N = p.shape[0], p.shape[1]
     _, d_n = _lengths(n, B, N, p.device)
-    ws, nbytes = _workspace(_lib.pvv_model_workspace_bytes, p.device, B, N)
+    ws, nbytes = _lib.workspace("pvv_model_workspace_bytes", p.device, B, N)
     lo, hi = torch.empty(B, 3, dtype=p.dtype, device=p.device), torch.empty(B, 3, dtype=p.dtype, device=p.device)
-    _call("pvv_model_bounds", p.device, p.data_ptr(), int(p.dtype == torch.float64), _native.ptr(d_n), B, N, ws.data_ptr(), nbytes,
-          lo.data_ptr(), hi.data_ptr())
+    _lib.call("pvv_model_bounds", p.device, p.data_ptr(), int(p.dtype == torch.float64), _native.ptr(d_n), B, N, ws.data_ptr(), nbytes,
+              lo.data_ptr(), hi.data_ptr())
     return lo, hi
 
 
@@ -148,10 +130,10 @@ def diameter(points, n=None):
     p, _ = _clouds(points, (torch.float32, torch.float64))
     B, N = p.shape[0], p.shape[1]
     _, d_n = _lengths(n, B, N, p.device)
-    ws, nbytes = _workspace(_lib.pvv_model_workspace_bytes, p.device, B, N)
+    ws, nbytes = _lib.workspace("pvv_model_workspace_bytes", p.device, B, N)
     out = torch.empty(B, dtype=torch.float64, device=p.device)
-    _call("pvv_model_diameter", p.device, p.data_ptr(), int(p.dtype == torch.float64), _native.ptr(d_n), B, N, ws.data_ptr(), nbytes,
-          out.data_ptr())
+    _lib.call("pvv_model_diameter", p.device, p.data_ptr(), int(p.dtype == torch.float64), _native.ptr(d_n), B, N, ws.data_ptr(), nbytes,
+              out.data_ptr())
     return out
 
 

@@ -6,9 +6,9 @@ arguments (numpy arrays on the host) and return value as the reference; there is
 """
 import numpy as np
 
-from ._native import INT, PTR, load
+from ._native import INT, PTR, bind
 
-_lib = load("nn_utils", "libpvnet_nn.so", {"findNearestPointIdxLauncher": (None, [PTR] * 3 + [INT] * 5)})
+_lib = bind("nn_utils", "libpvnet_nn.so", {"findNearestPointIdxLauncher": (None, [PTR] * 3 + [INT] * 5)})
 
 
 def find_nearest_point_idx(ref_pts, que_pts):

@@ -31,11 +31,10 @@ ROW = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("numel"
                 ("s", "<f4", (8,))])             # pvv_optim_row
 assert ROW.itemsize == 80
 
-_lib = _native.load("optim", "libpvnet_vote.so", {
-    "pvv_last_error": (ctypes.c_char_p, []),
+_lib = _native.bind("optim", "libpvnet_vote.so", {
     "pvv_optim_chunk": (INT, []),
     "pvv_optim_step": (INT, [INT, PTR, PTR, INT, LONGLONG, ctypes.c_float, INT, PTR]),
-})
+}, last_error="pvv_last_error")
 if _lib.pvv_optim_chunk() != CHUNK:
     raise ImportError("clean_pvnet_amd.optim: libpvnet_vote.so was built with PVV_OPTIM_CHUNK = %d, this module expects %d; rebuild"
                       % (_lib.pvv_optim_chunk(), CHUNK))
@@ -104,10 +103,6 @@ def build_table(kind, pointers, numels, scalars):
             s32[k, :len(values)], flags[k] = values, bits         # binary64 -> float32, once
         rows["s"], rows["flags"] = s32[which], flags[which]
     return rows, chunk_start.astype(np.int32)
-
-
-def _upload(block, dev):
-    return torch.from_numpy(block.view(np.uint8).reshape(-1)).pin_memory().to(dev, non_blocking=True)
 
 
 def _per_tensor(value, n, what, pair=False):
@@ -240,12 +235,9 @@ def _launch(kind, lists, keys, clip_value, zero_grad, degenerated_to_sgd, dev=No
     if not numels:
         return
     rows, chunk_start = build_table(kind, pointers, numels, scalars)
-    table = _upload(np.concatenate([rows.view(np.uint8), chunk_start.view(np.uint8)]), dev)      # 80 n bytes, then the prefix
-    try:
-        _native.call(_lib, "pvv_optim_step", dev, KINDS[kind], table.data_ptr(), table.data_ptr() + rows.nbytes, len(numels),
-                     int(chunk_start[-1]), float(clip_value) if clip_value is not None else 0.0, flags)
-    except RuntimeError as e:
-        raise RuntimeError("clean_pvnet_amd.optim: %s: %s" % (e, _lib.pvv_last_error().decode())) from None
+    table = _native.upload(np.concatenate([rows.view(np.uint8), chunk_start.view(np.uint8)]), dev)      # 80 n bytes, then the prefix
+    _lib.call("pvv_optim_step", dev, KINDS[kind], table.data_ptr(), table.data_ptr() + rows.nbytes, len(numels),
+              int(chunk_start[-1]), float(clip_value) if clip_value is not None else 0.0, flags)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the classes

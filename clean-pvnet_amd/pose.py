@@ -16,7 +16,7 @@ import numpy as np
 from . import _native
 from ._native import DOUBLE, INT, PTR
 
-_lib = _native.load("pose", "libpvnet_pose.so", {
+_lib = _native.bind("pose", "libpvnet_pose.so", {
     "pvp_initial_pose_batched": (INT, [PTR] * 4 + [INT] + [PTR] * 2 + [INT] * 4 + [PTR]),
     "pvp_pose_batched": (INT, [PTR] * 4 + [INT] + [PTR] * 5 + [INT] * 5 + [DOUBLE, PTR]),
 })
@@ -60,8 +60,8 @@ def initial_pose_batched(points_2d, points_3d, camera_matrix, weights_2d=None, m
     status = torch.empty(b, dtype=torch.int32, device=dev)
     if b == 0:
         return rt, status
-    _native.call(_lib, "pvp_initial_pose_batched", dev, p2.data_ptr(), p3.data_ptr(), _native.ptr(w2), Km.data_ptr(),
-                 METHODS[method], rt.data_ptr(), status.data_ptr(), b, pn, int(p3.dim() == 3), int(Km.dim() == 3))
+    _lib.call("pvp_initial_pose_batched", dev, p2.data_ptr(), p3.data_ptr(), _native.ptr(w2), Km.data_ptr(),
+              METHODS[method], rt.data_ptr(), status.data_ptr(), b, pn, int(p3.dim() == 3), int(Km.dim() == 3))
     return rt, status
 
 
@@ -81,10 +81,10 @@ def pose_batched(points_2d, points_3d, camera_matrix, weights_2d=None, method="d
     out["status"] = torch.empty(b, dtype=torch.int32, device=dev)
     if b == 0:
         return out
-    _native.call(_lib, "pvp_pose_batched", dev, p2.data_ptr(), p3.data_ptr(), _native.ptr(w2), Km.data_ptr(), METHODS[method],
-                 out["rt"].data_ptr(), out["Rt"].data_ptr(), out["init_rt"].data_ptr(), out["status"].data_ptr(),
-                 out["info"].data_ptr(), b, pn, int(p3.dim() == 3), int(Km.dim() == 3), int(max_iterations),
-                 float(function_tolerance))
+    _lib.call("pvp_pose_batched", dev, p2.data_ptr(), p3.data_ptr(), _native.ptr(w2), Km.data_ptr(), METHODS[method],
+              out["rt"].data_ptr(), out["Rt"].data_ptr(), out["init_rt"].data_ptr(), out["status"].data_ptr(),
+              out["info"].data_ptr(), b, pn, int(p3.dim() == 3), int(Km.dim() == 3), int(max_iterations),
+              float(function_tolerance))
     return out
 
 

@@ -22,19 +22,13 @@ import numpy as np
 from . import _native
 from ._native import DOUBLE, INT, PTR, SIZE
 
-_lib = _native.load("render", "libpvnet_vote.so", {
-    "pvv_last_error": (ctypes.c_char_p, []),
+_lib = _native.bind("render", "libpvnet_vote.so", {
     "pvv_render_workspace_bytes": (SIZE, [INT] * 5),
     "pvv_render_color": (INT, [PTR] * 3 + [INT, INT, PTR] + [INT] * 3 + [PTR] * 3 + [INT, PTR, PTR] + [INT] * 4 + [DOUBLE] * 3
                          + [PTR, SIZE] + [PTR] * 6),
-})
+}, last_error="pvv_last_error")
 
 MAX_M, MAX_FACES, MAX_SIDE = 255, 1 << 24, 16384          # PVV_RENDER_MAX_M, PVV_RENDER_MAX_FACES, PVV_RENDER_MAX_SIDE
-
-
-def _upload(array, dev):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(array)).pin_memory().to(dev, non_blocking=True)
 
 
 def check_ranges(ranges, N, F):
@@ -121,18 +115,12 @@ def render_color(pts, colors, faces, pose, K, size, *, ranges=None, obj=None, bg
            "depth": torch.empty(B, H, W, dtype=torch.float32, device=dev), "area": torch.empty(B, M, dtype=torch.int32, device=dev)}
     if return_face:
         out["face"] = torch.empty(B, H, W, dtype=torch.int32, device=dev)
-    d_ranges = _upload(rg, dev)
-    nbytes = _lib.pvv_render_workspace_bytes(B, M, Nmax, H, W)
-    if nbytes == 0:
-        raise ValueError("clean_pvnet_amd.render: %s" % _lib.pvv_last_error().decode())
-    ws = _native.workspace(nbytes, dev)
-    try:
-        _native.call(_lib, "pvv_render_color", dev, md.data_ptr(), cl.data_ptr(), fc.data_ptr() if F else None, N, F, d_ranges.data_ptr(),
-                     int(rg.shape[0]), Nmax, Fmax, ps.data_ptr(), _native.ptr(ob), Km.data_ptr(), int(Km.dim() == 3), _native.ptr(bgt), bgc,
-                     B, M, H, W, float(near), float(far), float(ambient), ws.data_ptr(), ws.numel(), out["img"].data_ptr(),
-                     out["label"].data_ptr(), out["depth"].data_ptr(), out["area"].data_ptr(), _native.ptr(out.get("face")))
-    except RuntimeError as e:
-        raise RuntimeError("clean_pvnet_amd.render: %s: %s" % (e, _lib.pvv_last_error().decode())) from None
+    d_ranges = _native.upload(rg, dev)
+    ws, _ = _lib.workspace("pvv_render_workspace_bytes", dev, B, M, Nmax, H, W)
+    _lib.call("pvv_render_color", dev, md.data_ptr(), cl.data_ptr(), fc.data_ptr() if F else None, N, F, d_ranges.data_ptr(),
+              int(rg.shape[0]), Nmax, Fmax, ps.data_ptr(), _native.ptr(ob), Km.data_ptr(), int(Km.dim() == 3), _native.ptr(bgt), bgc,
+              B, M, H, W, float(near), float(far), float(ambient), ws.data_ptr(), ws.numel(), out["img"].data_ptr(),
+              out["label"].data_ptr(), out["depth"].data_ptr(), out["area"].data_ptr(), _native.ptr(out.get("face")))
     return out
 
 

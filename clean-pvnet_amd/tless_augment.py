@@ -37,15 +37,14 @@ from . import _native, ct_augment
 from ._native import DOUBLE, INT, PTR, SIZE
 from .ct_augment import EIG_VAL, EIG_VEC, MEAN, STD, colour_params, invert_affine
 
-_lib = _native.load("tless_augment", "libpvnet_vote.so", {
-    "pvv_last_error": (ctypes.c_char_p, []),
+_lib = _native.bind("tless_augment", "libpvnet_vote.so", {
     "pvv_tless_rotate_side": (INT, [INT, INT]),
     "pvv_tless_rotate": (INT, [PTR, PTR] + [INT] * 6 + [PTR, PTR]),
     "pvv_tless_compose_workspace_bytes": (SIZE, [INT] * 8),
     "pvv_tless_compose": (INT, [PTR] * 11 + [INT] * 10 + [DOUBLE, PTR, SIZE] + [PTR] * 8),
     "pvv_tless_augment_workspace_bytes": (SIZE, [INT] * 3),
     "pvv_tless_augment": (INT, [PTR] * 4 + [INT] * 7 + [PTR] * 6 + [SIZE] + [PTR] * 9),
-})
+}, last_error="pvv_last_error")
 
 # per sample, then (rot, dst_y, dst_x) per distractor.  Columns 3-9 lie where ct_augment.COLUMNS has them.
 COLUMNS = ("scale", "box", "top", "order", "alpha_0", "alpha_1", "alpha_2", "normal_0", "normal_1", "normal_2", "rot", "dst_y", "dst_x", "black")
@@ -126,18 +125,8 @@ def cut_records(h, w, deg):
     return rec
 
 
-def _upload(parts, dev):
-    """One pinned block for the host arrays ``parts``, each a multiple of 4 bytes, those of 8-byte elements first: the device
-    tensor and the byte offset of each part."""
-    import torch
-    raw = [np.ascontiguousarray(p).view(np.uint8).reshape(-1) for p in parts]
-    offsets = np.cumsum([0] + [len(r) for r in raw])[:-1]
-    block = torch.from_numpy(np.concatenate(raw)).pin_memory().to(dev, non_blocking=True)
-    return block, [block.data_ptr() + int(o) for o in offsets]
-
-
 def _call(symbol, dev, *args):
-    _native.call_named("tless_augment", _lib, symbol, dev, *args)
+    _lib.call(symbol, dev, *args)
 
 
 def _interp(interp):
@@ -188,7 +177,7 @@ def rotate_image(img, deg, interp="linear"):
     dev = img.device
     src = _native.u8(img)
     out = torch.empty(lead + ((D, D, 3) if channels == 3 else (D, D)), dtype=torch.uint8, device=dev)
-    block, (cuts,) = _upload([rec], dev)
+    block, (cuts,) = _native.upload_parts([rec], dev)
     _call("pvv_tless_rotate", dev, src.data_ptr(), cuts, P, h, w, channels, D, nearest, out.data_ptr())
     size = np.stack([rec["bh"], rec["bw"]], axis=-1).astype(np.int32)
     return {"out": out, "size": torch.from_numpy(size), "rot": torch.from_numpy(rec["M"].reshape(lead + (2, 3)).copy())}
@@ -255,11 +244,8 @@ def tless_compose(bg, img, mask, kpt_2d, other_img, other_mask, draws, fused_bg=
            "kpt_2d": torch.empty(B, K, 2, dtype=torch.float64, device=dev), "bbox": torch.empty(B, 4, dtype=torch.int32, device=dev),
            "path": torch.empty(B, dtype=torch.int32, device=dev), "place": torch.empty(B, 1 + N, 6, dtype=torch.int32, device=dev),
            "visible": torch.empty(B, 2, dtype=torch.int64, device=dev)}
-    block, (p_cuts, p_u, p_flags) = _upload([cuts, u, flags], dev)
-    nbytes = _lib.pvv_tless_compose_workspace_bytes(B, N, H, W, ht, wt, ho, wo)
-    if nbytes == 0:
-        raise ValueError("clean_pvnet_amd.tless_augment: %s" % _lib.pvv_last_error().decode())
-    ws = _native.workspace(nbytes, dev)
+    block, (p_cuts, p_u, p_flags) = _native.upload_parts([cuts, u, flags], dev)
+    ws, _ = _lib.workspace("pvv_tless_compose_workspace_bytes", dev, B, N, H, W, ht, wt, ho, wo)
     _call("pvv_tless_compose", dev, keep[0].data_ptr(), _native.ptr(keep[6]), keep[1].data_ptr(), keep[2].data_ptr(), keep[3].data_ptr(),
           keep[4].data_ptr(), keep[5].data_ptr(), _native.ptr(keep[7]), p_cuts, p_u, p_flags, B, H, W, N, K, ht, wt, ho, wo, nearest, float(ratio),
           ws.data_ptr(), ws.numel(), out["img"].data_ptr(), out["mask"].data_ptr(), out["kpt_2d"].data_ptr(), out["bbox"].data_ptr(),
@@ -336,12 +322,9 @@ def tless_pvnet_augment(img, mask, kpt_2d, bbox, draws, input_size=(256, 256), s
            "mask": torch.empty(B, ih, iw, dtype=torch.uint8, device=dev), "kpt_2d": torch.empty(B, K, 2, dtype=torch.float64, device=dev),
            "trans_input": torch.empty(B, 2, 3, dtype=torch.float64, device=dev), "center": torch.empty(B, 2, dtype=torch.float64, device=dev),
            "scale": torch.empty(B, 2, dtype=torch.float32, device=dev), "box": torch.empty(B, 4, dtype=torch.int32, device=dev)}
-    block, (p_colour, p_ratio, p_factor) = _upload([colour, box_ratio, factor], dev)
+    block, (p_colour, p_ratio, p_factor) = _native.upload_parts([colour, box_ratio, factor], dev)
     mean_c, std_c = (ctypes.c_float * 3)(*[float(v) for v in mean]), (ctypes.c_float * 3)(*[float(v) for v in std])
-    nbytes = _lib.pvv_tless_augment_workspace_bytes(B, ih, iw)
-    if nbytes == 0:
-        raise ValueError("clean_pvnet_amd.tless_augment: %s" % _lib.pvv_last_error().decode())
-    ws = _native.workspace(nbytes, dev)
+    ws, _ = _lib.workspace("pvv_tless_augment_workspace_bytes", dev, B, ih, iw)
     _call("pvv_tless_augment", dev, keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr(), keep[3].data_ptr(), B, H, W, K, ih, iw, int(bool(train)),
           p_factor, p_ratio, p_colour, mean_c, std_c, ws.data_ptr(), ws.numel(), out["orig_img"].data_ptr(), out["inp"].data_ptr(),
           out["mask"].data_ptr(), out["kpt_2d"].data_ptr(), out["trans_input"].data_ptr(), out["center"].data_ptr(), out["scale"].data_ptr(),

@@ -9,46 +9,32 @@ mask and the keypoints.  The target equals the reference's bit for bit, the vote
 bit for bit, every sum is binary64 in a fixed order (tests/train_twin.py is the contract in numpy, tests/golden/train_*.npz
 the reference's own results).  CUDA float32 tensors, the current stream, nothing read back, no CPU fallback.
 """
-import ctypes
-
 import torch
 from torch import nn
-from torch.autograd.function import once_differentiable
 
 from . import _native
+from ._loss import FusedLoss
 from ._native import INT, LONGLONG, PTR, SIZE
 
 MAX_K, MAX_C = 64, 16                # PVV_TRAIN_MAX_K, PVV_TRAIN_MAX_C
 MASK_KINDS = {torch.uint8: 0, torch.bool: 0, torch.int32: 1, torch.int64: 2}     # PVV_MASK_U8, PVV_MASK_I32, PVV_MASK_I64
 
 _INPUTS = [PTR, LONGLONG, PTR, LONGLONG, PTR, INT, PTR, INT, PTR, LONGLONG] + [INT] * 5
-_lib = _native.load("train", "libpvnet_vote.so", {
-    "pvv_last_error": (ctypes.c_char_p, []),
+_lib = _native.bind("train", "libpvnet_vote.so", {
     "pvv_vertex_target": (INT, [PTR, INT, PTR, INT, INT, INT, INT, INT, PTR, PTR]),
     "pvv_pvnet_loss_workspace_bytes": (SIZE, [INT] * 3),
     "pvv_pvnet_loss_forward": (INT, _INPUTS + [PTR, SIZE, PTR, PTR, PTR]),
     "pvv_pvnet_loss_backward": (INT, _INPUTS + [PTR, PTR, PTR, PTR, PTR]),
-})
+}, last_error="pvv_last_error")
 
-
-def _call(symbol, dev, *args):
-    try:
-        _native.call(_lib, symbol, dev, *args)
-    except RuntimeError as e:
-        raise RuntimeError("clean_pvnet_amd.train: %s: %s" % (e, _lib.pvv_last_error().decode())) from None
+_F32 = (torch.float32,)
+_DTYPES = {"vertex_pred": _F32, "seg_pred": _F32, "vertex": _F32, "mask": tuple(MASK_KINDS), "kpt_2d": (torch.float32, torch.float64)}
 
 
 def _check(named, mask, kpt_2d):
     """Device, then dtype, of every tensor; shapes come after."""
-    for what, t in named + [("mask", mask)] + ([("kpt_2d", kpt_2d)] if kpt_2d is not None else []):
-        _native.need_cuda(t, what, "train")
-    for what, t in named:
-        if t.dtype != torch.float32:
-            raise RuntimeError("clean_pvnet_amd.train: %s must be float32, got %s" % (what, t.dtype))
-    if mask.dtype not in MASK_KINDS:
-        raise RuntimeError("clean_pvnet_amd.train: mask must be uint8, bool, int32 or int64, got %s" % mask.dtype)
-    if kpt_2d is not None and kpt_2d.dtype not in (torch.float32, torch.float64):
-        raise RuntimeError("clean_pvnet_amd.train: kpt_2d must be float32 or float64, got %s" % kpt_2d.dtype)
+    named = named + [("mask", mask)] + ([("kpt_2d", kpt_2d)] if kpt_2d is not None else [])
+    _native.check_tensors(named, _DTYPES, "train", {"mask": "uint8, bool, int32 or int64"})
 
 
 def _mask_kpt_shapes(mask, kpt_2d):
@@ -58,15 +44,6 @@ def _mask_kpt_shapes(mask, kpt_2d):
     if kpt_2d is not None and (kpt_2d.dim() != 3 or kpt_2d.shape[0] != B or kpt_2d.shape[2] != 2):
         raise ValueError("clean_pvnet_amd.train: kpt_2d must be [B = %d, K, 2], got %s" % (B, tuple(kpt_2d.shape)))
     return B, H, W
-
-
-def _per_image(t, what, channels, H, W):
-    """``t`` [B, channels, H, W] as (tensor, element stride between images): a view whose images are contiguous -- a channel
-    slice of the network's output -- is taken as it is, by its stride."""
-    image = channels * H * W
-    if not t[:1].is_contiguous() or (t.shape[0] > 1 and t.stride(0) < image):
-        t = t.contiguous()
-    return t, (t.stride(0) if t.shape[0] > 1 else image)
 
 
 def compute_vertex(mask, kpt_2d):
@@ -84,8 +61,8 @@ def compute_vertex(mask, kpt_2d):
     out = torch.empty(B, 2 * K, H, W, dtype=torch.float32, device=m.device)
     if out.numel() == 0:
         return out[0] if single else out
-    _call("pvv_vertex_target", m.device, m.data_ptr(), MASK_KINDS[m.dtype], kp.data_ptr(), int(kp.dtype == torch.float64), B, K, H, W,
-          out.data_ptr())
+    _lib.call("pvv_vertex_target", m.device, m.data_ptr(), MASK_KINDS[m.dtype], kp.data_ptr(), int(kp.dtype == torch.float64), B, K, H, W,
+              out.data_ptr())
     return out[0] if single else out
 
 
@@ -113,9 +90,9 @@ def _problem(vertex_pred, seg_pred, mask, kpt_2d, vertex):
         raise ValueError("clean_pvnet_amd.train: K must lie in [1, %d] and C in [1, %d], got K = %d, C = %d" % (MAX_K, MAX_C, K, C))
     if B == 0 or H * W == 0:
         raise ValueError("clean_pvnet_amd.train: an empty batch has no loss")
-    vp, vp_stride = _per_image(vertex_pred.detach(), "vertex_pred", 2 * K, H, W)
-    sp, sp_stride = _per_image(seg_pred.detach(), "seg_pred", C, H, W)
-    tg, tg_stride = (None, 0) if vertex is None else _per_image(vertex, "vertex", 2 * K, H, W)
+    vp, vp_stride = _native.per_image(vertex_pred.detach(), "vertex_pred", 2 * K, H, W)
+    sp, sp_stride = _native.per_image(seg_pred.detach(), "seg_pred", C, H, W)
+    tg, tg_stride = (None, 0) if vertex is None else _native.per_image(vertex, "vertex", 2 * K, H, W)
     m = mask.contiguous()
     kp = None if kpt_2d is None else kpt_2d.contiguous()
     args = (vp.data_ptr(), vp_stride, sp.data_ptr(), sp_stride, m.data_ptr(), MASK_KINDS[m.dtype], _native.ptr(kp),
@@ -123,34 +100,13 @@ def _problem(vertex_pred, seg_pred, mask, kpt_2d, vertex):
     return (vp, sp, m, kp, tg), args, (B, K, C, H, W)
 
 
-class _PVNetLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, vertex_pred, seg_pred, mask, kpt_2d, vertex):
-        keep, args, (B, K, C, H, W) = _problem(vertex_pred, seg_pred, mask, kpt_2d, vertex)
-        dev = vertex_pred.device
-        nbytes = _lib.pvv_pvnet_loss_workspace_bytes(B, H, W)
-        if nbytes == 0:
-            raise ValueError("clean_pvnet_amd.train: %s" % _lib.pvv_last_error().decode())
-        ws = _native.workspace(nbytes, dev)
-        losses = torch.empty(2, dtype=torch.float32, device=dev)
-        state = torch.empty(2, dtype=torch.int64, device=dev)
-        _call("pvv_pvnet_loss_forward", dev, *args, ws.data_ptr(), nbytes, losses.data_ptr(), state.data_ptr())
-        ctx.keep, ctx.args, ctx.sizes, ctx.state = keep, args, (B, K, C, H, W), state
-        return losses[0], losses[1]
+class _PVNetLoss(FusedLoss):
+    lib, workspace_query, state_len = _lib, "pvv_pvnet_loss_workspace_bytes", 2
+    forward_symbol, backward_symbol = "pvv_pvnet_loss_forward", "pvv_pvnet_loss_backward"
 
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, go_vote, go_seg):
-        B, K, C, H, W = ctx.sizes
-        dev = ctx.state.device
-        zero = None
-        if go_vote is None or go_seg is None:                      # an unused loss: its upstream gradient counts as zero
-            zero = torch.zeros((), dtype=torch.float32, device=dev)
-        go = torch.stack([zero if go_vote is None else go_vote.to(torch.float32), zero if go_seg is None else go_seg.to(torch.float32)])
-        grad_vertex = torch.empty(B, 2 * K, H, W, dtype=torch.float32, device=dev)
-        grad_seg = torch.empty(B, C, H, W, dtype=torch.float32, device=dev)
-        _call("pvv_pvnet_loss_backward", dev, *ctx.args, ctx.state.data_ptr(), go.data_ptr(), grad_vertex.data_ptr(), grad_seg.data_ptr())
-        return grad_vertex, grad_seg, None, None, None
+    problem = staticmethod(lambda *inputs: _problem(*inputs))
+    workspace_sizes = staticmethod(lambda B, K, C, H, W: (B, H, W))
+    grad_shapes = staticmethod(lambda B, K, C, H, W: ((B, 2 * K, H, W), (B, C, H, W)))
 
 
 def pvnet_loss(vertex_pred, seg_pred, mask, *, kpt_2d=None, vertex=None):

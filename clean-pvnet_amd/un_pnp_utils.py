@@ -18,7 +18,7 @@ import numpy as np
 from . import _native
 from ._native import DOUBLE, INT, PTR
 
-_lib = _native.load("un_pnp_utils", "libpvnet_pnp.so", {
+_lib = _native.bind("un_pnp_utils", "libpvnet_pnp.so", {
     "uncertainty_pnp": (None, [PTR] * 6 + [INT]),
     "pvp_uncertainty_pnp_batched": (INT, [PTR] * 7 + [INT] * 5 + [DOUBLE, PTR]),
 })
@@ -280,7 +280,7 @@ def uncertainty_pnp_batched(points_2d, weights_2d, points_3d, camera_matrix, ini
     info = torch.empty(b, 4, dtype=torch.float64, device=dev) if return_info else None
     if b == 0:
         return (out, info) if return_info else out
-    _native.call(_lib, "pvp_uncertainty_pnp_batched", dev, p2.data_ptr(), p3.data_ptr(), w2.data_ptr(), Km.data_ptr(),
-                 rt0.data_ptr(), out.data_ptr(), _native.ptr(info), b, pn, 1 if p3.dim() == 3 else 0, 1 if Km.dim() == 3 else 0,
-                 int(max_iterations), float(function_tolerance))
+    _lib.call("pvp_uncertainty_pnp_batched", dev, p2.data_ptr(), p3.data_ptr(), w2.data_ptr(), Km.data_ptr(),
+              rt0.data_ptr(), out.data_ptr(), _native.ptr(info), b, pn, 1 if p3.dim() == 3 else 0, 1 if Km.dim() == 3 else 0,
+              int(max_iterations), float(function_tolerance))
     return (out, info) if return_info else out

@@ -13,7 +13,7 @@ on the current stream in a workspace from the caching allocator.  There is no CP
 from . import _native
 from ._native import DOUBLE, INT, PTR, SIZE
 
-_lib = _native.load("vsd", "libpvnet_vsd.so", {
+_lib = _native.bind("vsd", "libpvnet_vsd.so", {
     "pvs_render_workspace_bytes": (SIZE, [INT] * 2),
     "pvs_render_depth_batched": (INT, [PTR] * 6 + [INT] * 6 + [DOUBLE] * 2 + [PTR]),
     "pvs_vsd_workspace_bytes": (SIZE, [INT] * 6),
@@ -61,10 +61,10 @@ def render_depth(pts, faces, pose, K, size, near=100., far=10000.):
     assert Km.shape in ((3, 3), (P, 3, 3)), Km.shape
     depth = torch.empty(P, H, W, dtype=torch.float32, device=dev)
     if P:
-        ws = _native.workspace(_lib.pvs_render_workspace_bytes(P, md.shape[0]), dev)
-        _native.call(_lib, "pvs_render_depth_batched", dev, md.data_ptr(), fc.data_ptr() if fc.shape[0] else None, ps.data_ptr(),
-                     Km.data_ptr(), depth.data_ptr(), ws.data_ptr(), P, md.shape[0], fc.shape[0], int(Km.dim() == 3), W, H,
-                     float(near), float(far))
+        ws, _ = _lib.workspace("pvs_render_workspace_bytes", dev, P, md.shape[0])
+        _lib.call("pvs_render_depth_batched", dev, md.data_ptr(), fc.data_ptr() if fc.shape[0] else None, ps.data_ptr(),
+                  Km.data_ptr(), depth.data_ptr(), ws.data_ptr(), P, md.shape[0], fc.shape[0], int(Km.dim() == 3), W, H,
+                  float(near), float(far))
     return depth
 
 
@@ -169,10 +169,10 @@ def vsd_from_depth(depth_est, depth_gt, depth_test, K, *, delta=15., tau=20., co
     counts = torch.empty(n, p, g, 3, dtype=torch.int64, device=dev)
     e = torch.empty(n, p, g, dtype=torch.float64, device=dev)
     if n * p * g:
-        ws = _native.workspace(_lib.pvs_vsd_workspace_bytes(n, p, g, H, W, COSTS[cost]), dev)
-        _native.call(_lib, "pvs_vsd_batched", dev, depth_est.data_ptr(), depth_gt.data_ptr(), dt.data_ptr(), kind,
-                     float(depth_scale), Km.data_ptr(), int(Km.dim() == 3), float(delta), float(tau), COSTS[cost],
-                     counts.data_ptr(), e.data_ptr(), ws.data_ptr(), n, p, g, H, W)
+        ws, _ = _lib.workspace("pvs_vsd_workspace_bytes", dev, n, p, g, H, W, COSTS[cost])
+        _lib.call("pvs_vsd_batched", dev, depth_est.data_ptr(), depth_gt.data_ptr(), dt.data_ptr(), kind,
+                  float(depth_scale), Km.data_ptr(), int(Km.dim() == 3), float(delta), float(tau), COSTS[cost],
+                  counts.data_ptr(), e.data_ptr(), ws.data_ptr(), n, p, g, H, W)
     if gt_valid is not None:
         e = torch.where((gt_valid != 0)[:, None, :], e, torch.full_like(e, float("nan")))
     if return_counts:

@@ -463,6 +463,59 @@ def test_native_loader_refuses_a_library_that_is_not_built():
         native.need_cuda(torch.zeros(1), "x", "nowhere")
 
 
+def _probe(native, **kw):
+    return native.bind("probe", "libpvnet_vote.so", {"pvv_ct_loss_workspace_bytes": (native.SIZE, [native.INT] * 4)}, **kw)
+
+
+def test_native_bind_opens_as_load_does_and_exposes_the_functions():
+    """``bind`` is ``load`` with the module's name kept: the same ImportError for a library that is not built, the ctypes
+    functions as attributes with their signatures set, and the error string's signature added when one is named."""
+    native = _load_file("_native_bind", ROOT, "clean-pvnet_amd", "_native.py")
+    texts = []
+    for opener in (native.load, native.bind):
+        with pytest.raises(ImportError) as ei:
+            opener("nowhere", "libpvnet_nowhere.so", {})
+        texts.append(str(ei.value))
+    assert texts[0] == texts[1] and "clean_pvnet_amd.nowhere: libpvnet_nowhere.so is not built" in texts[1]
+    lib = _probe(native, last_error="pvv_last_error")
+    fn = lib.pvv_ct_loss_workspace_bytes
+    assert isinstance(fn, ctypes._CFuncPtr) and fn.restype is ctypes.c_size_t and fn.argtypes == [ctypes.c_int] * 4
+    assert fn(2, 3, 37, 53) > 0 and fn(2, 3, 37, 53) % 256 == 0
+    assert lib.pvv_last_error.restype is ctypes.c_char_p
+    assert fn(0, 3, 8, 8) == 0 and b"positive" in lib.pvv_last_error()
+    with pytest.raises(AttributeError):
+        lib.pvv_no_such_symbol
+
+
+def test_native_workspace_refuses_with_the_librarys_message_and_allocates_through_the_module_global():
+    """``Library.workspace``: a refused size raises the module's exception with the library's message and asks for no memory; an
+    accepted one goes through ``_native.workspace`` as it is bound when the call is made -- what tests/guarded.py replaces."""
+    native = _load_file("_native_ws", ROOT, "clean-pvnet_amd", "_native.py")
+    asked, real = [], native.workspace
+
+    def recording(nbytes, dev):
+        asked.append(int(nbytes))
+        return real(nbytes, dev)
+    native.workspace = recording
+    lib = _probe(native, last_error="pvv_last_error")
+    with pytest.raises(ValueError) as ei:
+        lib.workspace("pvv_ct_loss_workspace_bytes", "cpu", 2, 0, 8, 8)                          # C = 0
+    assert str(ei.value) == "clean_pvnet_amd.probe: ct_train: B, C, H, W must be positive" and asked == []
+    short = _probe(native, last_error="pvv_last_error", prefix="probe")
+    with pytest.raises(RuntimeError) as ei:
+        short.workspace("pvv_ct_loss_workspace_bytes", "cpu", 1, 30, 8462, 8462, error=RuntimeError)
+    assert str(ei.value).startswith("probe: ct_train: C * H * W") and asked == []
+    ws, nbytes = lib.workspace("pvv_ct_loss_workspace_bytes", "cpu", 2, 3, 37, 53)
+    assert nbytes == lib.pvv_ct_loss_workspace_bytes(2, 3, 37, 53) and asked == [nbytes]
+    assert ws.dtype == torch.uint8 and ws.numel() == nbytes and ws.device.type == "cpu"
+    # the refusal is the call site's: a query whose refusal is a negative size takes 0 as a size (16 bytes are allocated)
+    ws, nbytes = lib.workspace("pvv_ct_loss_workspace_bytes", "cpu", 2, 0, 8, 8, refused=lambda n: n < 0)
+    assert nbytes == 0 and ws.numel() == 16 and asked[-1] == 0
+    native.workspace = real
+    lib.workspace("pvv_ct_loss_workspace_bytes", "cpu", 2, 3, 37, 53)
+    assert len(asked) == 2
+
+
 def test_build_table_headers_and_sources_name_the_same_libraries():
     import glob
     import re
