@@ -176,9 +176,9 @@ __device__ __forceinline__ LmInfo lm_refine(double x[6], const double *__restric
     const int limit = max_iter > 0 ? max_iter : 50;
     int it = 0, term = 0;
     for (; it < limit; ++it) {
-        double gmax = 0.0;
-        for (int k = 0; k < 6; ++k) gmax = fmax(gmax, fabs(g[k]));
-        if (gmax <= 1e-10) { term = 1; break; }
+        bool flat = true;                                     // max |g| <= 1e-10; a NaN entry is not flat (fmax would drop it)
+        for (int k = 0; k < 6; ++k) flat &= fabs(g[k]) <= 1e-10;
+        if (flat) { term = 1; break; }
         double d[6], ng[6], step[6];
         {
             int idx = 0;

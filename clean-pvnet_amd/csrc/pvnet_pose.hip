@@ -123,26 +123,25 @@ __device__ __forceinline__ double det3(const double M[3][3])
 // un_pnp_utils.rotation_to_angle_axis, branch for branch
 __device__ void angle_axis(const double R[3][3], double w[3])
 {
-    const double c = fmin(fmax((R[0][0] + R[1][1] + R[2][2] - 1.0) / 2.0, -1.0), 1.0);
-    const double th = acos(c);
+    const double c = (R[0][0] + R[1][1] + R[2][2] - 1.0) / 2.0;
     const double v[3] = {R[2][1] - R[1][2], R[0][2] - R[2][0], R[1][0] - R[0][1]};
+    const double s = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]) / 2.0;
+    const double th = atan2(s, c);                            // well conditioned at 0 and at pi, where acos(c) is not
     if (th < 1e-9) {
         for (int k = 0; k < 3; ++k) w[k] = v[k] / 2.0;
-    } else if (M_PI - th < 1e-6) {                           // near pi: the axis from the symmetric part
-        double A[3][3], a[3];
-        for (int r = 0; r < 3; ++r)
-            for (int k = 0; k < 3; ++k) A[r][k] = (R[r][k] + (r == k ? 1.0 : 0.0)) / 2.0;
-        for (int k = 0; k < 3; ++k) a[k] = sqrt(fmax(A[k][k], 0.0));
-        const int m = a[1] > a[0] ? (a[2] > a[1] ? 2 : 1) : (a[2] > a[0] ? 2 : 0);   // np.argmax: the first maximum
-        double ax[3];
-        for (int k = 0; k < 3; ++k) ax[k] = A[m][k] / a[m];
-        if (v[0] * ax[0] + v[1] * ax[1] + v[2] * ax[2] < 0.0)
-            for (int k = 0; k < 3; ++k) ax[k] = -ax[k];
-        const double n = sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
-        for (int k = 0; k < 3; ++k) w[k] = ax[k] / n * th;
-    } else {
-        const double f = th / (2.0 * sin(th));
+    } else if (c > -0.5) {                                    // the axis from the antisymmetric part, |v| = 2 sin th
+        const double f = th / (2.0 * s);
         for (int k = 0; k < 3; ++k) w[k] = v[k] * f;
+    } else {                                                  // towards pi v vanishes: (R + R^T) / 2 - c I = (1 - c) a a^T
+        double S[3][3];
+        for (int r = 0; r < 3; ++r)
+            for (int k = 0; k < 3; ++k) S[r][k] = (R[r][k] + R[k][r]) / 2.0 - (r == k ? c : 0.0);
+        const int m = S[1][1] > S[0][0] ? (S[2][2] > S[1][1] ? 2 : 1) : (S[2][2] > S[0][0] ? 2 : 0);   // np.argmax: the first maximum
+        double a[3] = {S[m][0], S[m][1], S[m][2]};
+        if (v[0] * a[0] + v[1] * a[1] + v[2] * a[2] < 0.0)
+            for (int k = 0; k < 3; ++k) a[k] = -a[k];
+        const double f = th / sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+        for (int k = 0; k < 3; ++k) w[k] = a[k] * f;
     }
 }
 
@@ -407,92 +406,142 @@ __device__ void start_dlt(const double *p2, const double *p3, const double *wg, 
         if (kept(i))
             for (int k = 0; k < 3; ++k) ss += (p3[i * 3 + k] - c[k]) * (p3[i * 3 + k] - c[k]);
     const double s = sqrt(wave_sum(ss) / cnt) + 1e-30;
-    // A^T A of the 2pn x 12 system: rows w [Qh, 0, -nx Qh] and w [0, Qh, -ny Qh] -> four symmetric 4 x 4 sums
-    double S[4][10];
-    for (int b = 0; b < 4; ++b)
-        for (int k = 0; k < 10; ++k) S[b][k] = 0.0;
-    for (int i = lane; i < pn; i += 64) {
-        if (!kept(i)) continue;
-        double w2 = 1.0;
-        if (with_key) { const double rw = fmax(sqrt(wkey(i) / kmax), 1e-3); w2 = rw * rw; }
-        const double u = p2[i * 2], v = p2[i * 2 + 1];
-        const double nx = Ki[0][0] * u + Ki[0][1] * v + Ki[0][2], ny = Ki[1][0] * u + Ki[1][1] * v + Ki[1][2];
-        const double Qh[4] = {(p3[i * 3] - c[0]) / s, (p3[i * 3 + 1] - c[1]) / s, (p3[i * 3 + 2] - c[2]) / s, 1.0};
-        const double wb[4] = {w2, w2 * nx, w2 * ny, w2 * (nx * nx + ny * ny)};
-        int k = 0;
-        for (int r = 0; r < 4; ++r)
-            for (int q = r; q < 4; ++q, ++k) {
-                const double e = Qh[r] * Qh[q];
-                for (int b = 0; b < 4; ++b) S[b][k] += wb[b] * e;
-            }
-    }
-    for (int b = 0; b < 4; ++b)
-        for (int k = 0; k < 10; ++k) S[b][k] = wave_sum(S[b][k]);
     double *A = ws, *V = ws + 144;                             // A[12][12], V[12][12] row-major
-    if (lane < 12) {
-        for (int q = 0; q < 12; ++q) { A[lane * 12 + q] = 0.0; V[lane * 12 + q] = lane == q ? 1.0 : 0.0; }
-    }
-    wave_sync();
-    if (lane == 0) {
-        // blocks (row offset, column offset, sum, sign): [0:4,0:4] = [4:8,4:8] = S0, [0:4,8:12] = -S1, [4:8,8:12] = -S2,
-        // [8:12,8:12] = S3, each symmetric, mirrored below the diagonal
-        const int blk[5][4] = {{0, 0, 0, 1}, {4, 4, 0, 1}, {0, 8, 1, -1}, {4, 8, 2, -1}, {8, 8, 3, 1}};
-        for (int e = 0; e < 5; ++e) {
-            const int ro = blk[e][0], co = blk[e][1];
+    double M[3][4];
+    if (six) {
+        // Six rows of weight down to 1e-3: the normal matrix would square a condition number of ~1e5 and leave the null
+        // vector to 1e-6 only.  Six keypoints make A itself 12 x 12, so its right singular vectors come from a one-sided
+        // (Hestenes) Jacobi on A's columns, as accurate as the twin's svd(A).  Lane r owns row r of A and of V; a column
+        // pair is rotated from its three dot products, reduced across the wave (the same bits in every lane).
+        if (lane < 12) {
+            const int i = min(max(sel[lane >> 1], 0), pn - 1);   // six distinct keypoints (pn >= 6); clamped all the same
+            const double rw = fmax(sqrt(wkey(i) / kmax), 1e-3);
+            const double u = p2[i * 2], v = p2[i * 2 + 1];
+            const double n = (lane & 1) ? Ki[1][0] * u + Ki[1][1] * v + Ki[1][2] : Ki[0][0] * u + Ki[0][1] * v + Ki[0][2];
+            const double Qh[4] = {(p3[i * 3] - c[0]) / s, (p3[i * 3 + 1] - c[1]) / s, (p3[i * 3 + 2] - c[2]) / s, 1.0};
+            const int off = (lane & 1) ? 4 : 0;
+            for (int q = 0; q < 12; ++q) { A[lane * 12 + q] = 0.0; V[lane * 12 + q] = lane == q ? 1.0 : 0.0; }
+            for (int q = 0; q < 4; ++q) { A[lane * 12 + off + q] = rw * Qh[q]; A[lane * 12 + 8 + q] = -(rw * n) * Qh[q]; }
+        }
+        wave_sync();
+        for (int sweep = 0; sweep < 30; ++sweep) {
+            bool rotated = false;
+            for (int p = 0; p < 11; ++p)
+                for (int q = p + 1; q < 12; ++q) {
+                    const double ap = lane < 12 ? A[lane * 12 + p] : 0.0, aq = lane < 12 ? A[lane * 12 + q] : 0.0;
+                    const double alpha = wave_sum(ap * ap), beta = wave_sum(aq * aq), gamma = wave_sum(ap * aq);
+                    if (fabs(gamma) <= 1e-15 * sqrt(alpha * beta)) continue;   // orthogonal to rounding (uniform)
+                    rotated = true;
+                    const double zeta = (beta - alpha) / (2.0 * gamma);
+                    double t = 1.0 / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                    if (zeta < 0.0) t = -t;
+                    const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
+                    if (lane < 12) {                           // its own row only: no other lane reads it before the end
+                        A[lane * 12 + p] = cs * ap - sn * aq;
+                        A[lane * 12 + q] = sn * ap + cs * aq;
+                        const double vp = V[lane * 12 + p], vq = V[lane * 12 + q];
+                        V[lane * 12 + p] = cs * vp - sn * vq;
+                        V[lane * 12 + q] = sn * vp + cs * vq;
+                    }
+                }
+            if (!rotated) break;
+        }
+        int jmin = 0;
+        double smin = INFINITY;
+        for (int j = 0; j < 12; ++j) {                         // the smallest singular value: the shortest column of A
+            const double a = lane < 12 ? A[lane * 12 + j] : 0.0;
+            const double n2 = wave_sum(a * a);
+            if (n2 < smin) { smin = n2; jmin = j; }
+        }
+        wave_sync();
+        for (int r = 0; r < 3; ++r)
+            for (int q = 0; q < 4; ++q) M[r][q] = V[(4 * r + q) * 12 + jmin];
+    } else {
+        // A^T A of the 2pn x 12 system: rows w [Qh, 0, -nx Qh] and w [0, Qh, -ny Qh] -> four symmetric 4 x 4 sums
+        double S[4][10];
+        for (int b = 0; b < 4; ++b)
+            for (int k = 0; k < 10; ++k) S[b][k] = 0.0;
+        for (int i = lane; i < pn; i += 64) {
+            if (!kept(i)) continue;
+            double w2 = 1.0;
+            if (with_key) { const double rw = fmax(sqrt(wkey(i) / kmax), 1e-3); w2 = rw * rw; }
+            const double u = p2[i * 2], v = p2[i * 2 + 1];
+            const double nx = Ki[0][0] * u + Ki[0][1] * v + Ki[0][2], ny = Ki[1][0] * u + Ki[1][1] * v + Ki[1][2];
+            const double Qh[4] = {(p3[i * 3] - c[0]) / s, (p3[i * 3 + 1] - c[1]) / s, (p3[i * 3 + 2] - c[2]) / s, 1.0};
+            const double wb[4] = {w2, w2 * nx, w2 * ny, w2 * (nx * nx + ny * ny)};
             int k = 0;
             for (int r = 0; r < 4; ++r)
                 for (int q = r; q < 4; ++q, ++k) {
-                    const double val = blk[e][3] * S[blk[e][2]][k];
-                    A[(ro + r) * 12 + co + q] = val; A[(co + q) * 12 + ro + r] = val;
-                    A[(ro + q) * 12 + co + r] = val; A[(co + r) * 12 + ro + q] = val;
+                    const double e = Qh[r] * Qh[q];
+                    for (int b = 0; b < 4; ++b) S[b][k] += wb[b] * e;
                 }
         }
-    }
-    wave_sync();
-    // cyclic Jacobi on the 12 x 12 normal matrix, lane r owns row r (and, A being symmetric, column r) of A and of V
-    for (int sweep = 0; sweep < 50; ++sweep) {
-        double off = 0.0;
-        if (lane < 12)
-            for (int q = lane + 1; q < 12; ++q) off += fabs(A[lane * 12 + q]);
-        if (wave_sum(off) == 0.0) break;
-        for (int p = 0; p < 11; ++p)
-            for (int q = p + 1; q < 12; ++q) {
-                const double apq = A[p * 12 + q], app = A[p * 12 + p], aqq = A[q * 12 + q];
-                if (apq == 0.0) continue;
-                const double g = 100.0 * fabs(apq);
-                const bool tiny = fabs(app) + g == fabs(app) && fabs(aqq) + g == fabs(aqq);
-                double t = 0.0, sn = 0.0, tau = 0.0;
-                if (!tiny) {
-                    const double theta = 0.5 * (aqq - app) / apq;
-                    t = 1.0 / (fabs(theta) + sqrt(1.0 + theta * theta));
-                    if (theta < 0.0) t = -t;
-                    const double cs = 1.0 / sqrt(1.0 + t * t);
-                    sn = t * cs; tau = sn / (1.0 + cs);
-                }
-                if (lane < 12 && !tiny) {
-                    if (lane != p && lane != q) {
-                        const double gp = A[lane * 12 + p], hq = A[lane * 12 + q];
-                        const double np_ = gp - sn * (hq + gp * tau), nq = hq + sn * (gp - hq * tau);
-                        A[lane * 12 + p] = np_; A[p * 12 + lane] = np_;
-                        A[lane * 12 + q] = nq; A[q * 12 + lane] = nq;
+        for (int b = 0; b < 4; ++b)
+            for (int k = 0; k < 10; ++k) S[b][k] = wave_sum(S[b][k]);
+        if (lane < 12) {
+            for (int q = 0; q < 12; ++q) { A[lane * 12 + q] = 0.0; V[lane * 12 + q] = lane == q ? 1.0 : 0.0; }
+        }
+        wave_sync();
+        if (lane == 0) {
+            // blocks (row offset, column offset, sum, sign): [0:4,0:4] = [4:8,4:8] = S0, [0:4,8:12] = -S1, [4:8,8:12] = -S2,
+            // [8:12,8:12] = S3, each symmetric, mirrored below the diagonal
+            const int blk[5][4] = {{0, 0, 0, 1}, {4, 4, 0, 1}, {0, 8, 1, -1}, {4, 8, 2, -1}, {8, 8, 3, 1}};
+            for (int e = 0; e < 5; ++e) {
+                const int ro = blk[e][0], co = blk[e][1];
+                int k = 0;
+                for (int r = 0; r < 4; ++r)
+                    for (int q = r; q < 4; ++q, ++k) {
+                        const double val = blk[e][3] * S[blk[e][2]][k];
+                        A[(ro + r) * 12 + co + q] = val; A[(co + q) * 12 + ro + r] = val;
+                        A[(ro + q) * 12 + co + r] = val; A[(co + r) * 12 + ro + q] = val;
                     }
-                    const double vp = V[lane * 12 + p], vq = V[lane * 12 + q];
-                    V[lane * 12 + p] = vp - sn * (vq + vp * tau);
-                    V[lane * 12 + q] = vq + sn * (vp - vq * tau);
-                }
-                if (lane == 0) {
-                    if (!tiny) { A[p * 12 + p] = app - t * apq; A[q * 12 + q] = aqq + t * apq; }
-                    A[p * 12 + q] = 0.0; A[q * 12 + p] = 0.0;
-                }
-                wave_sync();
             }
+        }
+        wave_sync();
+        // cyclic Jacobi on the 12 x 12 normal matrix, lane r owns row r (and, A being symmetric, column r) of A and of V
+        for (int sweep = 0; sweep < 50; ++sweep) {
+            double off = 0.0;
+            if (lane < 12)
+                for (int q = lane + 1; q < 12; ++q) off += fabs(A[lane * 12 + q]);
+            if (wave_sum(off) == 0.0) break;
+            for (int p = 0; p < 11; ++p)
+                for (int q = p + 1; q < 12; ++q) {
+                    const double apq = A[p * 12 + q], app = A[p * 12 + p], aqq = A[q * 12 + q];
+                    if (apq == 0.0) continue;
+                    const double g = 100.0 * fabs(apq);
+                    const bool tiny = fabs(app) + g == fabs(app) && fabs(aqq) + g == fabs(aqq);
+                    double t = 0.0, sn = 0.0, tau = 0.0;
+                    if (!tiny) {
+                        const double theta = 0.5 * (aqq - app) / apq;
+                        t = 1.0 / (fabs(theta) + sqrt(1.0 + theta * theta));
+                        if (theta < 0.0) t = -t;
+                        const double cs = 1.0 / sqrt(1.0 + t * t);
+                        sn = t * cs; tau = sn / (1.0 + cs);
+                    }
+                    if (lane < 12 && !tiny) {
+                        if (lane != p && lane != q) {
+                            const double gp = A[lane * 12 + p], hq = A[lane * 12 + q];
+                            const double np_ = gp - sn * (hq + gp * tau), nq = hq + sn * (gp - hq * tau);
+                            A[lane * 12 + p] = np_; A[p * 12 + lane] = np_;
+                            A[lane * 12 + q] = nq; A[q * 12 + lane] = nq;
+                        }
+                        const double vp = V[lane * 12 + p], vq = V[lane * 12 + q];
+                        V[lane * 12 + p] = vp - sn * (vq + vp * tau);
+                        V[lane * 12 + q] = vq + sn * (vp - vq * tau);
+                    }
+                    if (lane == 0) {
+                        if (!tiny) { A[p * 12 + p] = app - t * apq; A[q * 12 + q] = aqq + t * apq; }
+                        A[p * 12 + q] = 0.0; A[q * 12 + p] = 0.0;
+                    }
+                    wave_sync();
+                }
+        }
+        int jmin = 0;
+        for (int j = 1; j < 12; ++j)
+            if (A[j * 12 + j] < A[jmin * 12 + jmin]) jmin = j;
+        for (int r = 0; r < 3; ++r)
+            for (int q = 0; q < 4; ++q) M[r][q] = V[(4 * r + q) * 12 + jmin];
     }
-    int jmin = 0;
-    for (int j = 1; j < 12; ++j)
-        if (A[j * 12 + j] < A[jmin * 12 + jmin]) jmin = j;
-    double M[3][4];
-    for (int r = 0; r < 3; ++r)
-        for (int q = 0; q < 4; ++q) M[r][q] = V[(4 * r + q) * 12 + jmin];
     wave_sync();                                              // the LDS rows are the refinement's next
     double M3[3][3] = {{M[0][0], M[0][1], M[0][2]}, {M[1][0], M[1][1], M[1][2]}, {M[2][0], M[2][1], M[2][2]}};
     if (det3(M3) < 0.0)

@@ -35,21 +35,26 @@ def rodrigues(w):
 
 
 def rotation_to_angle_axis(R):
-    """Inverse of ``rodrigues`` (host, numpy)."""
-    c = np.clip((np.trace(R) - 1) / 2, -1, 1)
-    th = float(np.arccos(c))
+    """Inverse of ``rodrigues`` (host, numpy), well conditioned at every angle: an error of size e in ``R`` moves the
+    rotation of the result by O(e), the half turn included.  With v = the antisymmetric part (|v| = 2 sin th) and
+    c = (trace - 1) / 2 = cos th the angle is atan2(|v| / 2, c) -- acos(c) alone loses half the digits near 0 and pi.  The
+    axis is v / |v| while c > -0.5; beyond that v shrinks towards rounding, and the axis is the largest row (the first of
+    equals) of the symmetric part less its trace term, (R + R^T) / 2 - c I = (1 - c) a a^T, signed by v.  Below 1e-9 rad
+    the result is v / 2.  The device's ``angle_axis`` (csrc/pvnet_pose.hip) is this function, branch for branch."""
+    R = np.asarray(R, np.float64)
+    c = (R[0, 0] + R[1, 1] + R[2, 2] - 1) / 2
     v = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    s = float(np.sqrt(v @ v)) / 2
+    th = float(np.arctan2(s, c))
     if th < 1e-9:
         return v / 2
-    if np.pi - th < 1e-6:                       # near pi: axis from the symmetric part
-        A = (R + np.eye(3)) / 2
-        a = np.sqrt(np.clip(np.diag(A), 0, None))
-        k = int(np.argmax(a))
-        a = A[k] / a[k]
-        if v @ a < 0:
-            a = -a
-        return a / np.linalg.norm(a) * th
-    return v / (2 * np.sin(th)) * th
+    if c > -0.5:
+        return v * (th / (2 * s))
+    S = (R + R.T) / 2 - c * np.eye(3)
+    a = S[int(np.argmax(np.diag(S)))]
+    if v @ a < 0:
+        a = -a
+    return a * (th / float(np.sqrt(a @ a)))
 
 
 def initial_pose_dlt(points_3d, points_2d, camera_matrix, order_key=None):

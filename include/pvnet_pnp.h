@@ -37,6 +37,11 @@ void uncertainty_pnp(double *pts2d, double *pts3d, double *wgt2d, double *K, dou
  *            3 function tolerance, 4 radius underflow, 0 iteration limit)
  *   max_iterations <= 0 selects Ceres' default 50, function_tolerance <= 0 its default 1e-6 (the relative cost
  *   decrease below which an accepted step ends the iteration; pass e.g. 1e-15 to run to the minimum).  pn in [1, 4096].
+ *   Non-finite input is not screened here (pvp_pose_batched screens it): a NaN or infinity in a keypoint, weight, model
+ *   point or start, or a start that puts a keypoint at z = 0, makes the cost or the gradient non-finite.  No step is then
+ *   accepted, the radius halves away (14 iterations with the defaults) and the image ends with termination 4, d_result_rt
+ *   equal to d_init_rt bit for bit and NaN costs -- never with termination 1: a NaN gradient is not a converged one.  The
+ *   other images of the batch are unaffected.
  * Returns 0, -1 (bad arguments) or a hipError_t. */
 int pvp_uncertainty_pnp_batched(const double *d_pts2d, const double *d_pts3d, const double *d_wgt2d, const double *d_K,
                                 const double *d_init_rt, double *d_result_rt, double *d_info, int B, int pn,

@@ -21,6 +21,18 @@
  *                  start (OpenCV's DLT refuses it too).  A planar model (OpenCV's test: the scatter matrix of the centred 3D
  *                  points has eigenvalues l1 >= l2 >= l3 with l3 / l2 < 1e-3) gets PVP_STATUS_PLANAR: the homography start
  *                  OpenCV takes there is not implemented.
+ *                  The keyed DLT keeps the keypoints with a positive key; with fewer than six of them it takes the six
+ *                  largest keys (a tie goes to the lower index; 0, negative and non-finite keys all count as 0), each
+ *                  + 1e-12, row weight max(sqrt(key / max key), 1e-3).  Those six make the system 12 x 12 with rows of
+ *                  weight 1e-3, condition number ~1e5: its null vector comes from a one-sided Jacobi SVD of the system
+ *                  itself (as accurate as svd(A): the start equals the twin's to ~1e-9), not from the eigenvectors of
+ *                  the normal matrix A^T A, which every other DLT start here uses and which would leave it to ~1e-6.
+ * Rotation matrix -> angle-axis (both starts end with it; un_pnp_utils.rotation_to_angle_axis is its twin): with v the
+ *                  antisymmetric part of R (|v| = 2 sin th) and c = (trace - 1) / 2 the angle is atan2(|v| / 2, c), never
+ *                  acos(c), which loses half the digits at 0 and at pi; below 1e-9 rad the result is v / 2; the axis is
+ *                  v / |v| while c > -0.5 and otherwise the largest row (the first of equals) of (R + R^T) / 2 - c I =
+ *                  (1 - c) a a^T, signed by v.  An error e in R moves the rotation returned by O(e) at every angle; at a
+ *                  half turn w and -w are the same rotation and rounding picks between them.
  * Both starts also run inside pvp_pose_batched when the P3P start falls back.  The refinement is the LM of pvnet_pnp.h
  * (the same device code), with the weights given or, without them, identity weights (1, 0, 1).
  */

@@ -79,9 +79,9 @@ void Solve(const Solver::Options &o, Problem *problem, Solver::Summary *summary)
     int it = 0;
     summary->termination = 0;
     for (; it < max_iter; ++it) {
-        double gmax = 0;
-        for (int i = 0; i < n; ++i) gmax = std::fmax(gmax, std::fabs(g[i]));
-        if (gmax <= o.gradient_tolerance) { summary->termination = 1; break; }
+        bool flat = true;                // max |g| <= tolerance; a NaN entry is not flat (fmax would drop it)
+        for (int i = 0; i < n; ++i) flat = flat && std::fabs(g[i]) <= o.gradient_tolerance;
+        if (flat) { summary->termination = 1; break; }
         double d[6], step[6], neg_g[6];
         for (int i = 0; i < n; ++i) {
             const double di = std::fmin(std::fmax(JtJ[i * n + i] * s2[i], o.min_lm_diagonal), o.max_lm_diagonal);
