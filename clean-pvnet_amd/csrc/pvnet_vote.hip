@@ -489,3 +489,6 @@ PVV_EXPORT int pvv_count_inliers(const float *d_direct, const float *d_coords, c
 
 // ---- optimizer step: clipped Adam / RAdam / SGD for all parameter tensors in one launch (ABI v8, additive) -----
 #include "optim.hpp"
+
+// ---- PVNet output head: upsample, cat, conv3x3, BatchNorm, LeakyReLU, conv1x1 in one launch (ABI v8, additive) -----
+#include "head.hpp"

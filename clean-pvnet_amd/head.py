@@ -1,0 +1,160 @@
+"""PVNet's full-resolution output head on the device (``libpvnet_vote.so``, "PVNet output head" in include/pvnet_vote.h).
+
+The tail of the reference's ``Resnet18.forward`` (lib/networks/pvnet/resnet18.py:53-59, 90-94) -- ``up2storaw``, the ``cat`` with the
+image and ``convraw``: Conv3x3 without bias, BatchNorm2d, LeakyReLU(0.1), Conv1x1 with bias -- is six map-sized torch ops at full
+resolution.  ``pvnet_head`` is one launch that reads ``fm`` and the image and writes the ``seg_dim + ver_dim`` output channels,
+with no full-resolution intermediate in memory; ``PVNetHead`` holds ``convraw`` under the reference's parameter names, so the
+``convraw.*`` entries of a reference checkpoint load unchanged.  The result equals the numpy twin (tests/head_twin.py) bit for bit
+(-0 == +0); parity with torch's own upsample kernel and with MIOpen's convolution is unpinned.  Forward
+only, BatchNorm in eval mode: inference.  CUDA float32 tensors, the current stream, nothing read back, no CPU fallback.
+"""
+import ctypes
+
+import torch
+from torch import nn
+
+from . import _native
+from ._native import INT, LONGLONG, PTR
+
+FLOAT = ctypes.c_float
+_lib = _native.bind("head", "libpvnet_vote.so", {
+    "pvv_head_forward": (INT, [PTR, LONGLONG, PTR, LONGLONG] + [PTR] * 5 + [INT] * 9 + [FLOAT, INT, PTR, PTR]),
+    "pvv_head_upsample": (INT, [PTR, LONGLONG] + [INT] * 6 + [PTR, PTR]),
+}, last_error="pvv_last_error")
+
+MAX_UPSAMPLE = 1 << 28             # elements ``upsample2x`` agrees to write
+MAX_M = 64                         # output channels of either convolution
+OUT_KINDS = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+
+
+def _check(named):
+    _native.check_tensors(named, (torch.float32,), "head")
+    if torch.is_grad_enabled() and any(t.requires_grad for _, t in named):
+        raise RuntimeError("clean_pvnet_amd.head: forward only -- there is no backward pass; call under torch.no_grad() "
+                           "or with tensors that do not require grad")
+
+
+def _fm(fm):
+    if fm.dim() != 4 or fm.shape[1] < 1:
+        raise RuntimeError("clean_pvnet_amd.head: fm must be [B, C2 >= 1, h, w], got %s" % (tuple(fm.shape),))
+    B, C2, h, w = (int(v) for v in fm.shape)
+    t, stride = _native.per_image(fm.detach(), "fm", C2, h, w)
+    return (B, C2, h, w), t, stride
+
+
+def pvnet_head(fm, x, weight1, scale, shift, weight2, bias2, *, negative_slope=0.1, out_dtype=torch.float32):
+    """``convraw(cat([up2storaw(fm), x], 1))`` with the BatchNorm folded into ``scale`` and ``shift`` (``fold_bn``).
+    :param fm:       [B,C2,h,w] float32 CUDA tensor, the half-resolution feature map
+    :param x:        [B,C0,2h,2w], the image; C0 may be 0
+    :param weight1:  [M1, C2+C0, 3, 3], ``fm``'s channels first; [M1] ``scale`` and ``shift``
+    :param weight2:  [M2, M1] or [M2, M1, 1, 1]; ``bias2`` [M2]; M1, M2 <= 64
+    :return:         [B,M2,2h,2w] of ``out_dtype``: float32, or float16 / bfloat16 rounded to nearest even at the store
+    ``fm`` and ``x`` may be views (channel slices of larger tensors): they are read by their image strides.  The contract is in
+    include/pvnet_vote.h: torch's float32 align_corners source index and blend, zero padding ring, one ``fmaf`` chain per output
+    over k = channel*9 + tap from +0, ``fmaf(acc, scale, shift)``, the leaky slope, one ``fmaf`` chain over M1 from the bias."""
+    named = [("fm", fm), ("x", x), ("weight1", weight1), ("scale", scale), ("shift", shift), ("weight2", weight2), ("bias2", bias2)]
+    _check(named)
+    if out_dtype not in OUT_KINDS:
+        raise RuntimeError("clean_pvnet_amd.head: out_dtype must be float32, float16 or bfloat16, got %s" % (out_dtype,))
+    (B, C2, h, w), f, f_stride = _fm(fm)
+    H, W = 2 * h, 2 * w
+    if x.dim() != 4 or x.shape[0] != B:
+        raise RuntimeError("clean_pvnet_amd.head: x must be [B = %d, C0, %d, %d], got %s" % (B, H, W, tuple(x.shape)))
+    C0 = int(x.shape[1])
+    xi, x_stride = _native.per_image(x.detach(), "x", C0, H, W, module="head")
+    if weight1.dim() != 4 or tuple(weight1.shape[1:]) != (C2 + C0, 3, 3):
+        raise RuntimeError("clean_pvnet_amd.head: weight1 must be [M1, C2 + C0 = %d, 3, 3], got %s" % (C2 + C0, tuple(weight1.shape)))
+    M1, M2 = int(weight1.shape[0]), int(weight2.shape[0])
+    if tuple(weight2.shape) not in ((M2, M1), (M2, M1, 1, 1)):
+        raise RuntimeError("clean_pvnet_amd.head: weight2 must be [M2, M1 = %d] or [M2, %d, 1, 1], got %s" % (M1, M1, tuple(weight2.shape)))
+    if tuple(scale.shape) != (M1,) or tuple(shift.shape) != (M1,) or tuple(bias2.shape) != (M2,):
+        raise RuntimeError("clean_pvnet_amd.head: scale and shift must be [%d] and bias2 [%d], got %s, %s, %s"
+                           % (M1, M2, tuple(scale.shape), tuple(shift.shape), tuple(bias2.shape)))
+    if not (1 <= M1 <= MAX_M and 1 <= M2 <= MAX_M):
+        raise ValueError("clean_pvnet_amd.head: M1 and M2 must lie in [1, %d], got %d and %d" % (MAX_M, M1, M2))
+    out = torch.empty(B, M2, H, W, dtype=out_dtype, device=fm.device)
+    if out.numel() == 0:
+        return out
+    w1, sc, sh, w2, b2 = (t.detach().contiguous() for t in (weight1, scale, shift, weight2, bias2))
+    _lib.call("pvv_head_forward", fm.device, f.data_ptr(), f_stride, xi.data_ptr() if C0 else None, x_stride, w1.data_ptr(),
+              sc.data_ptr(), sh.data_ptr(), w2.data_ptr(), b2.data_ptr(), B, C2, C0, h, w, H, W, M1, M2, float(negative_slope),
+              OUT_KINDS[out_dtype], out.data_ptr())
+    return out
+
+
+def upsample2x(fm):
+    """``nn.UpsamplingBilinear2d(scale_factor=2)`` by the contract's float32 formula (``pvv_head_upsample``): [B,C2,2h,2w], the
+    same device function as ``pvnet_head`` blends with, written out so that a test can tell the upsample from the convolutions."""
+    _native.check_tensors([("fm", fm)], (torch.float32,), "head")
+    if fm.dim() == 4 and 4 * fm.numel() > MAX_UPSAMPLE:
+        raise ValueError("clean_pvnet_amd.head: an upsampled tensor of %d elements; at most 2^28 are written" % (4 * fm.numel()))
+    (B, C2, h, w), f, f_stride = _fm(fm)
+    u = torch.empty(B, C2, 2 * h, 2 * w, dtype=torch.float32, device=fm.device)
+    if u.numel() == 0:
+        return u
+    _lib.call("pvv_head_upsample", fm.device, f.data_ptr(), f_stride, B, C2, h, w, 2 * h, 2 * w, u.data_ptr())
+    return u
+
+
+def fold_bn(bn):
+    """(scale, shift) float32 [M] of an eval-mode ``BatchNorm2d``, on its device: in binary64 scale = weight / sqrt(running_var +
+    eps) and shift = bias - running_mean * scale from the unrounded scale, each rounded once.  A BatchNorm without affine
+    parameters or running statistics is refused."""
+    if not isinstance(bn, nn.modules.batchnorm._BatchNorm):
+        raise TypeError("clean_pvnet_amd.head: fold_bn takes a BatchNorm module, got %s" % type(bn).__name__)
+    if bn.weight is None or bn.bias is None:
+        raise ValueError("clean_pvnet_amd.head: fold_bn needs a BatchNorm with affine parameters (affine=True)")
+    if bn.running_mean is None or bn.running_var is None:
+        raise ValueError("clean_pvnet_amd.head: fold_bn needs a BatchNorm with running statistics (track_running_stats=True)")
+    with torch.no_grad():
+        scale = bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
+        shift = bn.bias.double() - bn.running_mean.double() * scale
+        return scale.float(), shift.float()
+
+
+class PVNetHead(nn.Module):
+    """``up2storaw`` and ``convraw`` of the reference's ``Resnet18`` (resnet18.py:53-59) as one module: ``self.convraw`` has the
+    reference's layers and names, ``forward(fm, x)`` is resnet18.py:90-96 up to the dict, through ``pvnet_head``."""
+
+    def __init__(self, ver_dim, seg_dim, s2dim=32, raw_dim=32, image_dim=3):
+        super().__init__()
+        self.ver_dim, self.seg_dim = ver_dim, seg_dim
+        self.convraw = nn.Sequential(
+            nn.Conv2d(image_dim + s2dim, raw_dim, 3, 1, 1, bias=False),
+            nn.BatchNorm2d(raw_dim),
+            nn.LeakyReLU(0.1, True),
+            nn.Conv2d(raw_dim, seg_dim + ver_dim, 1, 1)
+        )
+        self._folded = None
+
+    @classmethod
+    def from_state_dict(cls, sd, seg_dim=2, prefix="convraw.", image_dim=3):
+        """A head sized from the ``<prefix>*`` tensors of a state dict (a whole ``Resnet18`` checkpoint will do), loaded with
+        them, in eval mode.  ``seg_dim`` of the output channels are the segmentation's (2 in PVNet), the rest the vertex field's."""
+        w1, w2 = sd[prefix + "0.weight"], sd[prefix + "3.weight"]
+        m = cls(int(w2.shape[0]) - seg_dim, seg_dim, s2dim=int(w1.shape[1]) - image_dim, raw_dim=int(w1.shape[0]), image_dim=image_dim)
+        m.load_state_dict({"convraw." + k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)})
+        return m.eval()
+
+    def folded(self):
+        """``fold_bn`` of the BatchNorm, computed once and again whenever one of its tensors changes (``_version`` counts the
+        in-place writes; a loaded or moved tensor is another object)."""
+        bn = self.convraw[1]
+        if bn.weight is None or bn.running_mean is None:
+            return fold_bn(bn)                                      # raises
+        tensors = (bn.weight, bn.bias, bn.running_mean, bn.running_var)
+        key = tuple((id(t), t._version, t.device) for t in tensors) + (bn.eps,)
+        if self._folded is None or self._folded[0] != key:
+            self._folded = (key, fold_bn(bn))
+        return self._folded[1]
+
+    def forward(self, fm, x):
+        if self.training:
+            raise RuntimeError("clean_pvnet_amd.head: forward only -- the BatchNorm is folded from its running statistics; "
+                               "call .eval() first")
+        conv1, act, conv2 = self.convraw[0], self.convraw[2], self.convraw[3]
+        named = [("fm", fm), ("x", x), ("weight1", conv1.weight), ("weight2", conv2.weight), ("bias2", conv2.bias)]
+        _check(named)
+        scale, shift = self.folded()
+        out = pvnet_head(fm, x, conv1.weight, scale, shift, conv2.weight, conv2.bias, negative_slope=act.negative_slope)
+        return {"seg": out[:, :self.seg_dim], "vertex": out[:, self.seg_dim:]}

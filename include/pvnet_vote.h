@@ -504,6 +504,53 @@ int pvv_dcn_backward(const float *d_input, const float *d_weight, const float *d
                      void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------
+ * PVNet output head, forward only (ABI v8, additive): the tail of Resnet18.forward (lib/networks/pvnet/resnet18.py:53-59,
+ * 90-94) for inference, BatchNorm in eval mode, in one launch with no full-resolution intermediate in memory:
+ *   fm = up2storaw(fm)                      UpsamplingBilinear2d(scale_factor=2), [B,C2,h,w] -> [B,C2,H,W]
+ *   x  = convraw(cat([fm, x], 1))           Conv3x3(C2+C0 -> M1, padding 1, no bias), BatchNorm2d, LeakyReLU, Conv1x1(M1 -> M2, bias)
+ * Inputs, float32:
+ *   d_fm: image b at d_fm + b * fm_image_stride, [C2,h,w] contiguous      d_x: image b at d_x + b * x_image_stride, [C0,H,W]
+ *   (strides in elements: both may be channel slices of larger tensors; d_x may be NULL when C0 = 0);  H = 2h, W = 2w
+ *   d_weight1 [M1, C2+C0, 3, 3], fm's channels first as the cat puts them   d_scale, d_shift [M1]: the folded BatchNorm
+ *   d_weight2 [M2, M1]   d_bias2 [M2]        1 <= M1, M2 <= PVV_HEAD_MAX_M,  C2 >= 1,  C0 >= 0
+ * Output d_out [B,M2,H,W] contiguous, float32 / float16 / bfloat16 by out_kind.
+ *
+ * In this order, float32 throughout, no fused multiply-add except where fmaf is written:
+ *  Upsample (torch's align_corners=True source index, ATen/native/UpSample.h and the CUDA bilinear kernel), per axis:
+ *    r = (n_in > 1 && n_out > 1) ? (float)(n_in-1) / (float)(n_out-1) : 0;   src = r * (float)dst;   i0 = (int)src (never
+ *    above n_in-1);   i1 = i0 + (i0 < n_in-1);   l1 = src - (float)i0;   l0 = 1 - l1
+ *    u = hl0*(wl0*v00 + wl1*v01) + hl1*(wl0*v10 + wl1*v11),   v_ab = fm[b, c, hi_a, wi_b]
+ *    each operation rounded once in the order written; a zero weight still multiplies its sample (a NaN reaches u).
+ *  Padding: z = cat([u, x]) has a ring of zeros around it -- not an extrapolated upsample.
+ *  Conv1: acc = +0;  for k = c*9 + dy*3 + dx ascending (c over fm's channels, then x's):
+ *    acc = fmaf(weight1[o, k], z[b, c, y+dy-1, x+dx-1], acc)            one accumulator, one rounding per step
+ *  BatchNorm and activation:  t = fmaf(acc, scale[o], shift[o]);   a = t > 0 ? t : t * negative_slope
+ *  Conv2: acc = bias2[o];  for m = 0 .. M1-1 ascending: acc = fmaf(weight2[o, m], a[m], acc)
+ *  Store: float32, or rounded to nearest even to float16 / bfloat16 (overflow to Inf).
+ * Zero terms (0 * 0) may be added to fill an instruction (a K or M1 that is odd); they change at most the sign of a zero, so
+ * results compare as bit patterns with -0 mapped to +0.  The fold of the BatchNorm is host work in binary64:
+ *   scale = gamma / sqrt(var + eps),  shift = beta - mean * scale (from the unrounded scale), each rounded once to float32.
+ * tests/head_twin.py is this contract in numpy, bit for bit.  Bit parity with torch's own device upsample kernel and with
+ * MIOpen's convolution is not claimed: both are free to contract and to reorder.
+ * ---------------------------------------------------------------------- */
+#define PVV_HEAD_OUT_F32 0
+#define PVV_HEAD_OUT_F16 1
+#define PVV_HEAD_OUT_BF16 2
+#define PVV_HEAD_MAX_M 64
+
+/* One fused launch; no workspace, nothing read back.  Per-image element counts must stay below 2^31, B <= 65535, and the
+ * halo of C2+C0 channels must fit a CU's 160 KiB of LDS (about 90 channels). */
+int pvv_head_forward(const float *d_fm, long long fm_image_stride, const float *d_x, long long x_image_stride,
+                     const float *d_weight1, const float *d_scale, const float *d_shift, const float *d_weight2,
+                     const float *d_bias2, int B, int C2, int C0, int h, int w, int H, int W, int M1, int M2,
+                     float negative_slope, int out_kind, void *d_out, void *stream);
+
+/* The upsample alone, for tests: d_u [B,C2,H,W] float32 (at most 2^28 elements), one thread per element through the same
+ * device function as pvv_head_forward. */
+int pvv_head_upsample(const float *d_fm, long long fm_image_stride, int B, int C2, int h, int w, int H, int W, float *d_u,
+                      void *stream);
+
+/* ------------------------------------------------------------------------
  * Optimizer step: the clipped Adam / RAdam / SGD step of every parameter tensor in one launch (ABI v8, additive).  Citations:
  *   T = lib/train/trainers/trainer.py:42-45 (zero_grad, clip_grad_value_(..., 40), optimizer.step)
  *   O = lib/train/optimizer.py:12-27 (make_optimizer: every parameter is a param group of its own)
