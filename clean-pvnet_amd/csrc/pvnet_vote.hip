@@ -128,6 +128,21 @@ PVV_EXPORT size_t pvv_workspace_bytes(const pvv_problem *p)
     return make_layout(p).total;
 }
 
+// ransac_voting_layer_v3 behind its two exports, which have checked their arguments and say in `a` where the mask comes from
+static int run_v3(const pvv_problem *p, const Layout &L, FrontArgs &a, const float *d_vertex, const int32_t *d_idxs,
+                  const float *d_selection, void *d_workspace, float *d_out, int32_t *d_win_counts, int32_t *d_tn, void *stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = (char *)d_workspace;
+    a.vertex = d_vertex; a.idxs = d_idxs; a.selection = d_selection;
+    a.tn_out = d_tn;
+    a.need = CountsNeed::ArgMax;
+    if (int e = run_front(p, L, ws, st, a)) return e;
+    V3Out out;
+    out.kpt = d_out; out.win_counts = d_win_counts;
+    return finish_v3(p, L, ws, st, out);
+}
+
 PVV_EXPORT int pvv_ransac_voting_v3(const pvv_problem *p, const void *d_mask, const float *d_vertex,
                                     const int32_t *d_idxs, const float *d_selection,
                                     void *d_workspace, size_t workspace_bytes, float *d_out,
@@ -136,17 +151,9 @@ PVV_EXPORT int pvv_ransac_voting_v3(const pvv_problem *p, const void *d_mask, co
     Layout L;
     if (int e = check_ptrs(p, d_mask, d_vertex, d_workspace, workspace_bytes, &L)) return e;
     if (!d_out) return fail(PVV_E_ARG, "d_out is NULL");
-    hipStream_t st = (hipStream_t)stream;
-    char *ws = (char *)d_workspace;
     FrontArgs a;
-    a.mask = d_mask; a.vertex = d_vertex;
-    a.idxs = d_idxs; a.selection = d_selection;
-    a.tn_out = d_tn;
-    a.need = CountsNeed::ArgMax;
-    if (int e = run_front(p, L, ws, st, a)) return e;
-    V3Out out;
-    out.kpt = d_out; out.win_counts = d_win_counts;
-    return finish_v3(p, L, ws, st, out);
+    a.mask = d_mask;
+    return run_v3(p, L, a, d_vertex, d_idxs, d_selection, d_workspace, d_out, d_win_counts, d_tn, stream);
 }
 
 PVV_EXPORT int pvv_decode_keypoint_v3(const pvv_problem *p, const float *d_seg, const float *d_vertex,
@@ -159,17 +166,18 @@ PVV_EXPORT int pvv_decode_keypoint_v3(const pvv_problem *p, const float *d_seg, 
     if (int e = check_ptrs(p, d_seg, d_vertex, d_workspace, workspace_bytes, &L)) return e;
     if (!d_out) return fail(PVV_E_ARG, "d_out is NULL");
     if (p->seg_classes < 1 || p->seg_classes > 256) return fail(PVV_E_ARG, "seg_classes must be in [1, 256]");
-    hipStream_t st = (hipStream_t)stream;
-    char *ws = (char *)d_workspace;
     FrontArgs a;
-    a.seg = d_seg; a.mask_out = d_mask_out; a.vertex = d_vertex;
-    a.idxs = d_idxs; a.selection = d_selection;
-    a.tn_out = d_tn;
-    a.need = CountsNeed::ArgMax;
-    if (int e = run_front(p, L, ws, st, a)) return e;
-    V3Out out;
-    out.kpt = d_out; out.win_counts = d_win_counts;
-    return finish_v3(p, L, ws, st, out);
+    a.seg = d_seg; a.mask_out = d_mask_out;
+    return run_v3(p, L, a, d_vertex, d_idxs, d_selection, d_workspace, d_out, d_win_counts, d_tn, stream);
+}
+
+// k_covariance over columns [hoff, hoff + hn) of count rows hstride wide, about d_mean; d_hyp / d_counts: copies out, or nullptr
+static int launch_covariance(const pvv_problem *p, const Layout &L, char *ws, hipStream_t st, const float *d_mean, float *d_cov,
+                             float *d_hyp, int32_t *d_counts, float *d_weights, int hn, int hstride, int hoff)
+{
+    hipLaunchKernelGGL(k_covariance, dim3(p->K, p->B), dim3(kBlock), 0, st, (const int *)(ws + L.tn), (const float2 *)(ws + L.hyps),
+                       (const int *)(ws + L.counts), (const float2 *)d_mean, d_cov, (float2 *)d_hyp, d_counts, d_weights, p->K, hn, hstride, hoff);
+    return check_launch("k_covariance");
 }
 
 PVV_EXPORT int pvv_estimate_voting_distribution(const pvv_problem *p, const void *d_mask,
@@ -194,11 +202,7 @@ PVV_EXPORT int pvv_estimate_voting_distribution(const pvv_problem *p, const void
     a.need = d_counts ? CountsNeed::All : CountsNeed::EstimateWindow;
     a.mean = d_mean;
     if (int e = run_front(p, L, ws, st, a)) return e;
-    hipLaunchKernelGGL(k_covariance, dim3(p->K, p->B), dim3(kBlock), 0, st,
-                       (const int *)(ws + L.tn), (const float2 *)(ws + L.hyps),
-                       (const int *)(ws + L.counts), (const float2 *)d_mean, d_cov, (float2 *)d_hyp,
-                       d_counts, d_weights, p->K, p->hn, /*hstride=*/p->hn, /*hoff=*/0);
-    if (int e = check_launch("k_covariance")) return e;
+    if (int e = launch_covariance(p, L, ws, st, d_mean, d_cov, d_hyp, d_counts, d_weights, p->hn, /*hstride=*/p->hn, /*hoff=*/0)) return e;
     return mark(p, PVV_MARK_END, st);
 }
 
@@ -281,12 +285,7 @@ PVV_EXPORT int pvv_decode_keypoint_un_pnp(const pvv_problem *p, int32_t hn_est, 
         ec.col0 = p->hn; ec.hstride = q.hn; ec.lead_set = 1; ec.mean = d_kpt;
         if (int e = launch_count_any(&pe, L, ws, st, est_pass, ec)) return e;
     }
-    hipLaunchKernelGGL(k_covariance, dim3(p->K, p->B), dim3(kBlock), 0, st, (const int *)(ws + L.tn),
-                       (const float2 *)(ws + L.hyps), (const int *)(ws + L.counts), (const float2 *)d_kpt, d_cov,
-                       /*hyp_out=*/(float2 *)nullptr, /*counts_out=*/(int *)nullptr, d_weights, p->K, (int)hn_est, /*hstride=*/q.hn,
-                       /*hoff=*/p->hn);
-    if (int e = check_launch("k_covariance")) return e;
-    return PVV_OK;
+    return launch_covariance(p, L, ws, st, d_kpt, d_cov, /*d_hyp=*/nullptr, /*d_counts=*/nullptr, d_weights, (int)hn_est, /*hstride=*/q.hn, /*hoff=*/p->hn);
 }
 
 PVV_EXPORT int pvv_rerun_count_kernel(const pvv_problem *p, void *d_workspace, size_t workspace_bytes,

@@ -11,14 +11,20 @@
 //   * device / dtype / contiguity / every dimension are checked with TORCH_CHECK
 //     (-> Python RuntimeError) where the reference has CHECK_INPUT (ransac_voting.cpp:7-9) plus
 //     bare assert()s (kernel.cu:61-65) and exit() on a launch error (cuda_common.h:19-26).
+// Every batched call starts with begin_call (the problem, the checks, the workspace) and differs from the next in its outputs
+// and its C function; the two timing aids are one loop of such calls (timed_calls).
 // This file contains no device code; it is compiled by the host compiler only.
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime_api.h>
 #include <torch/extension.h>
 
+#include <algorithm>
+#include <cstring>
+#include <limits>
 #include <optional>
 #include <tuple>
+#include <utility>
 #include <vector>
 
 #include "pvnet_vote.h"
@@ -49,89 +55,85 @@ void ok(int code, const char *what)
 
 struct Dims { int tn, vn, hn; };
 
-Dims check_gen(const at::Tensor &direct, const at::Tensor &coords, const at::Tensor &idxs)
+// the pixel list of the reference's layouts: direct [tn,vn,2] with coords [tn,2] -> {tn, vn}
+Dims check_pixels(const at::Tensor &direct, const at::Tensor &coords)
 {
     check_dev(direct, "direct", at::kFloat);
     check_dev(coords, "coords", at::kFloat);
-    check_dev(idxs, "idxs", at::kInt);
     same_device(direct, coords, "coords");
-    same_device(direct, idxs, "idxs");
     TORCH_CHECK(direct.dim() == 3 && direct.size(2) == 2, "direct must be [tn,vn,2]");
     const int64_t tn = direct.size(0), vn = direct.size(1);
     TORCH_CHECK(vn > 0, "direct must have vn > 0");
     TORCH_CHECK(coords.dim() == 2 && coords.size(0) == tn && coords.size(1) == 2, "coords must be [tn,2]");
-    TORCH_CHECK(idxs.dim() == 3 && idxs.size(1) == vn && idxs.size(2) == 2, "idxs must be [hn,vn,2]");
-    TORCH_CHECK(tn > 0 || idxs.size(0) == 0, "idxs index an empty pixel list");
-    return {(int)tn, (int)vn, (int)idxs.size(0)};
+    return {(int)tn, (int)vn, 0};
 }
 
-Dims check_vote(const at::Tensor &direct, const at::Tensor &coords, const at::Tensor &hypo_pts,
-                const at::Tensor &inliers, int hdim)
+Dims check_gen(const at::Tensor &direct, const at::Tensor &coords, const at::Tensor &idxs)
 {
-    check_dev(direct, "direct", at::kFloat);
-    check_dev(coords, "coords", at::kFloat);
+    Dims d = check_pixels(direct, coords);
+    check_dev(idxs, "idxs", at::kInt);
+    same_device(direct, idxs, "idxs");
+    TORCH_CHECK(idxs.dim() == 3 && idxs.size(1) == d.vn && idxs.size(2) == 2, "idxs must be [hn,vn,2]");
+    TORCH_CHECK(d.tn > 0 || idxs.size(0) == 0, "idxs index an empty pixel list");
+    d.hn = (int)idxs.size(0);
+    return d;
+}
+
+// inliers: [hn,vn,tn] uint8, or null for a call that keeps no per-pixel result (count_inliers)
+Dims check_vote(const at::Tensor &direct, const at::Tensor &coords, const at::Tensor &hypo_pts,
+                const at::Tensor *inliers, int hdim)
+{
+    Dims d = check_pixels(direct, coords);
     check_dev(hypo_pts, "hypo_pts", at::kFloat);
-    check_dev(inliers, "inliers", at::kByte);
-    same_device(direct, coords, "coords");
     same_device(direct, hypo_pts, "hypo_pts");
-    same_device(direct, inliers, "inliers");
-    TORCH_CHECK(direct.dim() == 3 && direct.size(2) == 2, "direct must be [tn,vn,2]");
-    const int64_t tn = direct.size(0), vn = direct.size(1);
-    TORCH_CHECK(vn > 0, "direct must have vn > 0");
-    TORCH_CHECK(coords.dim() == 2 && coords.size(0) == tn && coords.size(1) == 2, "coords must be [tn,2]");
-    TORCH_CHECK(hypo_pts.dim() == 3 && hypo_pts.size(1) == vn && hypo_pts.size(2) == hdim,
+    TORCH_CHECK(hypo_pts.dim() == 3 && hypo_pts.size(1) == d.vn && hypo_pts.size(2) == hdim,
                 "hypo_pts must be [hn,vn,", hdim, "]");
-    const int64_t hn = hypo_pts.size(0);
-    TORCH_CHECK(inliers.dim() == 3 && inliers.size(0) == hn && inliers.size(1) == vn && inliers.size(2) == tn,
+    d.hn = (int)hypo_pts.size(0);
+    if (!inliers) return d;
+    check_dev(*inliers, "inliers", at::kByte);
+    same_device(direct, *inliers, "inliers");
+    TORCH_CHECK(inliers->dim() == 3 && inliers->size(0) == d.hn && inliers->size(1) == d.vn && inliers->size(2) == d.tn,
                 "inliers must be [hn,vn,tn]");
-    return {(int)tn, (int)vn, (int)hn};
+    return d;
 }
 
 // ---- reference module surface -----------------------------------------------------------
+// Two pairs: the vanishing-point functions differ from the plain ones in the C function and in the hypotheses' last dimension.
 
-at::Tensor generate_hypothesis(at::Tensor direct, at::Tensor coords, at::Tensor idxs)
+typedef int (*gen_fn)(const float *, const float *, const int32_t *, float *, int, int, int, void *);
+typedef int (*vote_fn)(const float *, const float *, const float *, uint8_t *, int, int, int, float, void *);
+
+at::Tensor legacy_generate(gen_fn fn, const char *name, int hdim, const at::Tensor &direct, const at::Tensor &coords,
+                           const at::Tensor &idxs)
 {
     const c10::DeviceGuard device_guard(direct.device());   // launch on the tensors' GPU, whatever the current device is
     Dims d = check_gen(direct, coords, idxs);
-    auto hypo_pts = at::empty({d.hn, d.vn, 2}, direct.options());
-    ok(pvv_generate_hypothesis(direct.data_ptr<float>(), coords.data_ptr<float>(), idxs.data_ptr<int32_t>(),
-                               hypo_pts.data_ptr<float>(), d.tn, d.vn, d.hn, cur_stream(direct)),
-       "generate_hypothesis");
+    auto hypo_pts = at::empty({d.hn, d.vn, hdim}, direct.options());
+    ok(fn(direct.data_ptr<float>(), coords.data_ptr<float>(), idxs.data_ptr<int32_t>(), hypo_pts.data_ptr<float>(), d.tn,
+          d.vn, d.hn, cur_stream(direct)),
+       name);
     return hypo_pts;
 }
 
-void voting_for_hypothesis(at::Tensor direct, at::Tensor coords, at::Tensor hypo_pts, at::Tensor inliers,
-                           float inlier_thresh)
+void legacy_vote(vote_fn fn, const char *name, int hdim, const at::Tensor &direct, const at::Tensor &coords,
+                 const at::Tensor &hypo_pts, const at::Tensor &inliers, float inlier_thresh)
 {
     const c10::DeviceGuard device_guard(direct.device());   // launch on the tensors' GPU, whatever the current device is
-    Dims d = check_vote(direct, coords, hypo_pts, inliers, 2);
-    ok(pvv_voting_for_hypothesis(direct.data_ptr<float>(), coords.data_ptr<float>(), hypo_pts.data_ptr<float>(),
-                                 inliers.data_ptr<uint8_t>(), d.tn, d.vn, d.hn, inlier_thresh,
-                                 cur_stream(direct)),
-       "voting_for_hypothesis");
+    Dims d = check_vote(direct, coords, hypo_pts, &inliers, hdim);
+    ok(fn(direct.data_ptr<float>(), coords.data_ptr<float>(), hypo_pts.data_ptr<float>(), inliers.data_ptr<uint8_t>(), d.tn,
+          d.vn, d.hn, inlier_thresh, cur_stream(direct)),
+       name);
 }
 
-at::Tensor generate_hypothesis_vanishing_point(at::Tensor direct, at::Tensor coords, at::Tensor idxs)
+at::Tensor generate_hypothesis(at::Tensor d, at::Tensor c, at::Tensor i) { return legacy_generate(pvv_generate_hypothesis, "generate_hypothesis", 2, d, c, i); }
+void voting_for_hypothesis(at::Tensor d, at::Tensor c, at::Tensor h, at::Tensor inl, float t) { legacy_vote(pvv_voting_for_hypothesis, "voting_for_hypothesis", 2, d, c, h, inl, t); }
+at::Tensor generate_hypothesis_vanishing_point(at::Tensor d, at::Tensor c, at::Tensor i)
 {
-    const c10::DeviceGuard device_guard(direct.device());   // launch on the tensors' GPU, whatever the current device is
-    Dims d = check_gen(direct, coords, idxs);
-    auto hypo_pts = at::empty({d.hn, d.vn, 3}, direct.options());
-    ok(pvv_generate_hypothesis_vanishing_point(direct.data_ptr<float>(), coords.data_ptr<float>(),
-                                               idxs.data_ptr<int32_t>(), hypo_pts.data_ptr<float>(), d.tn,
-                                               d.vn, d.hn, cur_stream(direct)),
-       "generate_hypothesis_vanishing_point");
-    return hypo_pts;
+    return legacy_generate(pvv_generate_hypothesis_vanishing_point, "generate_hypothesis_vanishing_point", 3, d, c, i);
 }
-
-void voting_for_hypothesis_vanishing_point(at::Tensor direct, at::Tensor coords, at::Tensor hypo_pts,
-                                           at::Tensor inliers, float inlier_thresh)
+void voting_for_hypothesis_vanishing_point(at::Tensor d, at::Tensor c, at::Tensor h, at::Tensor inl, float t)
 {
-    const c10::DeviceGuard device_guard(direct.device());   // launch on the tensors' GPU, whatever the current device is
-    Dims d = check_vote(direct, coords, hypo_pts, inliers, 3);
-    ok(pvv_voting_for_hypothesis_vanishing_point(direct.data_ptr<float>(), coords.data_ptr<float>(),
-                                                 hypo_pts.data_ptr<float>(), inliers.data_ptr<uint8_t>(),
-                                                 d.tn, d.vn, d.hn, inlier_thresh, cur_stream(direct)),
-       "voting_for_hypothesis_vanishing_point");
+    legacy_vote(pvv_voting_for_hypothesis_vanishing_point, "voting_for_hypothesis_vanishing_point", 3, d, c, h, inl, t);
 }
 
 // ---- additions -----------------------------------------------------------------------------
@@ -140,20 +142,10 @@ void voting_for_hypothesis_vanishing_point(at::Tensor direct, at::Tensor coords,
 at::Tensor count_inliers(at::Tensor direct, at::Tensor coords, at::Tensor hypo_pts, float inlier_thresh)
 {
     const c10::DeviceGuard device_guard(direct.device());   // launch on the tensors' GPU, whatever the current device is
-    check_dev(direct, "direct", at::kFloat);
-    check_dev(coords, "coords", at::kFloat);
-    check_dev(hypo_pts, "hypo_pts", at::kFloat);
-    same_device(direct, coords, "coords");
-    same_device(direct, hypo_pts, "hypo_pts");
-    TORCH_CHECK(direct.dim() == 3 && direct.size(2) == 2, "direct must be [tn,vn,2]");
-    const int64_t tn = direct.size(0), vn = direct.size(1);
-    TORCH_CHECK(vn > 0, "direct must have vn > 0");
-    TORCH_CHECK(coords.dim() == 2 && coords.size(0) == tn && coords.size(1) == 2, "coords must be [tn,2]");
-    TORCH_CHECK(hypo_pts.dim() == 3 && hypo_pts.size(1) == vn && hypo_pts.size(2) == 2, "hypo_pts must be [hn,vn,2]");
-    auto counts = at::empty({hypo_pts.size(0), vn}, direct.options().dtype(at::kInt));
+    Dims d = check_vote(direct, coords, hypo_pts, nullptr, 2);
+    auto counts = at::empty({d.hn, d.vn}, direct.options().dtype(at::kInt));
     ok(pvv_count_inliers(direct.data_ptr<float>(), coords.data_ptr<float>(), hypo_pts.data_ptr<float>(),
-                         counts.data_ptr<int32_t>(), (int)tn, (int)vn, (int)hypo_pts.size(0), inlier_thresh,
-                         cur_stream(direct)),
+                         counts.data_ptr<int32_t>(), d.tn, d.vn, d.hn, inlier_thresh, cur_stream(direct)),
        "count_inliers");
     return counts;
 }
@@ -184,13 +176,28 @@ int32_t half_flag(const at::Tensor &t, const char *name, int32_t f16, int32_t bf
 // data pointer of a float32 / float16 / bfloat16 field as the C ABI takes it (the flag bits say what it points to)
 const float *field_ptr(const at::Tensor &t) { return (const float *)t.data_ptr(); }
 
-int32_t seg_flag(const at::Tensor &seg) { return half_flag(seg, "seg", PVV_FLAG_SEG_F16, PVV_FLAG_SEG_BF16); }
+// A contiguous problem of the given sizes with the reference's defaults (min_num = 5, threshold 0.99) and the default cap: all the
+// host-only queries need, and what make_problem starts from.
+pvv_problem contiguous_problem(int64_t B, int64_t H, int64_t W, int64_t K, int64_t hn, int64_t max_num, int64_t mask_elem_size)
+{
+    pvv_problem p;
+    memset(&p, 0, sizeof(p));
+    p.B = (int32_t)B; p.H = (int32_t)H; p.W = (int32_t)W; p.K = (int32_t)K; p.hn = (int32_t)hn;
+    p.mask_elem_size = (int32_t)mask_elem_size;
+    p.min_num = 5; p.max_num = (int32_t)max_num;
+    p.cap = pvv_default_cap(p.H, p.W, p.max_num);
+    p.inlier_thresh = 0.99f;
+    return p;
+}
 
-// float32 outputs on the field's device, whatever the field's dtype
-at::TensorOptions f32_like(const at::Tensor &t) { return t.options().dtype(at::kFloat); }
+// the numbers of a voting call, in the order the module's functions take them
+struct Vote {
+    int64_t hn; double thresh; int64_t min_num, max_num, policy, seed;
+    int64_t first_image = 0;   // index of image 0 in the caller's larger batch (device RNG key)
+    int64_t count_kernel = 0;
+};
 
-pvv_problem make_problem(const at::Tensor &mask, const at::Tensor &vertex, int64_t hn, double thresh,
-                         int64_t min_num, int64_t max_num, int64_t policy, int64_t seed)
+pvv_problem make_problem(const at::Tensor &mask, const at::Tensor &vertex, const Vote &v)
 {
     TORCH_CHECK(mask.is_cuda(), "mask must be a CUDA tensor");
     TORCH_CHECK(vertex.is_cuda(), "vertex must be a CUDA tensor");
@@ -200,43 +207,33 @@ pvv_problem make_problem(const at::Tensor &mask, const at::Tensor &vertex, int64
     TORCH_CHECK(mask.dim() == 3 && mask.size(0) == vertex.size(0) && mask.size(1) == vertex.size(1) &&
                     mask.size(2) == vertex.size(2),
                 "mask must be [b,h,w] matching vertex");
-    TORCH_CHECK(hn > 0 && hn < (1 << 24), "hypothesis count must be in [1, 2^24)");
+    TORCH_CHECK(v.hn > 0 && v.hn < (1 << 24), "hypothesis count must be in [1, 2^24)");
     TORCH_CHECK(vertex.size(0) > 0 && vertex.size(3) > 0, "empty batch / no keypoints");
-    pvv_problem p;
-    memset(&p, 0, sizeof(p));
-    p.B = (int32_t)vertex.size(0); p.H = (int32_t)vertex.size(1); p.W = (int32_t)vertex.size(2);
-    p.K = (int32_t)vertex.size(3);
-    p.hn = (int32_t)hn;
-    p.mask_elem_size = mask_elem_size(mask);
     const int64_t big = std::numeric_limits<int32_t>::max();
-    p.min_num = (int32_t)std::max<int64_t>(-big, std::min<int64_t>(big, min_num));
-    p.max_num = (int32_t)std::max<int64_t>(0, std::min<int64_t>(big, max_num));
-    p.cap = pvv_default_cap(p.H, p.W, p.max_num);
-    p.singular_policy = (int32_t)policy;
-    p.inlier_thresh = (float)thresh;
+    pvv_problem p = contiguous_problem(vertex.size(0), vertex.size(1), vertex.size(2), vertex.size(3), v.hn,
+                                       std::max<int64_t>(0, std::min<int64_t>(big, v.max_num)), mask_elem_size(mask));
+    p.min_num = (int32_t)std::max<int64_t>(-big, std::min<int64_t>(big, v.min_num));
+    p.singular_policy = (int32_t)v.policy;
+    p.inlier_thresh = (float)v.thresh;
     for (int i = 0; i < 3; ++i) p.mask_stride[i] = mask.stride(i);
     for (int i = 0; i < 5; ++i) p.vertex_stride[i] = vertex.stride(i);
-    p.seed = (uint64_t)seed;
+    p.seed = (uint64_t)v.seed;
+    p.first_image = (int32_t)v.first_image;
+    p.count_kernel = (int32_t)v.count_kernel;
     p.flags = vflag;
     return p;
 }
 
-const int32_t *opt_idxs(const std::optional<at::Tensor> &idxs, const at::Tensor &vertex, const pvv_problem &p)
+// idxs: [b,hn,vn,2] int32 pixel-list indices to draw the hn hypotheses from, or none (the device RNG draws)
+const int32_t *opt_idxs(const std::optional<at::Tensor> &idxs, const at::Tensor &vertex, const pvv_problem &p, int64_t hn)
 {
     if (!idxs.has_value()) return nullptr;
     const at::Tensor &t = *idxs;
     check_dev(t, "idxs", at::kInt);
     same_device(vertex, t, "idxs");
-    TORCH_CHECK(t.dim() == 4 && t.size(0) == p.B && t.size(1) == p.hn && t.size(2) == p.K && t.size(3) == 2,
-                "idxs must be [b,hn,vn,2] = [", p.B, ",", p.hn, ",", p.K, ",2]");
+    TORCH_CHECK(t.dim() == 4 && t.size(0) == p.B && t.size(1) == hn && t.size(2) == p.K && t.size(3) == 2,
+                "idxs must be [b,hn,vn,2] = [", p.B, ",", hn, ",", p.K, ",2]");
     return t.data_ptr<int32_t>();
-}
-
-// Injected U(0,1) draws may let ANY number of foreground pixels survive (all zeros keep every pixel), so the rows
-// reserved per image are not bounded by max_num + 8 sigma then: reserve the whole image (call before make_workspace).
-void cap_for_selection(const std::optional<at::Tensor> &sel, pvv_problem &p)
-{
-    if (sel.has_value()) p.cap = (int32_t)std::min<int64_t>((int64_t)p.H * p.W, std::numeric_limits<int32_t>::max());
 }
 
 const float *opt_selection(const std::optional<at::Tensor> &sel, const at::Tensor &vertex, const pvv_problem &p)
@@ -250,31 +247,84 @@ const float *opt_selection(const std::optional<at::Tensor> &sel, const at::Tenso
     return t.data_ptr<float>();
 }
 
-// ABI v8: with nothing injected the device RNG draws everything -- the library then knows before the call that no per-pixel
-// subsample draw is ever stored for images small enough to subsample inside the compaction kernel, and leaves that storage
-// (4 B per pixel of the batch) out of the workspace.  Call before make_workspace.
-void promise_device_rng(pvv_problem &p, const std::optional<at::Tensor> &idxs, const std::optional<at::Tensor> &idxs2,
-                        const std::optional<at::Tensor> &selection)
-{
-    if (!idxs.has_value() && !idxs2.has_value() && !selection.has_value()) p.flags |= PVV_FLAG_DEVICE_RNG;
-}
-
 // `out` (optional): the caller's [b,vn,2] float32 result buffer -- e.g. this rank's rows of a persistent all_gather buffer
 // (clean_pvnet_amd.dist.GatherBuffer), so that the exchange needs no copy -- instead of a fresh tensor
-at::Tensor result_buffer(const std::optional<at::Tensor> &out, const pvv_problem &p, const at::Tensor &vertex)
+void check_result_buffer(const at::Tensor &out, const pvv_problem &p, const at::Tensor &vertex)
 {
-    if (!out.has_value()) return at::empty({p.B, p.K, 2}, f32_like(vertex));
-    check_dev(*out, "out", at::kFloat);
-    same_device(vertex, *out, "out");
-    TORCH_CHECK(out->dim() == 3 && out->size(0) == p.B && out->size(1) == p.K && out->size(2) == 2, "out must be [b,vn,2] = [", p.B, ",", p.K, ",2]");
-    return *out;
+    check_dev(out, "out", at::kFloat);
+    same_device(vertex, out, "out");
+    TORCH_CHECK(out.dim() == 3 && out.size(0) == p.B && out.size(1) == p.K && out.size(2) == 2, "out must be [b,vn,2] = [", p.B, ",", p.K, ",2]");
 }
 
-at::Tensor make_workspace(const pvv_problem &p, const at::Tensor &like)
+// What every batched call has once begin_call is through: the problem, the injected draws' pointers, the workspace -- and the
+// shapes of its outputs (float32 / int32 on the field's device, whatever the field's dtype).
+struct Call {
+    pvv_problem p;
+    at::Tensor mask_out;               // the int64 [b,h,w] mask a call on seg emits (undefined for a call on a mask)
+    const int32_t *idxs = nullptr, *idxs_est = nullptr;
+    const float *selection = nullptr;
+    at::Tensor ws;
+    at::TensorOptions f32, i32;
+    at::Tensor kpt() const { return at::empty({p.B, p.K, 2}, f32); }
+    at::Tensor cov() const { return at::empty({p.B, p.K, 2, 2}, f32); }
+    at::Tensor weights() const { return at::empty({p.B, p.K, 3}, f32); }
+    at::Tensor win() const { return at::empty({p.B, p.K}, i32); }
+    at::Tensor tn() const { return at::empty({p.B}, i32); }
+};
+
+const std::optional<at::Tensor> kNoTensor;
+
+// The head of every batched call, on `mask` or -- `mask` null -- on `seg` [b,c,h,w], whose class argmax the library then fuses
+// into its mask scan and writes out as Call::mask_out.  hyp_est > 0: the fused un_pnp call, whose workspace also holds the estimate's
+// hyp_est hypotheses per keypoint (drawn from idxs_est).
+Call begin_call(const at::Tensor *mask, const at::Tensor *seg, const at::Tensor &vertex, const Vote &v,
+                const std::optional<at::Tensor> &idxs = kNoTensor, const std::optional<at::Tensor> &selection = kNoTensor,
+                const std::optional<at::Tensor> &status = kNoTensor, std::optional<int64_t> cap = std::nullopt,
+                int64_t hyp_est = 0, const std::optional<at::Tensor> &idxs_est = kNoTensor)
 {
-    size_t n = pvv_workspace_bytes(&p);
+    at::Tensor mask_out;
+    if (seg) {
+        TORCH_CHECK(seg->is_cuda(), "seg must be a CUDA tensor");
+        TORCH_CHECK(seg->dim() == 4 && vertex.dim() == 5 && seg->size(0) == vertex.size(0) && seg->size(2) == vertex.size(1) &&
+                        seg->size(3) == vertex.size(2),
+                    "seg must be [b,c,h,w] matching vertex [b,h,w,vn,2]");
+        mask_out = at::empty({seg->size(0), seg->size(2), seg->size(3)}, seg->options().dtype(at::kLong));
+    }
+    Call c{make_problem(seg ? mask_out : *mask, vertex, v)};    // (built in place: no copy of the problem)
+    c.mask_out = std::move(mask_out);
+    pvv_problem &p = c.p;
+    if (seg) {
+        p.seg_classes = (int32_t)seg->size(1);
+        for (int i = 0; i < 4; ++i) p.seg_stride[i] = seg->stride(i);
+        p.flags |= half_flag(*seg, "seg", PVV_FLAG_SEG_F16, PVV_FLAG_SEG_BF16);
+    }
+    if (status.has_value()) {                               // per-image PVV_STATUS_* bits (e.g. list truncated at cap)
+        check_dev(*status, "status", at::kInt);
+        same_device(vertex, *status, "status");
+        TORCH_CHECK(status->dim() == 1 && status->size(0) == p.B, "status must be [b]");
+        p.d_status = status->data_ptr<int32_t>();
+    }
+    // Injected U(0,1) draws may let ANY number of foreground pixels survive (all zeros keep every pixel), so the rows reserved
+    // per image are not bounded by max_num + 8 sigma then: reserve the whole image.
+    if (selection.has_value()) p.cap = (int32_t)std::min<int64_t>((int64_t)p.H * p.W, std::numeric_limits<int32_t>::max());
+    if (cap.has_value()) {                                  // rows reserved per image (default: pvv_default_cap)
+        TORCH_CHECK(*cap >= 1 && *cap <= (int64_t)p.H * p.W, "cap must be in [1, h*w]");
+        p.cap = (int32_t)*cap;
+    }
+    c.idxs = opt_idxs(idxs, vertex, p, p.hn);
+    if (hyp_est > 0) c.idxs_est = opt_idxs(idxs_est, vertex, p, hyp_est);
+    c.selection = opt_selection(selection, vertex, p);
+    // ABI v8: with nothing injected the device RNG draws everything -- the library then knows before the call that no per-pixel
+    // subsample draw is ever stored for images small enough to subsample inside the compaction kernel, and leaves that storage
+    // (4 B per pixel of the batch) out of the workspace.
+    if (!idxs.has_value() && !idxs_est.has_value() && !selection.has_value()) p.flags |= PVV_FLAG_DEVICE_RNG;
+    const size_t n = hyp_est > 0 ? pvv_workspace_bytes_un_pnp(&p, (int32_t)hyp_est) : pvv_workspace_bytes(&p);
     TORCH_CHECK(n > 0, "invalid voting problem: ", pvv_last_error());
-    return at::empty({(int64_t)n}, like.options().dtype(at::kByte));
+    const at::TensorOptions like = vertex.options();
+    c.f32 = like.dtype(at::kFloat);
+    c.i32 = like.dtype(at::kInt);
+    c.ws = at::empty({(int64_t)n}, like.dtype(at::kByte));
+    return c;
 }
 
 // ransac_voting_layer_v3 for the whole batch -> (kpt [b,vn,2], win_counts [b,vn], tn [b], workspace)
@@ -285,33 +335,16 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> ransac_voting_v3(
     std::optional<int64_t> cap, std::optional<at::Tensor> out_buf)
 {
     const c10::DeviceGuard device_guard(vertex.device());   // launch on the tensors' GPU, whatever the current device is
-    pvv_problem p = make_problem(mask, vertex, round_hyp_num, inlier_thresh, min_num, max_num,
-                                 singular_policy, seed);
-    p.first_image = (int32_t)first_image;
-    p.count_kernel = (int32_t)count_kernel;
-    if (status.has_value()) {                               // per-image PVV_STATUS_* bits (e.g. list truncated at cap)
-        check_dev(*status, "status", at::kInt);
-        same_device(vertex, *status, "status");
-        TORCH_CHECK(status->dim() == 1 && status->size(0) == p.B, "status must be [b]");
-        p.d_status = status->data_ptr<int32_t>();
-    }
-    cap_for_selection(selection, p);
-    if (cap.has_value()) {                                  // rows reserved per image (default: pvv_default_cap)
-        TORCH_CHECK(*cap >= 1 && *cap <= (int64_t)p.H * p.W, "cap must be in [1, h*w]");
-        p.cap = (int32_t)*cap;
-    }
-    const int32_t *ip = opt_idxs(idxs, vertex, p);
-    const float *sp = opt_selection(selection, vertex, p);
-    promise_device_rng(p, idxs, std::nullopt, selection);
-    at::Tensor ws = make_workspace(p, vertex);
-    auto out = result_buffer(out_buf, p, vertex);
-    auto win = at::empty({p.B, p.K}, vertex.options().dtype(at::kInt));
-    auto tn = at::empty({p.B}, vertex.options().dtype(at::kInt));
-    ok(pvv_ransac_voting_v3(&p, mask.data_ptr(), field_ptr(vertex), ip, sp, ws.data_ptr(),
-                            (size_t)ws.numel(), out.data_ptr<float>(), win.data_ptr<int32_t>(),
+    Call c = begin_call(&mask, nullptr, vertex, {round_hyp_num, inlier_thresh, min_num, max_num, singular_policy, seed, first_image, count_kernel},
+                        idxs, selection, status, cap);
+    if (out_buf.has_value()) check_result_buffer(*out_buf, c.p, vertex);
+    auto out = out_buf.has_value() ? *out_buf : c.kpt();
+    auto win = c.win(), tn = c.tn();
+    ok(pvv_ransac_voting_v3(&c.p, mask.data_ptr(), field_ptr(vertex), c.idxs, c.selection, c.ws.data_ptr(),
+                            (size_t)c.ws.numel(), out.data_ptr<float>(), win.data_ptr<int32_t>(),
                             tn.data_ptr<int32_t>(), cur_stream(vertex)),
        "ransac_voting_v3");
-    return {out, win, tn, ws};
+    return {out, win, tn, c.ws};
 }
 
 // Resnet18.decode_keypoint's front half fused: mask = argmax(seg, 1) + ransac_voting_layer_v3(mask, vertex, ...)
@@ -322,30 +355,15 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> decode_keypoint_v3(
     int64_t first_image, int64_t count_kernel)
 {
     const c10::DeviceGuard device_guard(vertex.device());   // launch on the tensors' GPU, whatever the current device is
-    TORCH_CHECK(seg.is_cuda(), "seg must be a CUDA tensor");
-    TORCH_CHECK(seg.dim() == 4 && vertex.dim() == 5 && seg.size(0) == vertex.size(0) && seg.size(2) == vertex.size(1) &&
-                    seg.size(3) == vertex.size(2),
-                "seg must be [b,c,h,w] matching vertex [b,h,w,vn,2]");
-    auto mask = at::empty({seg.size(0), seg.size(2), seg.size(3)}, seg.options().dtype(at::kLong));
-    pvv_problem p = make_problem(mask, vertex, round_hyp_num, inlier_thresh, min_num, max_num, singular_policy, seed);
-    p.first_image = (int32_t)first_image;
-    p.count_kernel = (int32_t)count_kernel;
-    p.seg_classes = (int32_t)seg.size(1);
-    for (int i = 0; i < 4; ++i) p.seg_stride[i] = seg.stride(i);
-    p.flags |= seg_flag(seg);
-    cap_for_selection(selection, p);
-    const int32_t *ip = opt_idxs(idxs, vertex, p);
-    const float *sp = opt_selection(selection, vertex, p);
-    promise_device_rng(p, idxs, std::nullopt, selection);
-    at::Tensor ws = make_workspace(p, vertex);
-    auto out = at::empty({p.B, p.K, 2}, f32_like(vertex));
-    auto win = at::empty({p.B, p.K}, vertex.options().dtype(at::kInt));
-    auto tn = at::empty({p.B}, vertex.options().dtype(at::kInt));
-    ok(pvv_decode_keypoint_v3(&p, field_ptr(seg), field_ptr(vertex), ip, sp, ws.data_ptr(),
-                              (size_t)ws.numel(), mask.data_ptr<int64_t>(), out.data_ptr<float>(),
+    Call c = begin_call(nullptr, &seg, vertex, {round_hyp_num, inlier_thresh, min_num, max_num, singular_policy, seed, first_image, count_kernel},
+                        idxs, selection);
+    auto out = c.kpt();
+    auto win = c.win(), tn = c.tn();
+    ok(pvv_decode_keypoint_v3(&c.p, field_ptr(seg), field_ptr(vertex), c.idxs, c.selection, c.ws.data_ptr(),
+                              (size_t)c.ws.numel(), c.mask_out.data_ptr<int64_t>(), out.data_ptr<float>(),
                               win.data_ptr<int32_t>(), tn.data_ptr<int32_t>(), cur_stream(vertex)),
        "decode_keypoint_v3");
-    return {out, mask, win, tn};
+    return {out, c.mask_out, win, tn};
 }
 
 // Resnet18.decode_keypoint with cfg.test.un_pnp in one pass (pvv_decode_keypoint_un_pnp): one mask scan, one compaction,
@@ -357,39 +375,24 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tenso
     std::optional<at::Tensor> selection, int64_t seed, int64_t singular_policy, int64_t first_image, int64_t count_kernel)
 {
     const c10::DeviceGuard device_guard(vertex.device());
-    TORCH_CHECK(seg.is_cuda(), "seg must be a CUDA tensor");
-    TORCH_CHECK(seg.dim() == 4 && vertex.dim() == 5 && seg.size(0) == vertex.size(0) && seg.size(2) == vertex.size(1) &&
-                    seg.size(3) == vertex.size(2),
-                "seg must be [b,c,h,w] matching vertex [b,h,w,vn,2]");
     TORCH_CHECK(hyp_est > 0 && hyp_est < (1 << 24), "hypothesis count of the estimate must be in [1, 2^24)");
-    auto mask = at::empty({seg.size(0), seg.size(2), seg.size(3)}, seg.options().dtype(at::kLong));
-    pvv_problem p = make_problem(mask, vertex, round_hyp_num, inlier_thresh, min_num, max_num, singular_policy, seed);
-    p.first_image = (int32_t)first_image;
-    p.count_kernel = (int32_t)count_kernel;
-    p.seg_classes = (int32_t)seg.size(1);
-    for (int i = 0; i < 4; ++i) p.seg_stride[i] = seg.stride(i);
-    p.flags |= seg_flag(seg);
-    cap_for_selection(selection, p);
-    const int32_t *ip = opt_idxs(idxs, vertex, p);
-    pvv_problem pe = p;
-    pe.hn = (int32_t)hyp_est;
-    const int32_t *ie = opt_idxs(idxs_est, vertex, pe);
-    const float *sp = opt_selection(selection, vertex, p);
-    promise_device_rng(p, idxs, idxs_est, selection);
-    const size_t n = pvv_workspace_bytes_un_pnp(&p, (int32_t)hyp_est);
-    TORCH_CHECK(n > 0, "invalid voting problem: ", pvv_last_error());
-    at::Tensor ws = at::empty({(int64_t)n}, vertex.options().dtype(at::kByte));
-    auto kpt = at::empty({p.B, p.K, 2}, f32_like(vertex));
-    auto cov = at::empty({p.B, p.K, 2, 2}, f32_like(vertex));
-    auto weights = at::empty({p.B, p.K, 3}, f32_like(vertex));
-    auto win = at::empty({p.B, p.K}, vertex.options().dtype(at::kInt));
-    auto tn = at::empty({p.B}, vertex.options().dtype(at::kInt));
-    ok(pvv_decode_keypoint_un_pnp(&p, (int32_t)hyp_est, field_ptr(seg), field_ptr(vertex), ip, ie, sp,
-                                  ws.data_ptr(), n, mask.data_ptr<int64_t>(), kpt.data_ptr<float>(), cov.data_ptr<float>(),
-                                  weights.data_ptr<float>(), win.data_ptr<int32_t>(), tn.data_ptr<int32_t>(),
+    Call c = begin_call(nullptr, &seg, vertex, {round_hyp_num, inlier_thresh, min_num, max_num, singular_policy, seed, first_image, count_kernel},
+                        idxs, selection, kNoTensor, std::nullopt, hyp_est, idxs_est);
+    auto kpt = c.kpt(), cov = c.cov(), weights = c.weights();
+    auto win = c.win(), tn = c.tn();
+    ok(pvv_decode_keypoint_un_pnp(&c.p, (int32_t)hyp_est, field_ptr(seg), field_ptr(vertex), c.idxs, c.idxs_est, c.selection,
+                                  c.ws.data_ptr(), (size_t)c.ws.numel(), c.mask_out.data_ptr<int64_t>(), kpt.data_ptr<float>(),
+                                  cov.data_ptr<float>(), weights.data_ptr<float>(), win.data_ptr<int32_t>(), tn.data_ptr<int32_t>(),
                                   cur_stream(vertex)),
        "decode_keypoint_un_pnp");
-    return {kpt, mask, cov, weights, win, tn};
+    return {kpt, c.mask_out, cov, weights, win, tn};
+}
+
+void check_mean(const at::Tensor &mean, const pvv_problem &p, const at::Tensor &vertex)
+{
+    check_dev(mean, "mean", at::kFloat);
+    same_device(vertex, mean, "mean");
+    TORCH_CHECK(mean.dim() == 3 && mean.size(0) == p.B && mean.size(1) == p.K && mean.size(2) == 2, "mean must be [b,vn,2]");
 }
 
 // estimate_voting_distribution_with_mean for the whole batch
@@ -400,31 +403,15 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> estimate_
     int64_t seed, bool want_hyp, int64_t first_image, int64_t count_kernel)
 {
     const c10::DeviceGuard device_guard(vertex.device());   // launch on the tensors' GPU, whatever the current device is
-    pvv_problem p = make_problem(mask, vertex, hyp_total, inlier_thresh, min_num, max_num, 0, seed);
-    p.first_image = (int32_t)first_image;
-    p.count_kernel = (int32_t)count_kernel;
-    cap_for_selection(selection, p);
-    check_dev(mean, "mean", at::kFloat);
-    same_device(vertex, mean, "mean");
-    TORCH_CHECK(mean.dim() == 3 && mean.size(0) == p.B && mean.size(1) == p.K && mean.size(2) == 2,
-                "mean must be [b,vn,2]");
-    const int32_t *ip = opt_idxs(idxs, vertex, p);
-    const float *sp = opt_selection(selection, vertex, p);
-    promise_device_rng(p, idxs, std::nullopt, selection);
-    at::Tensor ws = make_workspace(p, vertex);
-    auto cov = at::empty({p.B, p.K, 2, 2}, f32_like(vertex));
-    auto tn = at::empty({p.B}, vertex.options().dtype(at::kInt));
-    at::Tensor hyp, counts;
-    if (want_hyp) {
-        hyp = at::empty({p.B, p.K, p.hn, 2}, f32_like(vertex));
-        counts = at::empty({p.B, p.K, p.hn}, vertex.options().dtype(at::kInt));
-    } else {
-        hyp = at::empty({0}, f32_like(vertex));
-        counts = at::empty({0}, vertex.options().dtype(at::kInt));
-    }
-    auto weights = at::empty({p.B, p.K, 3}, f32_like(vertex));
-    ok(pvv_estimate_voting_distribution(&p, mask.data_ptr(), field_ptr(vertex), ip, sp,
-                                        mean.data_ptr<float>(), ws.data_ptr(), (size_t)ws.numel(),
+    Call c = begin_call(&mask, nullptr, vertex, {hyp_total, inlier_thresh, min_num, max_num, 0, seed, first_image, count_kernel}, idxs, selection);
+    const pvv_problem &p = c.p;
+    check_mean(mean, p, vertex);
+    auto cov = c.cov(), weights = c.weights();
+    auto tn = c.tn();
+    auto hyp = want_hyp ? at::empty({p.B, p.K, p.hn, 2}, c.f32) : at::empty({0}, c.f32);
+    auto counts = want_hyp ? at::empty({p.B, p.K, p.hn}, c.i32) : at::empty({0}, c.i32);
+    ok(pvv_estimate_voting_distribution(&p, mask.data_ptr(), field_ptr(vertex), c.idxs, c.selection,
+                                        mean.data_ptr<float>(), c.ws.data_ptr(), (size_t)c.ws.numel(),
                                         cov.data_ptr<float>(), want_hyp ? hyp.data_ptr<float>() : nullptr,
                                         want_hyp ? counts.data_ptr<int32_t>() : nullptr,
                                         tn.data_ptr<int32_t>(), weights.data_ptr<float>(), cur_stream(vertex)),
@@ -432,127 +419,117 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> estimate_
     return {cov, hyp, counts, tn, weights};
 }
 
-// `reps` full ransac_voting_layer_v3 calls cycling over the given batches, each with a HIP event pair recorded around its
-// inlier-count launch (pvv_problem.ev_count_begin / ev_count_end) -> the kernel's duration inside the pipeline, ms per call.
-// One synchronisation at the end; a measurement aid (bench.py), not part of the voting path.
+// ---- timing aids: HIP events recorded inside full calls (bench.py, tools/); not part of the voting path ------------------
+
+// the events of a timing aid: created by timed_calls, destroyed on every way out of the aid
+struct Events {
+    std::vector<hipEvent_t> ev;
+    Events() = default;
+    Events(const Events &) = delete;
+    ~Events() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+};
+
+// `reps` full calls cycling over the given batches, call r on the r-th share of the events it creates and with seed v.seed + r; one synchronisation
+// at the end.  marks: the share is PVV_N_MARKS events, one per stage boundary (pvv_problem.ev_marks) -- else a pair around the
+// inlier-count launch (ev_count_begin / ev_count_end).  The call is pvv_ransac_voting_v3 on masks, or
+//   segs (one [b,c,h,w] float32 / float16 / bfloat16 tensor per vertex field): pvv_decode_keypoint_v3 -- the class argmax fused into
+//     the mask scan, the int64 mask written out; `masks` may then be empty;
+//   estimate: estimate_voting_distribution_with_mean with v.hn hypotheses in total, taken about means (one [b,vn,2] float32 tensor
+//     per vertex field: its staged pass orders the chunks by them) or, means empty, about zeros (row-major order: timing only).
+void timed_calls(Events &events, bool marks, bool inner_marks, const std::vector<at::Tensor> &masks,
+                 const std::vector<at::Tensor> &vertices, const std::vector<at::Tensor> &segs, const std::vector<at::Tensor> &means,
+                 Vote v, int64_t reps, bool estimate)
+{
+    const bool fused = !segs.empty();
+    const size_t per = marks ? (size_t)PVV_N_MARKS : 2;
+    std::vector<hipEvent_t> &ev = events.ev;
+    for (hipEvent_t e; ev.size() < per * (size_t)reps; ev.push_back(e)) TORCH_CHECK(hipEventCreate(&e) == hipSuccess, "hipEventCreate failed");
+    std::vector<at::Tensor> keep;
+    for (int64_t r = 0; r < reps; ++r, ++v.seed) {
+        const at::Tensor &vertex = vertices[r % vertices.size()];
+        const at::Tensor *mask = fused ? nullptr : &masks[r % masks.size()];
+        Call c = begin_call(mask, fused ? &segs[r % segs.size()] : nullptr, vertex, v);
+        pvv_problem &p = c.p;
+        void *mk[PVV_N_MARKS];
+        for (size_t i = 0; i < per; ++i) mk[i] = (void *)ev[per * (size_t)r + i];
+        if (marks) {
+            // inner_marks = false: no records INSIDE the count pass (each costs ~2 us): its duration is then what rocprofv3 sees
+            if (!inner_marks) mk[PVV_MARK_STAGE0] = mk[PVV_MARK_PRUNE0] = nullptr;
+            p.ev_marks = mk;
+        } else {
+            p.ev_count_begin = mk[0];
+            p.ev_count_end = mk[1];
+        }
+        auto out = c.kpt();
+        if (estimate) {
+            if (means.empty()) out.zero_();
+            else {
+                const at::Tensor &mn = means[r % means.size()];
+                check_mean(mn, p, vertex);
+                out.copy_(mn);
+            }
+            auto cov = c.cov();
+            ok(pvv_estimate_voting_distribution(&p, mask->data_ptr(), field_ptr(vertex), nullptr, nullptr, out.data_ptr<float>(),
+                                                c.ws.data_ptr(), (size_t)c.ws.numel(), cov.data_ptr<float>(), nullptr, nullptr, nullptr,
+                                                nullptr, cur_stream(vertex)),
+               "estimate_voting_distribution");
+            keep.push_back(cov);
+        } else if (fused) {
+            ok(pvv_decode_keypoint_v3(&p, field_ptr(segs[r % segs.size()]), field_ptr(vertex), nullptr, nullptr, c.ws.data_ptr(),
+                                      (size_t)c.ws.numel(), c.mask_out.data_ptr<int64_t>(), out.data_ptr<float>(), nullptr, nullptr,
+                                      cur_stream(vertex)),
+               "decode_keypoint_v3");
+            keep.push_back(c.mask_out);
+        } else {
+            ok(pvv_ransac_voting_v3(&p, mask->data_ptr(), field_ptr(vertex), nullptr, nullptr, c.ws.data_ptr(),
+                                    (size_t)c.ws.numel(), out.data_ptr<float>(), nullptr, nullptr, cur_stream(vertex)),
+               "ransac_voting_v3");
+        }
+        keep.push_back(c.ws);
+        keep.push_back(out);
+    }
+    TORCH_CHECK(hipStreamSynchronize((hipStream_t)cur_stream(vertices[0])) == hipSuccess, "hipStreamSynchronize failed");
+}
+
+// The inlier-count kernel's duration inside the pipeline, ms per call of `reps` full ransac_voting_layer_v3 calls.
 std::vector<double> count_kernel_ms_in_pipeline(std::vector<at::Tensor> masks, std::vector<at::Tensor> vertices,
                                                 int64_t round_hyp_num, double inlier_thresh, int64_t min_num,
                                                 int64_t max_num, int64_t seed, int64_t reps)
 {
     TORCH_CHECK(!masks.empty() && masks.size() == vertices.size(), "need as many masks as vertex fields");
     const c10::DeviceGuard device_guard(vertices[0].device());
-    std::vector<hipEvent_t> ev(2 * (size_t)reps);
-    for (auto &e : ev) TORCH_CHECK(hipEventCreate(&e) == hipSuccess, "hipEventCreate failed");
-    std::vector<at::Tensor> keep;
-    for (int64_t r = 0; r < reps; ++r) {
-        const at::Tensor &mask = masks[r % masks.size()], &vertex = vertices[r % masks.size()];
-        pvv_problem p = make_problem(mask, vertex, round_hyp_num, inlier_thresh, min_num, max_num, PVV_SINGULAR_REFERENCE,
-                                     seed + r);
-        p.ev_count_begin = (void *)ev[2 * r];
-        p.ev_count_end = (void *)ev[2 * r + 1];
-        p.flags |= PVV_FLAG_DEVICE_RNG;
-        at::Tensor ws = make_workspace(p, vertex);
-        auto out = at::empty({p.B, p.K, 2}, f32_like(vertex));
-        ok(pvv_ransac_voting_v3(&p, mask.data_ptr(), field_ptr(vertex), nullptr, nullptr, ws.data_ptr(),
-                                (size_t)ws.numel(), out.data_ptr<float>(), nullptr, nullptr, cur_stream(vertex)),
-           "ransac_voting_v3");
-        keep.push_back(ws);
-        keep.push_back(out);
-    }
-    TORCH_CHECK(hipStreamSynchronize((hipStream_t)cur_stream(vertices[0])) == hipSuccess, "hipStreamSynchronize failed");
+    Events ev;
+    timed_calls(ev, false, false, masks, vertices, {}, {}, {round_hyp_num, inlier_thresh, min_num, max_num, PVV_SINGULAR_REFERENCE, seed},
+                reps, false);
     std::vector<double> ms((size_t)reps);
     for (int64_t r = 0; r < reps; ++r) {
         float t = 0.f;
-        TORCH_CHECK(hipEventElapsedTime(&t, ev[2 * r], ev[2 * r + 1]) == hipSuccess, "hipEventElapsedTime failed");
+        TORCH_CHECK(hipEventElapsedTime(&t, ev.ev[2 * r], ev.ev[2 * r + 1]) == hipSuccess, "hipEventElapsedTime failed");
         ms[(size_t)r] = t;
     }
-    for (auto &e : ev) (void)hipEventDestroy(e);
     return ms;
 }
 
-// `reps` full ransac_voting_layer_v3 calls cycling over the given batches with a HIP event at every stage boundary
-// (pvv_problem.ev_marks) -> per call the PVV_N_MARKS - 1 durations in ms: [scan, compact+hyp, count pass, select_refit,
-// finalize, (staged only:) first count launch, first prune, 0].  One synchronisation at the end; a measurement aid.
+// Per call of `reps` full calls (see timed_calls) the PVV_N_MARKS - 1 durations in ms: [scan, compact+hyp, count pass, select_refit,
+// finalize, (staged only:) first count launch, first prune, 0].
 std::vector<std::vector<double>> stage_ms_in_pipeline(std::vector<at::Tensor> masks, std::vector<at::Tensor> vertices,
                                                       int64_t round_hyp_num, double inlier_thresh, int64_t min_num,
                                                       int64_t max_num, int64_t seed, int64_t reps, int64_t count_kernel,
                                                       bool inner_marks, bool estimate, std::vector<at::Tensor> segs,
                                                       std::vector<at::Tensor> means)
 {
-    // means (optional, with estimate: one [b,vn,2] float32 tensor per vertex field): the keypoints the estimate is taken about --
-    // its staged pass orders the chunks by them; empty: zeros (row-major order, the timing of rounds 2-4)
     TORCH_CHECK(means.empty() || (estimate && means.size() == vertices.size()), "means: one per vertex field, estimate only");
-    // segs (optional, one [b,c,h,w] float32 / float16 / bfloat16 tensor per vertex field): time pvv_decode_keypoint_v3 -- the class argmax fused
-    // into the mask scan, the int64 mask written out -- instead of pvv_ransac_voting_v3; `masks` may then be empty
     const bool fused = !segs.empty();
     TORCH_CHECK(!vertices.empty() && (fused ? segs.size() == vertices.size() : masks.size() == vertices.size()),
                 "need as many masks (or segs) as vertex fields");
     TORCH_CHECK(!(fused && estimate), "segs and estimate are exclusive");
     const c10::DeviceGuard device_guard(vertices[0].device());
-    std::vector<hipEvent_t> ev((size_t)PVV_N_MARKS * (size_t)reps);
-    for (auto &e : ev) TORCH_CHECK(hipEventCreate(&e) == hipSuccess, "hipEventCreate failed");
-    std::vector<at::Tensor> keep;
-    for (int64_t r = 0; r < reps; ++r) {
-        const at::Tensor &vertex = vertices[r % vertices.size()];
-        at::Tensor mask;
-        if (fused) {
-            const at::Tensor &seg = segs[r % segs.size()];
-            seg_flag(seg);
-            TORCH_CHECK(seg.is_cuda() && seg.dim() == 4 && seg.size(0) == vertex.size(0) && seg.size(2) == vertex.size(1) &&
-                            seg.size(3) == vertex.size(2), "seg must be a float32 / float16 / bfloat16 [b,c,h,w] matching vertex");
-            mask = at::empty({seg.size(0), seg.size(2), seg.size(3)}, seg.options().dtype(at::kLong));
-        } else {
-            mask = masks[r % masks.size()];
-        }
-        pvv_problem p = make_problem(mask, vertex, round_hyp_num, inlier_thresh, min_num, max_num, PVV_SINGULAR_REFERENCE,
-                                     seed + r);
-        p.count_kernel = (int32_t)count_kernel;
-        if (fused) {
-            const at::Tensor &seg = segs[r % segs.size()];
-            p.seg_classes = (int32_t)seg.size(1);
-            for (int i = 0; i < 4; ++i) p.seg_stride[i] = seg.stride(i);
-            p.flags |= seg_flag(seg);
-        }
-        std::vector<void *> marks(PVV_N_MARKS);
-        for (int i = 0; i < PVV_N_MARKS; ++i) marks[(size_t)i] = (void *)ev[(size_t)PVV_N_MARKS * (size_t)r + (size_t)i];
-        // inner_marks = false: no records INSIDE the count pass (each costs ~2 us): its duration is then what rocprofv3 sees
-        if (!inner_marks) marks[PVV_MARK_STAGE0] = marks[PVV_MARK_PRUNE0] = nullptr;
-        p.ev_marks = marks.data();
-        p.flags |= PVV_FLAG_DEVICE_RNG;
-        at::Tensor ws = make_workspace(p, vertex);
-        auto out = at::empty({p.B, p.K, 2}, f32_like(vertex));
-        if (estimate) {      // estimate_voting_distribution_with_mean with round_hyp_num hypotheses in total (mean = zeros: timing only)
-            if (means.empty()) out.zero_();
-            else {
-                const at::Tensor &mn = means[r % means.size()];
-                check_dev(mn, "mean", at::kFloat);
-                TORCH_CHECK(mn.dim() == 3 && mn.size(0) == p.B && mn.size(1) == p.K && mn.size(2) == 2, "mean must be [b,vn,2]");
-                out.copy_(mn);
-            }
-            auto cov = at::empty({p.B, p.K, 2, 2}, f32_like(vertex));
-            ok(pvv_estimate_voting_distribution(&p, mask.data_ptr(), field_ptr(vertex), nullptr, nullptr, out.data_ptr<float>(),
-                                                ws.data_ptr(), (size_t)ws.numel(), cov.data_ptr<float>(), nullptr, nullptr, nullptr,
-                                                nullptr, cur_stream(vertex)),
-               "estimate_voting_distribution");
-            keep.push_back(cov);
-        } else if (fused) {
-            ok(pvv_decode_keypoint_v3(&p, field_ptr(segs[r % segs.size()]), field_ptr(vertex), nullptr, nullptr, ws.data_ptr(),
-                                      (size_t)ws.numel(), mask.data_ptr<int64_t>(), out.data_ptr<float>(), nullptr, nullptr,
-                                      cur_stream(vertex)),
-               "decode_keypoint_v3");
-            keep.push_back(mask);
-        } else {
-            ok(pvv_ransac_voting_v3(&p, mask.data_ptr(), field_ptr(vertex), nullptr, nullptr, ws.data_ptr(),
-                                    (size_t)ws.numel(), out.data_ptr<float>(), nullptr, nullptr, cur_stream(vertex)),
-               "ransac_voting_v3");
-        }
-        keep.push_back(ws);
-        keep.push_back(out);
-    }
-    TORCH_CHECK(hipStreamSynchronize((hipStream_t)cur_stream(vertices[0])) == hipSuccess, "hipStreamSynchronize failed");
+    Events ev;
+    timed_calls(ev, true, inner_marks, masks, vertices, segs, means,
+                {round_hyp_num, inlier_thresh, min_num, max_num, PVV_SINGULAR_REFERENCE, seed, 0, count_kernel}, reps, estimate);
     std::vector<std::vector<double>> ms((size_t)reps, std::vector<double>(PVV_N_MARKS - 1, 0.0));
     for (int64_t r = 0; r < reps; ++r) {
-        hipEvent_t *e = &ev[(size_t)PVV_N_MARKS * (size_t)r];
+        const hipEvent_t *e = &ev.ev[(size_t)PVV_N_MARKS * (size_t)r];
         auto dt = [&](int a, int b) {
             float t = 0.f;
             if (hipEventElapsedTime(&t, e[a], e[b]) == hipSuccess) return (double)t;
@@ -567,8 +544,17 @@ std::vector<std::vector<double>> stage_ms_in_pipeline(std::vector<at::Tensor> ma
         ms[(size_t)r][5] = dt(PVV_MARK_COMPACT, PVV_MARK_STAGE0);
         ms[(size_t)r][6] = dt(PVV_MARK_STAGE0, PVV_MARK_PRUNE0);
     }
-    for (auto &e : ev) (void)hipEventDestroy(e);
     return ms;
+}
+
+// pvv_stage_hint_query for this problem shape -> (data there, mean winner ratio of the last calls, AUTO's threshold)
+std::tuple<bool, double, double> stage_hint(at::Tensor mask, at::Tensor vertex, int64_t hn)
+{
+    const c10::DeviceGuard device_guard(vertex.device());
+    const Call c = begin_call(&mask, nullptr, vertex, {hn, 0.99, 5, 30000, 0, 0});
+    float mean = -1.f, thr = -1.f;
+    const int valid = pvv_stage_hint_query(&mean, &thr, &c.p, cur_stream(vertex));
+    return {valid != 0, (double)mean, (double)thr};
 }
 
 // SURVEY 8(d)'s streaming-read microbenchmark: one read-once pass over `buf` (pvv_stream_read_probe); the caller brackets
@@ -588,8 +574,7 @@ void rerun_count_kernel(at::Tensor mask, at::Tensor vertex, int64_t hn, double i
                         int64_t max_num, at::Tensor ws, bool zero_counts, int64_t count_kernel, std::optional<int64_t> cap, bool device_rng)
 {
     const c10::DeviceGuard device_guard(vertex.device());   // launch on the tensors' GPU, whatever the current device is
-    pvv_problem p = make_problem(mask, vertex, hn, inlier_thresh, min_num, max_num, 0, 0);
-    p.count_kernel = (int32_t)count_kernel;
+    pvv_problem p = make_problem(mask, vertex, {hn, inlier_thresh, min_num, max_num, 0, 0, 0, count_kernel});
     // the workspace offsets depend on the flags the call that made `ws` carried: ransac_voting_v3 promises the device RNG
     // (PVV_FLAG_DEVICE_RNG: no draw storage) exactly when neither idxs nor selection was injected -- say so here
     if (device_rng) p.flags |= PVV_FLAG_DEVICE_RNG;
@@ -636,21 +621,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("shutdown", []() { ok(pvv_shutdown(), "pvv_shutdown"); },
           "pvv_shutdown: release the library's per-device side streams, events and pinned stage-hint arrays; forget every hint");
     m.def("estimate_counts_in_stages", [](int64_t B, int64_t H, int64_t W, int64_t K, int64_t hn, int64_t max_num) {
-              pvv_problem p;
-              memset(&p, 0, sizeof(p));
-              p.B = (int32_t)B; p.H = (int32_t)H; p.W = (int32_t)W; p.K = (int32_t)K; p.hn = (int32_t)hn;
-              p.mask_elem_size = 8; p.min_num = 5; p.max_num = (int32_t)max_num;
-              p.cap = pvv_default_cap(p.H, p.W, p.max_num); p.inlier_thresh = 0.99f;
+              const pvv_problem p = contiguous_problem(B, H, W, K, hn, max_num, 8);
               return pvv_estimate_counts_in_stages(&p) == 1;
           }, "pvv_estimate_counts_in_stages: would AUTO count an estimate of this size in stages? (host-only)", py::arg("B"), py::arg("H"),
           py::arg("W"), py::arg("K"), py::arg("hn"), py::arg("max_num") = 30000);
     m.def("workspace_bytes", [](int64_t B, int64_t H, int64_t W, int64_t K, int64_t hn, int64_t max_num, int64_t mask_elem_size,
                                 int64_t count_kernel, bool device_rng) {
-              pvv_problem p;
-              memset(&p, 0, sizeof(p));
-              p.B = (int32_t)B; p.H = (int32_t)H; p.W = (int32_t)W; p.K = (int32_t)K; p.hn = (int32_t)hn;
-              p.mask_elem_size = (int32_t)mask_elem_size; p.min_num = 5; p.max_num = (int32_t)max_num;
-              p.cap = pvv_default_cap(p.H, p.W, p.max_num); p.inlier_thresh = 0.99f; p.count_kernel = (int32_t)count_kernel;
+              pvv_problem p = contiguous_problem(B, H, W, K, hn, max_num, mask_elem_size);
+              p.count_kernel = (int32_t)count_kernel;
               p.flags = device_rng ? PVV_FLAG_DEVICE_RNG : 0;
               return (int64_t)pvv_workspace_bytes(&p);
           }, "pvv_workspace_bytes for a contiguous problem (host-only: no GPU needed)", py::arg("B"), py::arg("H"), py::arg("W"),
@@ -677,12 +655,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("vertices"), py::arg("round_hyp_num"), py::arg("inlier_thresh"), py::arg("min_num"), py::arg("max_num"),
           py::arg("seed"), py::arg("reps"), py::arg("count_kernel") = 0, py::arg("inner_marks") = true, py::arg("estimate") = false,
           py::arg("segs") = std::vector<at::Tensor>(), py::arg("means") = std::vector<at::Tensor>());
-    m.def("stage_hint", [](at::Tensor mask, at::Tensor vertex, int64_t hn) {
-              pvv_problem p = make_problem(mask, vertex, hn, 0.99, 5, 30000, 0, 0);
-              float mean = -1.f, thr = -1.f;
-              const int valid = pvv_stage_hint_query(&mean, &thr, &p, cur_stream(vertex));
-              return std::make_tuple(valid != 0, (double)mean, (double)thr);
-          }, "pvv_stage_hint_query for this problem shape -> (data there, mean winner ratio of the last calls, AUTO's threshold)",
+    m.def("stage_hint", &stage_hint,
+          "pvv_stage_hint_query for this problem shape -> (data there, mean winner ratio of the last calls, AUTO's threshold)",
           py::arg("mask"), py::arg("vertex"), py::arg("hn"));
     m.def("stream_read_probe", &stream_read_probe, "one read-once streaming pass over a buffer (bench aid)");
     m.def("count_kernel_ms_in_pipeline", &count_kernel_ms_in_pipeline,

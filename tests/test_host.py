@@ -84,6 +84,33 @@ def test_workspace_size_regression_and_the_device_rng_flag():
     assert L.pvv_workspace_bytes(ctypes.byref(p)) == 0 and b"count_kernel" in L.pvv_last_error()
 
 
+def _contiguous_problem(B, H, W, K, hn, max_num=30000, mask_elem_size=8, count_kernel=0, flags=0):
+    """What the extension module's two host-only queries lay out: contiguous, min_num = 5, 0.99, the default cap."""
+    p = capi.Problem()
+    p.B, p.H, p.W, p.K, p.hn, p.mask_elem_size, p.min_num, p.max_num = B, H, W, K, hn, mask_elem_size, 5, max_num
+    p.cap = capi.load().pvv_default_cap(H, W, max_num)
+    p.inlier_thresh, p.count_kernel, p.flags = 0.99, count_kernel, flags
+    return p
+
+
+def test_extension_host_queries_equal_the_c_abi_on_the_same_problem(pkg):
+    """ext.workspace_bytes and ext.estimate_counts_in_stages build their pvv_problem themselves: the answers are those of
+    pvv_workspace_bytes / pvv_estimate_counts_in_stages on the equal capi.Problem (no GPU: no stage hint, the proxy decides)."""
+    from clean_pvnet_amd import ransac_voting as ext
+    L = capi.load()
+    for B, H, W, K, hn, max_num, elem in ((64, 480, 640, 9, 512, 30000, 8), (16, 540, 720, 17, 2048, 30000, 1), (3, 37, 53, 4, 130, 100, 4)):
+        for device_rng in (True, False):
+            for kernel in (ext.COUNT_FULL, ext.COUNT_AUTO):
+                p = _contiguous_problem(B, H, W, K, hn, max_num, elem, kernel, 1 if device_rng else 0)
+                want = L.pvv_workspace_bytes(ctypes.byref(p))
+                assert want > 0, L.pvv_last_error()
+                assert ext.workspace_bytes(B, H, W, K, hn, max_num, elem, kernel, device_rng) == want, (B, H, W, device_rng, kernel)
+    assert ext.workspace_bytes(64, 480, 640, 9, 512) == L.pvv_workspace_bytes(ctypes.byref(_contiguous_problem(64, 480, 640, 9, 512, flags=1)))
+    for B, want in ((24, True), (8, False), (3, False)):          # the sizes test_gpu_staged.py asks about, before any hint
+        got = L.pvv_estimate_counts_in_stages(ctypes.byref(_contiguous_problem(B, 480, 640, 9, 4096)))
+        assert ext.estimate_counts_in_stages(B, 480, 640, 9, 4096) == (got == 1) == want, B
+
+
 def test_shutdown_without_a_gpu_is_a_no_op():
     """pvv_shutdown() on a process that never launched anything has nothing to release and says so with 0 -- also twice."""
     L = capi.load()
