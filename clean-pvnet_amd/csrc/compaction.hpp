@@ -547,6 +547,12 @@ struct HypArgs {
     int *surv;               // [B, kSurvCap] scratch: the survivors of a heavily subsampled image (see k_compact_hyp)
     int *lead;               // [B,K,8] or null: leader counts of the staged count pass (count_prune.hpp); [4..7] zeroed here
     int *miss;               // [B,K,hn] or null: the staged pass's shared miss counters (count_filter_runs.hpp), zeroed here
+    // Deferred rows (a call whose first count pass is v3 in stages; 0 / null otherwise: every row is gathered here).  The first count
+    // launch reads only the rows of its own chunks -- residues mod kStageM in defer_mask -- of an image it stages; everything else reads
+    // dirs one launch later.  So for an image that will be staged and whose lists this call did not subsample, the compaction blocks
+    // gather only the rows of those chunks and the first count launch gathers the rest beside its counting (count_bf16.hpp: gather blocks).
+    uint32_t defer_mask;     // the first launch's residues (kStageFirst / kStageFirstEighth), or 0
+    int *deferred;           // [B]: 1 = the image's other rows are left to the first count launch; written with tn
 };
 
 constexpr int kHypRejectTries = 1 << 12;
@@ -583,7 +589,10 @@ __device__ __forceinline__ int select_pixel(const int *prefix, int T, const unsi
 //    the count kernel's loads are unit-stride).
 // Dynamic LDS: T ints (the tile prefix of the hypothesis blocks).  VT: the vertex field's element type (the only read of it;
 // coords and dirs are f32 whatever it is).
-template <int VT>
+// DEFER: the call defers rows (HypArgs.defer_mask != 0).  A call that does not runs the instantiation without that code: the kernel
+// sits at its SGPR limit, and the flag, the mask and the per-row test cost the whole kernel -- hypothesis blocks included -- a dozen
+// more SGPR spills (the fused un_pnp call, whose rows hold nine times the hypotheses: +1 % per call when it deferred).
+template <int VT, bool DEFER = false>
 __global__ __launch_bounds__(kBlock) void k_compact_hyp(MaskArgs a, VertexArgs v, HypArgs h,
                                                         const uint32_t *__restrict__ tiles,
                                                         const unsigned short *__restrict__ tile_list,
@@ -754,6 +763,7 @@ __global__ __launch_bounds__(kBlock) void k_compact_hyp(MaskArgs a, VertexArgs v
             tn_out[b] = 0;
             if (a.tn_user) a.tn_user[b] = 0;
             if (a.status) a.status[b] = PVV_STATUS_SKIPPED;
+            if constexpr (DEFER) h.deferred[b] = 0;
         }
         return;
     }
@@ -763,6 +773,7 @@ __global__ __launch_bounds__(kBlock) void k_compact_hyp(MaskArgs a, VertexArgs v
     // survivor count for its row offset -- and filters its own list.  Only for images with foreground_num > max_num,
     // and it saves a launch on every call; the last tile's block reports tn.
     const bool sub = a.fuse_sub && tot.fg > (long long)a.max_num;
+    bool deferred = false;                                               // (block-uniform, the same in every block of the image)
     if (sub) {
         const float prob = (float)a.max_num / (float)tot.fg;
         int cnt = 0;
@@ -828,9 +839,15 @@ __global__ __launch_bounds__(kBlock) void k_compact_hyp(MaskArgs a, VertexArgs v
             tn_out[b] = all < a.cap ? all : a.cap;
             if (a.tn_user) a.tn_user[b] = tn_out[b];
             if (a.status) a.status[b] = PVV_STATUS_SUBSAMPLED | (all > a.cap ? PVV_STATUS_TRUNCATED : 0);
+            if constexpr (DEFER) h.deferred[b] = 0;
         }
     } else {
+        // (foreground_num > max_num without the fused path: k_tile_subsample rewrote the lists -- subsampled, never deferred)
+        const int rows = tot.total < a.cap ? tot.total : a.cap;
+        if constexpr (DEFER)
+            deferred = tot.fg <= (long long)a.max_num && ((rows + kStageChunkRows - 1) >> kStageChunkShift) >= kStageMinChunks;
         if (t == 0 && threadIdx.x == 0) {
+            if constexpr (DEFER) h.deferred[b] = deferred ? 1 : 0;
             tn_out[b] = tot.total < a.cap ? tot.total : a.cap;
             if (a.tn_user) a.tn_user[b] = tn_out[b];
             // not fused: k_tile_subsample has already rewritten the lists of an image with foreground_num > max_num
@@ -855,6 +872,9 @@ __global__ __launch_bounds__(kBlock) void k_compact_hyp(MaskArgs a, VertexArgs v
         const int p = t * kTile + list[li];
         const int y = p / a.W, x = p - y * a.W;
         coords[(size_t)b * a.cap + before + li] = make_float2((float)x, (float)y);
+        // a deferred image: coords for every row, the gathers only for the rows the first count launch itself reads
+        if constexpr (DEFER)
+            if (deferred && !((h.defer_mask >> (((before + li) >> kStageChunkShift) % kStageM)) & 1u)) continue;
         float2 *drow = dirs + (size_t)b * v.K * a.cap + before + li;
         for (int v0 = 0; v0 < v.K; v0 += kKeys) {
             typename VertexRaw<VT>::type d[kKeys];

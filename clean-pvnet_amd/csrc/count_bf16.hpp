@@ -57,11 +57,8 @@ enum { kCountFull = 0, kCountFirst = 1, kCountFilter = 2 };
 // parameters they were a dozen integer divisions per work item): the first launch counts the 512-pixel chunks c with
 // (c mod 8) in {1, 5} -- a quarter of the chunks, spread over the object (rows of the compacted list = raster order) --,
 // the second launch the other residues; images of fewer than kStageMinChunks chunks are counted completely by the first.
-#ifndef PVV_STAGE_M                    // (tools/build_variant.sh -DPVV_STAGE_M=.. -DPVV_STAGE_FIRST=..: schedule sweeps)
-#define PVV_STAGE_M 8
-#define PVV_STAGE_FIRST 0x22u
-#endif
-constexpr int kStageM = PVV_STAGE_M;
+// (kStageM, kStageMinChunks and the chunk length are stated in vote_common.hpp: the compaction needs them too.)
+static_assert(4 * kBfPixPerWave == kStageChunkRows, "a chunk is what one block of the count kernels walks per item");
 constexpr uint32_t kStageFirst = PVV_STAGE_FIRST;
 // Round 4: with the second launch eliminating as it goes (count_filter_runs.hpp) a SMALLER first stage pays once its runs are
 // long: an eighth of the chunks ({1} of 8) instead of a quarter is -4 % per call at config 3 / B = 128 and -9 % on config 5 /
@@ -69,7 +66,6 @@ constexpr uint32_t kStageFirst = PVV_STAGE_FIRST;
 // of the pass; the host picks it from the problem's size (launch_count_bf16).
 constexpr uint32_t kStageFirstEighth = 0x02u;
 constexpr uint32_t stage_rest_of(uint32_t first) { return ((1u << kStageM) - 1u) & ~first; }
-constexpr int kStageMinChunks = 8;
 
 struct StageArgs {
     const int *lead;      // kCountFilter: [B,K,8] leaders' partial counts [0..3] (-1: none) and their SURE inliers among the
@@ -112,13 +108,99 @@ __device__ __forceinline__ int stage_pixels(int tn, int nch, int PC)
     return stage_chunks<MASK>(nch) * PC - (((MASK >> ((nch - 1) % kStageM)) & 1u) ? nch * PC - tn : 0);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Gather blocks of the first count launch.  Its count blocks read only the rows of their own chunks, and from about half of its span
+// on a growing part of the chip's block slots is empty (1728 items on 1280 slots at config 3 / B = 64); k_lead, the second launch and
+// the refit read the other rows one launch later.  So for the images k_compact_hyp marked (HypArgs.deferred: staged, not subsampled)
+// the rows of the REST chunks are gathered here instead of in front of the count pass: the host adds G blocks to the grid, which leave
+// through gather_deferred_rows before the item loop.  A unit is one rest chunk of one image, all K keypoints, two rows per thread;
+// gather block i walks units i, i + G, ...  Nothing in the launch waits for another of its blocks: count blocks never read a rest
+// chunk of a deferred image, gather blocks never write anything else.
+// Where in the grid: right behind the first resident generation of count blocks (k_count_bf16: g_first), not at the top.  At the top
+// they queue behind the ~2500 count blocks of the 15-per-CU grid that only pass through, start in the launch's last quarter and
+// lengthen it by 9-13 us where k_compact_hyp saves 6.4; at the bottom they hold back 256 count blocks per G / CU (+6.4 us at one
+// per CU); behind the first generation they take the first slots it frees: +3.3 ... 4.4 us (profiles/deferred_rows_kernel_stats.json).
+// ---------------------------------------------------------------------------------------------
+struct GatherArgs {
+    int G;                // gather blocks in the grid; 0: none (every row was gathered by k_compact_hyp)
+    int vt;               // element type of the vertex field (kElem*): a run-time switch, the branch is cold
+    const int *deferred;  // [B] k_compact_hyp's flags
+    float2 *dirs;         // the planar rows (the kernel's own `dirs` is its read-only view of the first-stage rows)
+    VertexArgs v;
+};
+
+// rows [pb, pb + 512) of image b below tn: coords -> pixel (exact integers) -> the K vertex pairs -> dirs
+template <int VT>
+__device__ __forceinline__ void gather_unit(const GatherArgs &ga, const float2 *__restrict__ crd, int b, int pb, int tn, int cap)
+{
+    // An f32 gather in flight holds four registers (a 64-bit address: the strides are the caller's; the pair): the two rows of a thread
+    // go one after the other, kKeys gathers each, so that the branch stays far below the count kernel's 96 (no scratch).
+    constexpr int kKeys = 10;                                            // gathers in flight (K = 9: one trip per row)
+    const int r0 = pb + (int)threadIdx.x, r1 = r0 + kBlock;
+    const float2 c0 = r0 < tn ? crd[r0] : make_float2(0.f, 0.f), c1 = r1 < tn ? crd[r1] : make_float2(0.f, 0.f);
+#pragma unroll 1
+    for (int q = 0; q < 2; ++q) {
+        const int row = q ? r1 : r0;
+        if (row >= tn) break;
+        const int x = (int)(q ? c1.x : c0.x), y = (int)(q ? c1.y : c0.y);
+        float2 *drow = ga.dirs + (size_t)b * ga.v.K * cap + row;
+        for (int v0 = 0; v0 < ga.v.K; v0 += kKeys) {
+            typename VertexRaw<VT>::type d[kKeys];
+#pragma unroll
+            for (int u = 0; u < kKeys; ++u)
+                if (v0 + u < ga.v.K) d[u] = load_vertex<VT>(ga.v, b, y, x, v0 + u);
+#pragma unroll
+            for (int u = 0; u < kKeys; ++u)
+                if (v0 + u < ga.v.K) drow[(size_t)(v0 + u) * cap] = widen_vertex<VT>(ga.v, d[u]);
+        }
+    }
+}
+
+// A gather block's whole life (gi: its index among the G).  chunk_end: the count kernel's table, here the inclusive prefix of the
+// deferred images' rest chunks.
+template <uint32_t REST>
+__device__ __forceinline__ void gather_deferred_rows(const GatherArgs &ga, int gi, int *chunk_end, const float2 *__restrict__ coords,
+                                                     const int *__restrict__ tn_arr, int B, int cap)
+{
+    const int lane = lane_id();
+    if (wave_id() == 0) {
+        int carry = 0;
+        for (int b0 = 0; b0 < B; b0 += 64) {
+            const int b = b0 + lane;
+            int inc = 0;
+            if (b < B && ga.deferred[b] != 0) inc = stage_chunks<REST>((tn_arr[b] + kStageChunkRows - 1) >> kStageChunkShift);
+            inc = wave_incl_scan(inc) + carry;
+            if (b < B) chunk_end[b] = inc;
+            carry = __builtin_amdgcn_readlane(inc, 63);
+        }
+    }
+    __syncthreads();
+    const int units = chunk_end[B - 1];
+    for (int u = gi; u < units; u += ga.G) {
+        int local;
+        const int b = locate_item(chunk_end, B, u, &local);
+        const int pb = stage_chunk_at<REST>(local) << kStageChunkShift;
+        const int tn = tn_arr[b];
+        const float2 *crd = coords + (size_t)b * cap;
+        if (ga.vt == kElemF16) gather_unit<kElemF16>(ga, crd, b, pb, tn, cap);
+        else if (ga.vt == kElemBF16) gather_unit<kElemBF16>(ga, crd, b, pb, tn, cap);
+        else gather_unit<kElemF32>(ga, crd, b, pb, tn, cap);
+    }
+}
+
 // 5 blocks (= 5 waves per SIMD) per CU: <= 96 VGPRs and 30 KB of LDS per block; measured -4.4 % against 4
-template <int MODE, uint32_t FIRST = kStageFirst>
+// GATHER (first launch only): the launch carries gather blocks.  A launch without deferred rows runs the instantiation without
+// the branch, whose code is the one the kernel had before there were gather blocks (the branch costs the item prologue a dozen
+// SGPR spill moves: the register allocation is one for the whole kernel).
+// `dirs` is __restrict__ and read-only here while gather blocks write the same array through GatherArgs.dirs: that holds because no
+// thread does both -- a gather block leaves before anything reads `dirs`, and must never read it -- and because count blocks read
+// only first-stage chunks of a deferred image, gather blocks write only its rest chunks.
+template <int MODE, uint32_t FIRST = kStageFirst, bool GATHER = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5, 5))) void k_count_bf16(
     const float2 *__restrict__ coords /*[B,cap]*/, const float2 *__restrict__ dirs /*[B,K,cap]*/,
     const float2 *__restrict__ hyps /*[B,K,hn]*/, int *__restrict__ counts /*[B,K,hn]*/,
     const int *__restrict__ tn_arr, int B, int K, int hn, int cap, float thresh, Bf16Consts fc, int target_items,
-    long long *__restrict__ dbg /*tuning builds: phase timestamps; nullptr otherwise*/, StageArgs sa)
+    long long *__restrict__ dbg /*tuning builds: phase timestamps; nullptr otherwise*/, StageArgs sa, GatherArgs ga /*GATHER only*/)
 {
     PVV_STAMP(0);
     PVV_CENSUS_IN();
@@ -139,6 +221,20 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5, 5))) 
     const int nt = (hn + 31) >> 5;                  // 32-hypothesis tiles per keypoint
     const int hs = sa.hstride > 0 ? sa.hstride : hn; // row length of hyps / counts
     if constexpr (FILTER) if (*sa.any_staged == 0) return;
+    // The count grid: the launch's blocks less the gather blocks, which leave here; bid: a count block's index in it.  The gather
+    // blocks follow the first target_items count blocks -- one resident generation (5 per CU) -- in dispatch order, so they take the
+    // first slots that generation frees, ahead of the count grid's other blocks, most of which only pass through (nblk below).
+    static_assert(!GATHER || MODE == kCountFirst, "only the first launch of a staged pass gathers");
+    const int n_gather = GATHER ? ga.G : 0;
+    const int ngrid = (int)gridDim.x - n_gather;
+    const int g_first = min(target_items, ngrid);
+    const int bid = (int)blockIdx.x - ((int)blockIdx.x >= g_first ? n_gather : 0);
+    if constexpr (GATHER) {
+        if ((int)blockIdx.x >= g_first && bid < g_first) {
+            gather_deferred_rows<REST>(ga, (int)blockIdx.x - g_first, chunk_end, coords, tn_arr, B, cap);
+            return;
+        }
+    }
 
     // Work item = (image, keypoint, 512-pixel chunk, a run of hypothesis groups).  A group is up to 16 tiles (512
     // hypotheses, what fits the LDS staging); an item walks as many groups as possible (the pixel operands are
@@ -184,7 +280,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5, 5))) 
         if (gpi == 1 && !FILTER)                                    // (the filter compacts groups of 512 hypotheses: no smaller ones)
             while (htpi > htpi_min && chunks * ((nt + htpi - 1) / htpi) < target_items) htpi = (htpi + 1) >> 1;
         if (lane == 0) { s_htpi = htpi; s_gpi = gpi; s_chunks = carry; }
-        if constexpr (MODE == kCountFirst) if (blockIdx.x == 0 && lane == 0) *sa.any_staged = any_staged ? 1 : 0;
+        if constexpr (MODE == kCountFirst) if (bid == 0 && lane == 0) *sa.any_staged = any_staged ? 1 : 0;
     }
     __syncthreads();
     PVV_STAMP(1);
@@ -203,13 +299,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5, 5))) 
     // (they pass through the slots the working blocks free: no measurable tail).  With many items every block works
     // (config 5 at B = 16: 1.43 vs 1.70 ms), and so does the 48-per-CU grid of the long-hypothesis configurations
     // (11 000 leaving blocks would be a tail: +10 % on config 4 at B = 16).
-    const int nblk = (total <= target_items + (target_items >> 1) + (target_items >> 2) && (int)gridDim.x > target_items &&
-                      (int)gridDim.x <= 3 * target_items) ? target_items : (int)gridDim.x;
-    if ((int)blockIdx.x >= nblk) return;
+    const int nblk = (total <= target_items + (target_items >> 1) + (target_items >> 2) && ngrid > target_items &&
+                      ngrid <= 3 * target_items) ? target_items : ngrid;
+    if (bid >= nblk) return;
     // item -> (chunk over the whole batch, rest) without a division per item: both advance by a constant step
     const int step_q = nblk / per_chunk, step_r = nblk - step_q * per_chunk;
-    int gchunk = (int)blockIdx.x / per_chunk, rem = (int)blockIdx.x - gchunk * per_chunk;
-    for (int item = blockIdx.x; item < total;
+    int gchunk = bid / per_chunk, rem = bid - gchunk * per_chunk;
+    for (int item = bid; item < total;
          item += nblk, gchunk += step_q + (rem + step_r >= per_chunk ? 1 : 0), rem += step_r - (rem + step_r >= per_chunk ? per_chunk : 0)) {
         int local;
         const int b = locate_item(chunk_end, B, gchunk, &local);   // image, and the chunk's index within it (this stage's)

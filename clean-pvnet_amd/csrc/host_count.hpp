@@ -49,6 +49,9 @@ struct CountCols {
     int hstride = 0;     // row length (0: p->hn, whole rows)
     int lead_set = 0;    // which of the workspace's two sets of leader words the pass uses
     const float *mean = nullptr;   // the estimate in stages: [B,K,2] keypoints (device) its second launch orders the chunks by, or nullptr
+    // a staged pass whose schedule was chosen ahead of the front kernels (run_front: k_compact_hyp deferred rows against it)
+    uint32_t first = 0;                 // the first launch's residues; 0: launch_count_bf16 chooses (stage_schedule)
+    const GatherArgs *gather = nullptr; // != nullptr: rows were deferred, the first launch gathers them (G is set by launch_staged)
 };
 
 struct StagedLaunch {
@@ -62,6 +65,13 @@ struct StagedLaunch {
     CountPass pass;      // StagedEstimate: the estimate's bound (StageArgs.sub_tenth)
     CountCols cols;
 };
+
+// Gather blocks added to the first count launch when rows were deferred, per CU.  The host does not know tn, so the number is
+// fixed.  A unit (512 rows x K gathers) is three dependent round trips and config 3 at B = 64 has 576 of them; one-process A/B of
+// whole calls there, 1 / 2 / 4 per CU: 0.1884 / 0.1883 / 0.1884 ms against the parent's 0.1916; at B = 32 0.1213 / 0.1211 / 0.1210
+// against 0.1212 (profiles/deferred_rows_ab.json).  One: a batch whose images all turn out subsampled or small pays a table build
+// per gather block for nothing.
+constexpr int kGatherBlocksPerCu = 1;
 
 // the three launches of a staged count pass for one chunk schedule (FIRST = the residues mod 8 the first launch counts)
 template <uint32_t FIRST>
@@ -87,8 +97,17 @@ int launch_staged(const StagedLaunch &a)
 #ifdef PVV_STAMPS
     sa.dbg = tuning_ptr("PVV_DBG_PTR_FILTER");                    // phase census of the second launch (tools/census_filter.py)
 #endif
-    hipLaunchKernelGGL((k_count_bf16<kCountFirst, FIRST>), dim3(a.per_cu_first * num_cus()), dim3(kBlock), 0, st, coords, dirs, hyps, counts, tn,
-                       p->B, p->K, p->hn, p->cap, p->inlier_thresh, fc, a.target_first, a.dbg, sa);
+    GatherArgs ga{};
+    if (a.cols.gather) {
+        ga = *a.cols.gather;
+        ga.G = tuning_int("PVV_GATHER_PER_CU", kGatherBlocksPerCu) * num_cus();
+    }
+    if (ga.G > 0)
+        hipLaunchKernelGGL((k_count_bf16<kCountFirst, FIRST, true>), dim3(a.per_cu_first * num_cus() + ga.G), dim3(kBlock), 0, st, coords, dirs, hyps, counts, tn,
+                           p->B, p->K, p->hn, p->cap, p->inlier_thresh, fc, a.target_first, a.dbg, sa, ga);
+    else
+        hipLaunchKernelGGL((k_count_bf16<kCountFirst, FIRST>), dim3(a.per_cu_first * num_cus()), dim3(kBlock), 0, st, coords, dirs, hyps, counts, tn,
+                           p->B, p->K, p->hn, p->cap, p->inlier_thresh, fc, a.target_first, a.dbg, sa, ga);
     if (int e = check_launch("k_count_bf16<first>")) return e;
     if (int e = mark(p, PVV_MARK_STAGE0, st)) return e;
     LeadArgs la;
@@ -121,8 +140,34 @@ int launch_staged(const StagedLaunch &a)
         return check_launch("k_count_filter_runs");
     }
     hipLaunchKernelGGL((k_count_bf16<kCountFilter, FIRST>), dim3(a.per_cu_filter * num_cus()), dim3(kBlock), 0, st, coords, dirs, hyps, counts, tn,
-                       p->B, p->K, p->hn, p->cap, p->inlier_thresh, fc, a.target_filter, a.dbg, sa);
+                       p->B, p->K, p->hn, p->cap, p->inlier_thresh, fc, a.target_filter, a.dbg, sa, GatherArgs{});
     return check_launch("k_count_bf16<filter>");
+}
+
+// Is the count grid of the short kind (5 or 15 blocks per CU, whose blocks beyond one resident generation mostly pass through),
+// not the 48-per-CU grid of long, uneven items in which every block works?  Rows are deferred only for the short kind: the gather
+// blocks live on the slots the first generation frees early, and a grid in which every block works has none to spare (config 5 at
+// B = 16, where moreover every image is subsampled and nothing would be deferred: +0.3 % per call when it carried them).
+bool count_grid_short(const pvv_problem *p) { return p->hn < 2048 || p->B <= 8; }
+
+// The chunk schedule of a staged pass: the residues mod kStageM its first launch counts.
+// The first stage is a QUARTER of the chunks, or an EIGHTH when the problem is so large that the second launch's runs are long
+// (measured, one-process A/B of whole calls: -5 % at config 3 / B = 96, -4 % at B = 128, -9 % on config 5 / B = 16, -5 % at its
+// B = 8; +2.5 % at config 3 / B = 64, +4.8 % on config 5 / B = 4 with unequal keypoints).  "Long" is a property of the RUNS, not of
+// the hypothesis count: x = K * sum(tn) / 512 chunks per block slot of the second launch -- 5.4 at config 3 / B = 64, 8.1 at 96,
+// 6.2 / 3.1 on config 5 at B = 8 / 4 -- and the eighth pays from x = 5.8 on.  (Until round 5 the bound was on the work
+// K * hn * sum(tn), which told the same for 512 hypotheses and sent config 5's 2048 to the eighth from B = 2 on: the one case
+// of tools/auto_regret.py above 1.03.)
+// (the ESTIMATE keeps the quarter at every size: its second launch walks the chunks nearest to the keypoint first, and an
+// eighth is 1.5 % slower at B = 64, 2-3 % at B = 6-8, +-1 % on config 5 -- profiles/r05_experiments.txt (15))
+// It reads the stage hint, which the device may rewrite at any time: a call asks ONCE -- run_front ahead of k_compact_hyp when rows
+// are deferred against the schedule (CountCols.first), launch_count_bf16 otherwise.
+uint32_t stage_schedule(const pvv_problem *p, hipStream_t st, CountPass pass)
+{
+    const double sum_tn = (p->count_kernel == PVV_COUNT_AUTO ? stage_work(p, st) : stage_proxy_work(p)) * kStageProxyFg / ((double)p->K * p->hn);
+    const double chunks_per_slot = (double)p->K * sum_tn / (4.0 * kBfPixPerWave) / (5.0 * num_cus());
+    const bool eighth = tuning_int("PVV_STAGE_EIGHTH", (pass != CountPass::StagedEstimate && chunks_per_slot >= 5.8) ? 1 : 0) != 0;
+    return eighth ? kStageFirstEighth : kStageFirst;
 }
 
 int launch_count_bf16(const pvv_problem *p, const Layout &L, char *ws, hipStream_t st, CountPass pass, const CountCols &cc)
@@ -154,7 +199,7 @@ int launch_count_bf16(const pvv_problem *p, const Layout &L, char *ws, hipStream
             few = sum_tn / (4 * kBfPixPerWave) * p->K * ((p->hn + 511) / 512) <= 2000.0;
     }
     // (not few at B <= 8 -- only the hint can say so --: 15 per CU whatever hn; config 5 at B = 2, staged: 48 per CU +2 %)
-    const int per_cu = per_cu_t > 0 ? per_cu_t : (few ? 5 : ((p->hn < 2048 || p->B <= 8) ? 15 : 48));
+    const int per_cu = per_cu_t > 0 ? per_cu_t : (few ? 5 : (count_grid_short(p) ? 15 : 48));
     const float2 *coords = (const float2 *)(ws + L.coords), *dirs = (const float2 *)(ws + L.dirs);
     const float2 *hyps = (const float2 *)(ws + L.hyps) + cc.col0;
     int *counts = (int *)(ws + L.counts) + cc.col0;
@@ -172,29 +217,19 @@ int launch_count_bf16(const pvv_problem *p, const Layout &L, char *ws, hipStream
         StageArgs full{};
         full.hstride = cc.hstride;
         hipLaunchKernelGGL(k_count_bf16<kCountFull>, dim3(per_cu * num_cus()), dim3(kBlock), 0, st, coords, dirs, hyps, counts, tn,
-                           p->B, p->K, p->hn, p->cap, p->inlier_thresh, fc, target, dbg, full);
+                           p->B, p->K, p->hn, p->cap, p->inlier_thresh, fc, target, dbg, full, GatherArgs{});
         return check_launch("k_count_bf16");
     }
     // ransac_voting_layer_v3, staged: count a spread part of the chunks for every hypothesis, bound the winner's count from
-    // below through two leaders (k_lead), then the rest only for the hypotheses that can still reach that bound.  The first
-    // stage is a QUARTER of the chunks, or an EIGHTH when the problem is so large that the second launch's runs are long
-    // (measured, one-process A/B of whole calls: -5 % at config 3 / B = 96, -4 % at B = 128, -9 % on config 5 / B = 16, -5 % at its
-    // B = 8; +2.5 % at config 3 / B = 64, +4.8 % on config 5 / B = 4 with unequal keypoints).  "Long" is a property of the RUNS, not of
-    // the hypothesis count: x = K * sum(tn) / 512 chunks per block slot of the second launch -- 5.4 at config 3 / B = 64, 8.1 at 96,
-    // 6.2 / 3.1 on config 5 at B = 8 / 4 -- and the eighth pays from x = 5.8 on.  (Until round 5 the bound was on the work
-    // K * hn * sum(tn), which told the same for 512 hypotheses and sent config 5's 2048 to the eighth from B = 2 on: the one case
-    // of tools/auto_regret.py above 1.03.)
+    // below through two leaders (k_lead), then the rest only for the hypotheses that can still reach that bound.  Which chunks
+    // the first launch counts: stage_schedule.
     StagedLaunch sl;
     sl.p = p; sl.ws = ws; sl.L = &L; sl.st = st; sl.fc = fc; sl.dbg = dbg;
     sl.per_cu_first = per_cu_first; sl.per_cu_filter = per_cu_filter; sl.target_first = target_first; sl.target_filter = target_filter;
     sl.pass = pass;
     sl.cols = cc;
-    // (the ESTIMATE keeps the quarter at every size: its second launch walks the chunks nearest to the keypoint first, and an
-    // eighth is 1.5 % slower at B = 64, 2-3 % at B = 6-8, +-1 % on config 5 -- profiles/r05_experiments.txt (15))
-    const double sum_tn = (p->count_kernel == PVV_COUNT_AUTO ? stage_work(p, st) : stage_proxy_work(p)) * kStageProxyFg / ((double)p->K * p->hn);
-    const double chunks_per_slot = (double)p->K * sum_tn / (4.0 * kBfPixPerWave) / (5.0 * num_cus());
-    const bool eighth = tuning_int("PVV_STAGE_EIGHTH", (pass != CountPass::StagedEstimate && chunks_per_slot >= 5.8) ? 1 : 0) != 0;
-    return eighth ? launch_staged<kStageFirstEighth>(sl) : launch_staged<kStageFirst>(sl);
+    const uint32_t first = cc.first ? cc.first : stage_schedule(p, st, pass);
+    return first == kStageFirstEighth ? launch_staged<kStageFirstEighth>(sl) : launch_staged<kStageFirst>(sl);
 }
 
 CountArgs planar_count_args(const pvv_problem *p, const Layout &L, char *ws)

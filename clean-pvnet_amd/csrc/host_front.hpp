@@ -143,6 +143,7 @@ Front make_front(const pvv_problem *p, const Layout &L, char *ws, const FrontArg
     h.surv = (int *)(ws + L.surv);
     h.lead = L.lead ? (int *)(ws + L.lead) : nullptr;
     h.miss = L.miss ? (int *)(ws + L.miss) : nullptr;
+    h.defer_mask = 0u; h.deferred = nullptr;                       // (run_front: a call whose first count pass is v3 in stages)
     return f;
 }
 
@@ -277,6 +278,22 @@ int run_front(const pvv_problem *p, const Layout &L, char *ws, hipStream_t st, c
     const CountPlan *plan = a.plan;
     const CountPass pass = plan ? plan->staged : decide_staged(p, L, st, a.need);
     if (!plan && pass == CountPass::Full) { f.h.miss = nullptr; f.h.lead = nullptr; }
+    // ... and so is the chunk schedule of a v3 pass in stages, because k_compact_hyp then leaves the rows the first count launch
+    // does not read to that launch's gather blocks (HypArgs.defer_mask; count_bf16.hpp).  Every other pass -- full, exact, the
+    // estimate in stages, a v3 pass on the 48-per-CU grid (count_grid_short), the fused un_pnp call -- has all its rows gathered up front, as has
+    // pvv_rerun_count_kernel, whose rows are there already.
+    CountCols cols = plan ? plan->cols : CountCols();
+    if (!plan) cols.mean = a.mean;
+    GatherArgs ga{};
+    // (not the fused un_pnp call -- a plan --: its compaction launch is mostly hypothesis blocks, nine times v3's, and a second count
+    // pass follows; deferring there measured +1 % per call, profiles/deferred_rows_ab.json)
+    if (!plan && pass == CountPass::StagedV3 && L.deferred != 0 && count_grid_short(p) && tuning_int("PVV_DEFER_ROWS", 1) != 0) {
+        cols.first = stage_schedule(p, st, pass);
+        f.h.defer_mask = cols.first;
+        f.h.deferred = (int *)(ws + L.deferred);
+        ga.vt = f.vt; ga.deferred = f.h.deferred; ga.dirs = (float2 *)(ws + L.dirs); ga.v = f.v;
+        cols.gather = &ga;
+    }
     if (int e = mark(p, PVV_MARK_BEGIN, st)) return e;
     SideJoin sj;
     // no side stream to be had (the caller's stream is being captured, ...): the scan writes the mask itself
@@ -291,7 +308,8 @@ int run_front(const pvv_problem *p, const Layout &L, char *ws, hipStream_t st, c
     if (int e = mark(p, PVV_MARK_SCAN, st)) return e;
     auto compact = [&](auto et) {
         constexpr int VT = decltype(et)::value;
-        hipLaunchKernelGGL(k_compact_hyp<VT>, dim3(L.T + f.h.blocks, p->B), dim3(kBlock), sizeof(int) * (size_t)L.T, st, f.m, f.v,
+        auto kernel = f.h.defer_mask != 0u ? k_compact_hyp<VT, true> : k_compact_hyp<VT, false>;
+        hipLaunchKernelGGL(kernel, dim3(L.T + f.h.blocks, p->B), dim3(kBlock), sizeof(int) * (size_t)L.T, st, f.m, f.v,
                            f.h, (const uint32_t *)(ws + L.tiles), (const unsigned short *)(ws + L.tile_list),
                            (const float *)(ws + L.tile_draw), (int *)(ws + L.tn), (float2 *)(ws + L.coords),
                            (float2 *)(ws + L.dirs));
@@ -323,9 +341,7 @@ int run_front(const pvv_problem *p, const Layout &L, char *ws, hipStream_t st, c
         }
         if (le) return le;
     }
-    CountCols whole;
-    whole.mean = a.mean;
-    if (int e = launch_count_any(plan ? plan->p : p, L, ws, st, pass, plan ? plan->cols : whole)) return e;
+    if (int e = launch_count_any(plan ? plan->p : p, L, ws, st, pass, cols)) return e;
     if (int e = sj.finish()) return e;
     return mark(p, PVV_MARK_COUNT, st);
 }

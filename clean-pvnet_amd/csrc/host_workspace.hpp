@@ -40,6 +40,7 @@ struct Layout {
     size_t lead;                                     // staged counting (count_prune.hpp): [B,K,8] leader counts; 0 = not reserved
     size_t ratio;                                    // [B,K] winner count / tn (k_select_refit -> k_finalize_v3 -> stage hint)
     size_t miss;                                     // staged counting: [B,K,hn] shared miss counters (count_filter_runs.hpp); 0 = not reserved
+    size_t deferred;                                 // staged counting: [B] images whose rest-chunk rows the first count launch gathers; 0 = not reserved
 };
 
 bool use_bf16_count(const pvv_problem *p);
@@ -90,6 +91,7 @@ Layout make_layout(const pvv_problem *p)
     // (+ the any_staged word; TWO sets: the fused un_pnp call counts its v3 hypotheses and its estimate's as two staged passes)
     L.lead = may_stage(p) ? take(sizeof(int) * 2 * lead_set_words(p)) : 0;
     L.miss = may_stage(p) ? take(sizeof(int) * (size_t)p->B * p->K * p->hn) : 0;
+    L.deferred = may_stage(p) ? take(sizeof(int) * (size_t)p->B) : 0;
     L.total = off;
     return L;
 }

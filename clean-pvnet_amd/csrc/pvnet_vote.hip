@@ -128,6 +128,16 @@ PVV_EXPORT size_t pvv_workspace_bytes(const pvv_problem *p)
     return make_layout(p).total;
 }
 
+PVV_EXPORT int pvv_workspace_layout(const pvv_problem *p, pvv_workspace_offsets *out)
+{
+    if (int e = validate(p)) return e;
+    if (!out) return fail(PVV_E_ARG, "out is NULL");
+    const Layout L = make_layout(p);
+    out->tn = L.tn; out->coords = L.coords; out->dirs = L.dirs; out->hyps = L.hyps; out->counts = L.counts;
+    out->deferred = L.deferred; out->total = L.total;
+    return PVV_OK;
+}
+
 // ransac_voting_layer_v3 behind its two exports, which have checked their arguments and say in `a` where the mask comes from
 static int run_v3(const pvv_problem *p, const Layout &L, FrontArgs &a, const float *d_vertex, const int32_t *d_idxs,
                   const float *d_selection, void *d_workspace, float *d_out, int32_t *d_win_counts, int32_t *d_tn, void *stream)

@@ -586,8 +586,8 @@ void rerun_count_kernel(at::Tensor mask, at::Tensor vertex, int64_t hn, double i
     check_dev(ws, "workspace", at::kByte);
     // ransac_voting_v3 sizes its workspace to exactly pvv_workspace_bytes of ITS problem: a different total here means different
     // flags / cap / hn, i.e. every offset behind the tile lists would be shifted and the kernel would count on garbage.
-    // (The staged pass's leader words and miss counters come LAST in the layout, so a workspace made under AUTO / STAGED serves a
-    // re-run of the full pass: the two totals that differ only in that tail are both accepted.)
+    // (The staged pass's leader words, miss counters and deferred-row flags come LAST in the layout, so a workspace made under
+    // AUTO / STAGED serves a re-run of the full pass: the two totals that differ only in that tail are both accepted.)
     pvv_problem p_auto = p;
     p_auto.count_kernel = PVV_COUNT_AUTO;
     TORCH_CHECK((size_t)ws.numel() == pvv_workspace_bytes(&p) || (size_t)ws.numel() == pvv_workspace_bytes(&p_auto),
@@ -634,6 +634,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           }, "pvv_workspace_bytes for a contiguous problem (host-only: no GPU needed)", py::arg("B"), py::arg("H"), py::arg("W"),
           py::arg("K"), py::arg("hn"), py::arg("max_num") = 30000, py::arg("mask_elem_size") = 8, py::arg("count_kernel") = 0,
           py::arg("device_rng") = true);
+    m.def("workspace_layout", [](int64_t B, int64_t H, int64_t W, int64_t K, int64_t hn, int64_t max_num, int64_t mask_elem_size,
+                                 int64_t count_kernel, bool device_rng, std::optional<int64_t> cap) {
+              pvv_problem p = contiguous_problem(B, H, W, K, hn, max_num, mask_elem_size);
+              p.count_kernel = (int32_t)count_kernel;
+              p.flags = device_rng ? PVV_FLAG_DEVICE_RNG : 0;
+              if (cap.has_value()) p.cap = (int32_t)*cap;
+              pvv_workspace_offsets o;
+              ok(pvv_workspace_layout(&p, &o), "pvv_workspace_layout");
+              py::dict d;
+              d["tn"] = o.tn; d["coords"] = o.coords; d["dirs"] = o.dirs; d["hyps"] = o.hyps; d["counts"] = o.counts;
+              d["deferred"] = o.deferred; d["total"] = o.total; d["cap"] = (int64_t)p.cap;
+              return d;
+          }, "pvv_workspace_layout: byte offsets of tn, coords, dirs, hyps, counts and the deferred-row flags in the workspace of a "
+             "contiguous problem, with the rows reserved per image (host-only, read-only)", py::arg("B"), py::arg("H"), py::arg("W"),
+          py::arg("K"), py::arg("hn"), py::arg("max_num") = 30000, py::arg("mask_elem_size") = 8, py::arg("count_kernel") = 0,
+          py::arg("device_rng") = true, py::arg("cap") = py::none());
     m.def("decode_keypoint_v3", &decode_keypoint_v3, "argmax(seg) fused with batched ransac_voting_layer_v3",
           py::arg("seg"), py::arg("vertex"), py::arg("round_hyp_num"), py::arg("inlier_thresh"), py::arg("min_num"),
           py::arg("max_num"), py::arg("idxs"), py::arg("selection"), py::arg("seed"), py::arg("singular_policy"),

@@ -193,3 +193,16 @@ __device__ __forceinline__ uint32_t rng_u32(uint64_t seed, uint32_t stream, uint
     uint64_t k = mix64(seed + 0x9E3779B97F4A7C15ull * (uint64_t)(stream + 1));
     return (uint32_t)(mix64(k ^ (((uint64_t)a << 32) | b)) >> 32);
 }
+
+// The staged count pass's chunk grid (count_bf16.hpp: the schedule itself), stated here because the compaction -- which comes first,
+// in the file and in the call -- leaves the rows of some chunks to the first count launch (compaction.hpp: deferred rows): rows of the
+// compacted list are counted in chunks of kStageChunkRows, a chunk's stage is its index mod kStageM, and an image of fewer than
+// kStageMinChunks chunks is not staged at all.
+#ifndef PVV_STAGE_M                    // (tools/build_variant.sh -DPVV_STAGE_M=.. -DPVV_STAGE_FIRST=..: schedule sweeps)
+#define PVV_STAGE_M 8
+#define PVV_STAGE_FIRST 0x22u
+#endif
+constexpr int kStageM = PVV_STAGE_M;
+constexpr int kStageMinChunks = 8;
+constexpr int kStageChunkShift = 9;
+constexpr int kStageChunkRows = 1 << kStageChunkShift;

@@ -236,6 +236,17 @@ int32_t pvv_default_cap(int32_t H, int32_t W, int32_t max_num);
  * 256-byte aligned (any hipMalloc / torch allocation is). */
 size_t pvv_workspace_bytes(const pvv_problem *p);
 
+/* ABI v8, additive (ask with dlsym).  Where a layer call on `p` leaves its state inside the workspace, in bytes from its start --
+ * read-only knowledge for tests and tools that read the compacted rows back; nothing here is an input of any call.
+ *   tn [B] i32 | coords [B,cap] f32x2 | dirs [B,K,cap] f32x2 (planar per keypoint) | hyps [B,K,hn] f32x2 | counts [B,K,hn] i32
+ *   deferred [B] i32, 0 = not reserved: the images whose rows outside the first count launch's chunks that launch gathered itself
+ *   (a v3 call counted in stages; every row below tn is there once the call has completed, whoever gathered it).
+ * Returns PVV_OK, or what pvv_workspace_bytes() would have failed with. */
+typedef struct pvv_workspace_offsets {
+    size_t tn, coords, dirs, hyps, counts, deferred, total;
+} pvv_workspace_offsets;
+int pvv_workspace_layout(const pvv_problem *p, pvv_workspace_offsets *out);
+
 /* ransac_voting_layer_v3 (P:112-199).
  *   d_mask      [B,H,W] integer/bool mask, foreground = low byte != 0 (P:125)
  *   d_vertex    [B,H,W,K,2] f32 through p->vertex_stride (f16 / bf16 with PVV_FLAG_VERTEX_F16 / _BF16)
