@@ -2,9 +2,11 @@
 voting call itself, ``libpvnet_nn.so``, ``libpvnet_pnp.so``, ``libpvnet_pose.so``, ``libpvnet_metrics.so``, ``libpvnet_vsd.so``,
 ``libpvnet_icp.so``; ``_build.py`` has the table).
 
-Every device entry point of these libraries takes the stream as its last argument and returns 0 on success.  A module states its
-signatures once and keeps what ``bind`` returns as its ``_lib``: a ``Library``, whose attributes are the ctypes functions, whose
-``call`` is that convention and whose ``workspace`` asks a size query and allocates.  The module's name, the prefix of its
+Every device entry point of these libraries takes the stream as its last argument and returns 0 on success.  The header states
+the signatures: ``libpvnet_<name>.so`` is opened with the ``restype`` / ``argtypes`` of every function ``include/pvnet_<name>.h``
+declares (``declarations``; a declaration its rules do not cover is an ImportError, never a default), so no module, test or tool
+writes a type down.  A module keeps what ``bind`` returns as its ``_lib``: a ``Library``, whose attributes are the ctypes functions,
+whose ``call`` is that convention and whose ``workspace`` asks a size query and allocates.  The module's name, the prefix of its
 messages and the library's error string (``pvv_last_error``, where the library keeps one) are fixed there, so no wrapper repeats
 them around a launch.  ``Library`` is built on the functions below it, which stay importable: ``load`` opens a library, ``call`` /
 ``call_named`` are the convention without and with the error string, ``need_cuda`` / ``workspace`` / ``ptr`` what the wrappers share
@@ -16,23 +18,89 @@ There is no CPU fallback anywhere behind this module.
 """
 import ctypes
 import os
+import re
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 PTR, INT, LONGLONG, DOUBLE, SIZE = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_double, ctypes.c_size_t
 
+# The scalar types of the C ABI.  A parameter with a ``*`` is PTR whatever it points to; ``const char *`` is the one pointer returned.
+_SCALARS = {"int": INT, "int32_t": INT, "long long": LONGLONG, "int64_t": LONGLONG, "size_t": SIZE, "double": DOUBLE,
+            "float": ctypes.c_float, "uint64_t": ctypes.c_uint64, "unsigned": ctypes.c_uint, "uint32_t": ctypes.c_uint}
+_TYPE_WORDS = {"int", "long", "short", "char", "signed", "unsigned", "float", "double", "void"}     # never a parameter's name
+_declarations, _libraries = {}, {}
 
-def load(module, libname, signatures):
-    """``CDLL`` of ``libname`` next to this file for ``clean_pvnet_amd.<module>``, with ``restype`` / ``argtypes`` set from
-    ``signatures``: {symbol: (restype, argtypes)}."""
-    try:
-        lib = ctypes.CDLL(os.path.join(HERE, libname))
-    except OSError as e:
-        raise ImportError("clean_pvnet_amd.%s: %s is not built (run `python __graft_entry__.py`); "
-                          "there is no CPU fallback. Original error: %s" % (module, libname, e)) from e
-    for symbol, (restype, argtypes) in signatures.items():
+
+def parse(text, header="<text>"):
+    """{symbol: (restype, argtypes)} of every function the header text declares.  Comments, preprocessor lines, ``typedef
+    struct {...}`` bodies and the ``extern "C"`` braces are dropped; each statement left must be a function declaration in the
+    types above, and one that is not is an ImportError that names ``header`` and the declaration."""
+    def refuse(declaration):
+        return ImportError("clean_pvnet_amd._native: %s: no ctypes rule covers `%s`" % (header, declaration))
+
+    def scalar(words, declaration, named):
+        m = re.fullmatch(r"(?:const )?(long long|\w+)(?: (\w+))?", words)
+        if not m or m.group(1) not in _SCALARS or m.group(2) in _TYPE_WORDS or (m.group(2) and not named):
+            raise refuse(declaration)
+        return _SCALARS[m.group(1)]
+
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#(?:[^\n]*\\\n)*[^\n]*", " ", text, flags=re.M)
+    text = re.sub(r"\btypedef\s+struct\b[^{};]*\{[^{}]*\}[^;]*;", " ", text)
+    text = re.sub(r'\bextern\s+"C"\s*\{(.*)\}', r"\1", text, flags=re.S)
+    found = {}
+    for declaration in (" ".join(d.split()) for d in text.split(";")):
+        if not declaration:
+            continue
+        m = re.fullmatch(r"(.*?) ?\b(\w+) ?\(([^()]*)\)", declaration)
+        if not m or m.group(2) in found:
+            raise refuse(declaration)
+        returns, symbol, params = m.group(1), m.group(2), m.group(3).strip()
+        if returns == "void":
+            restype = None
+        elif "*" in returns:
+            if not re.fullmatch(r"const char ?\*", returns):
+                raise refuse(declaration)
+            restype = ctypes.c_char_p
+        else:
+            restype = scalar(returns, declaration, named=False)
+        found[symbol] = (restype, [] if params in ("", "void") else
+                         [PTR if "*" in p else scalar(p.strip(), declaration, named=True) for p in params.split(",")])
+    return found
+
+
+def declarations(header):
+    """``parse`` of ``include/<header>``, read once per process."""
+    if header not in _declarations:
+        try:
+            with open(os.path.join(INCLUDE, header)) as f:
+                text = f.read()
+        except OSError as e:
+            raise ImportError("clean_pvnet_amd._native: include/%s, which states the signatures of its library, cannot be read; "
+                              "there is no CPU fallback. Original error: %s" % (header, e)) from e
+        _declarations[header] = parse(text, "include/" + header)
+    return _declarations[header]
+
+
+def declare(lib, header):
+    """``lib``, an open ``CDLL``, with the ``restype`` / ``argtypes`` of every function ``include/<header>`` declares."""
+    for symbol, (restype, argtypes) in declarations(header).items():
         fn = getattr(lib, symbol)
         fn.restype, fn.argtypes = restype, argtypes
     return lib
+
+
+def load(module, libname):
+    """``CDLL`` of ``lib<name>.so`` next to this file for ``clean_pvnet_amd.<module>``, declared by ``include/<name>.h``: opened
+    and declared once per process, the modules bound to one library share it."""
+    if libname not in _libraries:
+        try:
+            lib = ctypes.CDLL(os.path.join(HERE, libname))
+        except OSError as e:
+            raise ImportError("clean_pvnet_amd.%s: %s is not built (run `python __graft_entry__.py`); "
+                              "there is no CPU fallback. Original error: %s" % (module, libname, e)) from e
+        _libraries[libname] = declare(lib, libname[len("lib"):-len(".so")] + ".h")
+    return _libraries[libname]
 
 
 def need_cuda(t, what, module):
@@ -71,16 +139,13 @@ class Library:
     """``libname`` bound for ``clean_pvnet_amd.<module>`` (``load``'s ImportError when it is not built).  ``lib.<symbol>`` is the
     ctypes function, for the host-only entry points and the tests; every launch goes through ``call`` and every workspace
     through ``workspace``.
-    :param signatures:   {symbol: (restype, argtypes)}
-    :param last_error:   the symbol of the library's error string (``"pvv_last_error"``), whose signature is added here; None for
-                         a library that keeps none: its calls fail with the plain message and its size queries refuse nothing
+    :param last_error:   the symbol of the library's error string (``"pvv_last_error"``); None for a library that keeps none: its
+                         calls fail with the plain message and its size queries refuse nothing
     :param prefix:       what a refused workspace's message starts with; ``clean_pvnet_amd.<module>`` by default
     :param plain_calls:  a failed call keeps the plain message although the library has an error string (``crop``, ``det_eval``)"""
 
-    def __init__(self, module, libname, signatures, last_error=None, prefix=None, plain_calls=False):
-        if last_error is not None:
-            signatures = {last_error: (ctypes.c_char_p, []), **signatures}
-        self._cdll = load(module, libname, signatures)
+    def __init__(self, module, libname, last_error=None, prefix=None, plain_calls=False):
+        self._cdll = load(module, libname)
         self._module, self._last_error = module, last_error
         self._prefix = "clean_pvnet_amd.%s" % module if prefix is None else prefix
         self._named = last_error is not None and not plain_calls
@@ -107,7 +172,7 @@ class Library:
         return workspace(nbytes, dev), nbytes
 
 
-bind = Library                       # ``_lib = _native.bind("module", "libpvnet_x.so", {...}, last_error="pvv_last_error")``
+bind = Library                       # ``_lib = _native.bind("module", "libpvnet_x.so", last_error="pvv_last_error")``
 
 
 def ptr(t):

@@ -24,14 +24,8 @@ import math
 import numpy as np
 
 from . import _native
-from ._native import DOUBLE, INT, PTR, SIZE
 
-_lib = _native.bind("augment", "libpvnet_vote.so", {
-    "pvv_augment_workspace_bytes": (SIZE, [INT, INT, INT]),
-    "pvv_pvnet_augment": (INT, [PTR, PTR, PTR, INT, INT, INT, INT, INT, INT, INT, DOUBLE, PTR, INT, INT, PTR, SIZE, PTR, PTR, PTR, PTR, PTR, PTR]),
-    "pvv_transform_workspace_bytes": (SIZE, [INT, INT, INT]),
-    "pvv_pvnet_transform": (INT, [PTR, INT, INT, INT, PTR, INT, INT, PTR, PTR, PTR, SIZE, PTR, PTR]),
-}, last_error="pvv_last_error")
+_lib = _native.bind("augment", "libpvnet_vote.so", last_error="pvv_last_error")
 
 N_DRAWS = 12
 COLUMNS = ("degree", "ratio", "hbeg", "wbeg", "blur", "blur_size", "brightness", "contrast", "saturation", "hue", "order", "unused")

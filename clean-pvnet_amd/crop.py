@@ -14,16 +14,8 @@ parity of the two warps with ``cv2.warpAffine`` is unpinned (DESIGN.md section 1
 import ctypes
 
 from . import _native
-from ._native import DOUBLE, INT, PTR, SIZE
 
-_lib = _native.bind("crop", "libpvnet_vote.so", {
-    "pvv_ct_workspace_bytes": (SIZE, [INT] * 5),
-    "pvv_ct_decode": (INT, [PTR, PTR, INT, INT, INT, INT, INT, INT, PTR, SIZE, PTR, PTR, PTR, PTR]),
-    "pvv_crop_boxes": (INT, [PTR, INT, INT, INT, PTR, PTR, INT, INT, INT, DOUBLE, INT, DOUBLE, PTR, PTR, PTR, SIZE, PTR, PTR, PTR,
-                             PTR, PTR, PTR]),
-    "pvv_uncrop_keypoints": (INT, [PTR, INT, PTR, INT, INT, PTR, PTR]),
-    "pvv_uncrop_mask": (INT, [PTR, INT, INT, INT, PTR, INT, INT, INT, PTR, PTR]),
-}, last_error="pvv_last_error", prefix="crop", plain_calls=True)
+_lib = _native.bind("crop", "libpvnet_vote.so", last_error="pvv_last_error", prefix="crop", plain_calls=True)
 
 MAX_K = 256                        # PVV_CT_MAX_K
 _WORKSPACE_PER_BOX = 96            # PVV_CROP_WORKSPACE_PER_BOX

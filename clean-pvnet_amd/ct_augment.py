@@ -26,13 +26,8 @@ import math
 import numpy as np
 
 from . import _native
-from ._native import INT, PTR, SIZE
 
-_lib = _native.bind("ct_augment", "libpvnet_vote.so", {
-    "pvv_ct_compose": (INT, [PTR] * 5 + [INT] * 6 + [PTR] * 4),
-    "pvv_ct_augment_workspace_bytes": (SIZE, [INT] * 4),
-    "pvv_ct_augment": (INT, [PTR, PTR] + [INT] * 10 + [PTR, PTR, PTR, PTR, SIZE, PTR, PTR, PTR, PTR]),
-}, last_error="pvv_last_error")
+_lib = _native.bind("ct_augment", "libpvnet_vote.so", last_error="pvv_last_error")
 
 # per sample, then (place_y, place_x) per instance
 COLUMNS = ("scale", "center_x", "center_y", "order", "alpha_0", "alpha_1", "alpha_2", "normal_0", "normal_1", "normal_2", "rot")

@@ -15,19 +15,12 @@ from torch import nn
 
 from . import _native
 from ._loss import FusedLoss
-from ._native import INT, LONGLONG, PTR, SIZE
 
 MAX_N = 512                          # PVV_CT_TRAIN_MAX_N
 BOX_KINDS = {torch.float32: 0, torch.int32: 1, torch.int64: 2}        # PVV_BOX_F32, PVV_BOX_I32, PVV_BOX_I64
 _INTS = (torch.int32, torch.int64)
 
-_INPUTS = [PTR, LONGLONG, PTR, LONGLONG, PTR, LONGLONG, PTR, PTR, INT, PTR] + [INT] * 5
-_lib = _native.bind("ct_train", "libpvnet_vote.so", {
-    "pvv_ct_targets": (INT, [PTR, INT, PTR, INT, PTR, INT] + [INT] * 5 + [PTR] * 7),
-    "pvv_ct_loss_workspace_bytes": (SIZE, [INT] * 4),
-    "pvv_ct_loss_forward": (INT, _INPUTS + [PTR, SIZE, PTR, PTR, PTR]),
-    "pvv_ct_loss_backward": (INT, _INPUTS + [PTR, PTR, PTR, PTR, PTR]),
-}, last_error="pvv_last_error")
+_lib = _native.bind("ct_train", "libpvnet_vote.so", last_error="pvv_last_error")
 
 
 def ct_targets(boxes, cls, num, num_classes, height, width):

@@ -15,12 +15,8 @@ import torch
 from torch import nn
 
 from . import _native
-from ._native import INT, LONGLONG, PTR
 
-_lib = _native.bind("dcn", "libpvnet_vote.so", {
-    "pvv_dcn_forward": (INT, [PTR, PTR, PTR, PTR, LONGLONG, PTR, LONGLONG] + [INT] * 14 + [PTR, PTR]),
-    "pvv_dcn_columns": (INT, [PTR, PTR, LONGLONG, PTR, LONGLONG] + [INT] * 13 + [PTR, PTR]),
-}, last_error="pvv_last_error")
+_lib = _native.bind("dcn", "libpvnet_vote.so", last_error="pvv_last_error")
 
 MAX_COLUMNS = 1 << 28              # elements ``columns`` agrees to write
 

@@ -15,12 +15,8 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _native, dcn
-from ._native import INT, LONGLONG, PTR, SIZE
 
-_lib = _native.bind("dcn_train", "libpvnet_vote.so", {
-    "pvv_dcn_backward_workspace_bytes": (LONGLONG, [INT] * 15),
-    "pvv_dcn_backward": (INT, [PTR, PTR, PTR, LONGLONG, PTR, LONGLONG, PTR] + [INT] * 14 + [PTR] * 6 + [SIZE, PTR]),
-}, last_error="pvv_last_error")
+_lib = _native.bind("dcn_train", "libpvnet_vote.so", last_error="pvv_last_error")
 
 SLAB = 512                         # PVV_DCN_SLAB: pixels of one grad_weight chain
 

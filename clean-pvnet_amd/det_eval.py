@@ -18,16 +18,9 @@ import ctypes
 import numpy as np
 
 from . import _native
-from ._native import INT, LONGLONG, PTR, SIZE
 from .ct_augment import affine, invert_affine
 
-_lib = _native.bind("det_eval", "libpvnet_vote.so", {
-    "pvv_det_box_iou": (INT, [PTR, INT, PTR, PTR, INT, PTR, PTR]),
-    "pvv_det_map": (INT, [PTR, PTR, PTR, INT, INT, INT, ctypes.c_float, PTR, PTR, PTR, PTR, PTR, PTR, PTR]),
-    "pvv_det_match": (INT, [PTR, PTR, PTR, PTR, PTR, INT, PTR, INT, INT, PTR, PTR, PTR, PTR, INT, INT, PTR, PTR, PTR, PTR, PTR, PTR]),
-    "pvv_det_accumulate_workspace_bytes": (SIZE, [LONGLONG]),
-    "pvv_det_accumulate": (INT, [PTR, PTR, PTR, LONGLONG, PTR, INT, PTR, PTR, PTR, SIZE, PTR, PTR, PTR, PTR]),
-}, last_error="pvv_last_error", prefix="det_eval", plain_calls=True)
+_lib = _native.bind("det_eval", "libpvnet_vote.so", last_error="pvv_last_error", prefix="det_eval", plain_calls=True)
 
 T, R, A, M = 10, 101, 4, 3         # PVV_DET_T, _R, _A, _M
 MAX_K = 128                        # PVV_DET_MAX_K

@@ -8,19 +8,12 @@ with no full-resolution intermediate in memory; ``PVNetHead`` holds ``convraw`` 
 (-0 == +0); parity with torch's own upsample kernel and with MIOpen's convolution is unpinned.  Forward
 only, BatchNorm in eval mode: inference.  CUDA float32 tensors, the current stream, nothing read back, no CPU fallback.
 """
-import ctypes
-
 import torch
 from torch import nn
 
 from . import _native
-from ._native import INT, LONGLONG, PTR
 
-FLOAT = ctypes.c_float
-_lib = _native.bind("head", "libpvnet_vote.so", {
-    "pvv_head_forward": (INT, [PTR, LONGLONG, PTR, LONGLONG] + [PTR] * 5 + [INT] * 9 + [FLOAT, INT, PTR, PTR]),
-    "pvv_head_upsample": (INT, [PTR, LONGLONG] + [INT] * 6 + [PTR, PTR]),
-}, last_error="pvv_last_error")
+_lib = _native.bind("head", "libpvnet_vote.so", last_error="pvv_last_error")
 
 MAX_UPSAMPLE = 1 << 28             # elements ``upsample2x`` agrees to write
 MAX_M = 64                         # output channels of either convolution

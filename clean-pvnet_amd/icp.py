@@ -12,13 +12,8 @@ import math
 
 from . import _native
 from . import vsd as _vsd
-from ._native import DOUBLE, INT, PTR, SIZE
 
-_lib = _native.bind("icp", "libpvnet_icp.so", {
-    "pvi_workspace_bytes": (SIZE, [INT] * 4),
-    "pvi_refine_batched": (INT, [PTR, PTR, INT, DOUBLE, INT, PTR, INT, INT, INT, PTR, PTR, INT, PTR, PTR, PTR, INT, DOUBLE, INT,
-                                 INT, DOUBLE, DOUBLE, PTR, PTR, PTR, INT, INT, INT, PTR]),
-})
+_lib = _native.bind("icp", "libpvnet_icp.so")
 
 STATUS = ("refined", "empty_render", "not_visible", "rotation_limit", "bad_pose", "small_mask", "bad_index")   # PVI_REFINED ...
 INFO = ("status", "n_syn", "n_real", "n", "rounds")                                                            # PVI_STATUS ...

@@ -9,14 +9,8 @@ call on the current stream, reading ``output['pose']`` where ``pose.solve_pose``
 the reference's hit counts on the device and reads back once, in ``summarize()``.  There is no CPU fallback.
 """
 from . import _native
-from ._native import INT, LONGLONG, PTR, SIZE
 
-_lib = _native.bind("metrics", "libpvnet_metrics.so", {
-    "pvm_adds_slabs": (INT, [INT] * 2),
-    "pvm_workspace_bytes": (SIZE, [INT] * 3),
-    "pvm_pose_metrics_batched": (INT, [PTR] * 8 + [INT] * 4 + [PTR]),
-    "pvm_mask_iou_batched": (INT, [PTR] * 2 + [LONGLONG] * 2 + [INT] * 2 + [PTR] * 2 + [INT] * 3 + [PTR]),
-})
+_lib = _native.bind("metrics", "libpvnet_metrics.so")
 
 COLUMNS = ("add", "adds", "proj2d", "trans_cm", "ang_deg")          # PVM_ADD ... PVM_ANG_DEG
 

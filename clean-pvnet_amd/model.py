@@ -14,20 +14,13 @@ import random
 import torch
 
 from . import _native
-from ._native import INT, PTR, SIZE
 
 AUTO, ONE_BLOCK, TILED = 0, 1, 2     # PVV_FPS_*: ONE_BLOCK runs all rounds in one launch (N <= ONE_BLOCK_MAX), TILED one launch per round
 ONE_BLOCK_MAX = 8192                 # PVV_FPS_ONE_BLOCK_MAX
 TILE = 1024                          # PVV_MODEL_TILE
 MAX_N = 1 << 20                      # PVV_MODEL_MAX_N
 
-_lib = _native.bind("model", "libpvnet_vote.so", {
-    "pvv_fps_workspace_bytes": (SIZE, [INT] * 4),
-    "pvv_fps": (INT, [PTR, PTR, PTR, INT, INT, INT, INT, PTR, SIZE, PTR, PTR]),
-    "pvv_model_workspace_bytes": (SIZE, [INT] * 2),
-    "pvv_model_bounds": (INT, [PTR, INT, PTR, INT, INT, PTR, SIZE, PTR, PTR, PTR]),
-    "pvv_model_diameter": (INT, [PTR, INT, PTR, INT, INT, PTR, SIZE, PTR, PTR]),
-}, last_error="pvv_last_error")
+_lib = _native.bind("model", "libpvnet_vote.so", last_error="pvv_last_error")
 
 
 def _clouds(points, dtypes):

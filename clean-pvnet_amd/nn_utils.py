@@ -6,9 +6,9 @@ arguments (numpy arrays on the host) and return value as the reference; there is
 """
 import numpy as np
 
-from ._native import INT, PTR, bind
+from ._native import bind
 
-_lib = bind("nn_utils", "libpvnet_nn.so", {"findNearestPointIdxLauncher": (None, [PTR] * 3 + [INT] * 5)})
+_lib = bind("nn_utils", "libpvnet_nn.so")
 
 
 def find_nearest_point_idx(ref_pts, que_pts):

@@ -14,14 +14,12 @@ byte for byte); the scalars are computed here in binary64 by the reference's own
 deviation: the clamped gradient is used and not written back to ``p.grad`` (``clip_grad_value_`` writes it; calling it first is
 still fine, clamping twice is the identity).  CUDA float32 tensors, the current stream, nothing read back, no CPU fallback.
 """
-import ctypes
 import math
 
 import numpy as np
 import torch
 
 from . import _native
-from ._native import INT, LONGLONG, PTR
 
 CHUNK = 8192                                     # PVV_OPTIM_CHUNK: elements one block works on
 KINDS = {"adam": 0, "radam": 1, "sgd": 2}        # PVV_OPTIM_ADAM, PVV_OPTIM_RADAM, PVV_OPTIM_SGD
@@ -31,10 +29,7 @@ ROW = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("numel"
                 ("s", "<f4", (8,))])             # pvv_optim_row
 assert ROW.itemsize == 80
 
-_lib = _native.bind("optim", "libpvnet_vote.so", {
-    "pvv_optim_chunk": (INT, []),
-    "pvv_optim_step": (INT, [INT, PTR, PTR, INT, LONGLONG, ctypes.c_float, INT, PTR]),
-}, last_error="pvv_last_error")
+_lib = _native.bind("optim", "libpvnet_vote.so", last_error="pvv_last_error")
 if _lib.pvv_optim_chunk() != CHUNK:
     raise ImportError("clean_pvnet_amd.optim: libpvnet_vote.so was built with PVV_OPTIM_CHUNK = %d, this module expects %d; rebuild"
                       % (_lib.pvv_optim_chunk(), CHUNK))

@@ -14,12 +14,8 @@ those images come back as NaN with their status.  There is no CPU fallback.
 import numpy as np
 
 from . import _native
-from ._native import DOUBLE, INT, PTR
 
-_lib = _native.bind("pose", "libpvnet_pose.so", {
-    "pvp_initial_pose_batched": (INT, [PTR] * 4 + [INT] + [PTR] * 2 + [INT] * 4 + [PTR]),
-    "pvp_pose_batched": (INT, [PTR] * 4 + [INT] + [PTR] * 5 + [INT] * 5 + [DOUBLE, PTR]),
-})
+_lib = _native.bind("pose", "libpvnet_pose.so")
 
 METHODS = {"p3p": 0, "dlt": 1}                    # PVP_START_P3P, PVP_START_DLT
 # d_status codes (PVP_STATUS_*): >= 0 a start was found, < 0 the image's outputs are NaN

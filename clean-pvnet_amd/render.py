@@ -20,13 +20,8 @@ import ctypes
 import numpy as np
 
 from . import _native
-from ._native import DOUBLE, INT, PTR, SIZE
 
-_lib = _native.bind("render", "libpvnet_vote.so", {
-    "pvv_render_workspace_bytes": (SIZE, [INT] * 5),
-    "pvv_render_color": (INT, [PTR] * 3 + [INT, INT, PTR] + [INT] * 3 + [PTR] * 3 + [INT, PTR, PTR] + [INT] * 4 + [DOUBLE] * 3
-                         + [PTR, SIZE] + [PTR] * 6),
-}, last_error="pvv_last_error")
+_lib = _native.bind("render", "libpvnet_vote.so", last_error="pvv_last_error")
 
 MAX_M, MAX_FACES, MAX_SIDE = 255, 1 << 24, 16384          # PVV_RENDER_MAX_M, PVV_RENDER_MAX_FACES, PVV_RENDER_MAX_SIDE
 

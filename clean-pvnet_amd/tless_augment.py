@@ -34,17 +34,9 @@ import math
 import numpy as np
 
 from . import _native, ct_augment
-from ._native import DOUBLE, INT, PTR, SIZE
 from .ct_augment import EIG_VAL, EIG_VEC, MEAN, STD, colour_params, invert_affine
 
-_lib = _native.bind("tless_augment", "libpvnet_vote.so", {
-    "pvv_tless_rotate_side": (INT, [INT, INT]),
-    "pvv_tless_rotate": (INT, [PTR, PTR] + [INT] * 6 + [PTR, PTR]),
-    "pvv_tless_compose_workspace_bytes": (SIZE, [INT] * 8),
-    "pvv_tless_compose": (INT, [PTR] * 11 + [INT] * 10 + [DOUBLE, PTR, SIZE] + [PTR] * 8),
-    "pvv_tless_augment_workspace_bytes": (SIZE, [INT] * 3),
-    "pvv_tless_augment": (INT, [PTR] * 4 + [INT] * 7 + [PTR] * 6 + [SIZE] + [PTR] * 9),
-}, last_error="pvv_last_error")
+_lib = _native.bind("tless_augment", "libpvnet_vote.so", last_error="pvv_last_error")
 
 # per sample, then (rot, dst_y, dst_x) per distractor.  Columns 3-9 lie where ct_augment.COLUMNS has them.
 COLUMNS = ("scale", "box", "top", "order", "alpha_0", "alpha_1", "alpha_2", "normal_0", "normal_1", "normal_2", "rot", "dst_y", "dst_x", "black")

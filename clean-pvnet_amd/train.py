@@ -14,18 +14,11 @@ from torch import nn
 
 from . import _native
 from ._loss import FusedLoss
-from ._native import INT, LONGLONG, PTR, SIZE
 
 MAX_K, MAX_C = 64, 16                # PVV_TRAIN_MAX_K, PVV_TRAIN_MAX_C
 MASK_KINDS = {torch.uint8: 0, torch.bool: 0, torch.int32: 1, torch.int64: 2}     # PVV_MASK_U8, PVV_MASK_I32, PVV_MASK_I64
 
-_INPUTS = [PTR, LONGLONG, PTR, LONGLONG, PTR, INT, PTR, INT, PTR, LONGLONG] + [INT] * 5
-_lib = _native.bind("train", "libpvnet_vote.so", {
-    "pvv_vertex_target": (INT, [PTR, INT, PTR, INT, INT, INT, INT, INT, PTR, PTR]),
-    "pvv_pvnet_loss_workspace_bytes": (SIZE, [INT] * 3),
-    "pvv_pvnet_loss_forward": (INT, _INPUTS + [PTR, SIZE, PTR, PTR, PTR]),
-    "pvv_pvnet_loss_backward": (INT, _INPUTS + [PTR, PTR, PTR, PTR, PTR]),
-}, last_error="pvv_last_error")
+_lib = _native.bind("train", "libpvnet_vote.so", last_error="pvv_last_error")
 
 _F32 = (torch.float32,)
 _DTYPES = {"vertex_pred": _F32, "seg_pred": _F32, "vertex": _F32, "mask": tuple(MASK_KINDS), "kpt_2d": (torch.float32, torch.float64)}

@@ -16,12 +16,8 @@ without ``init_rt`` computes that start on the device (``pose.py``, the same sel
 import numpy as np
 
 from . import _native
-from ._native import DOUBLE, INT, PTR
 
-_lib = _native.bind("un_pnp_utils", "libpvnet_pnp.so", {
-    "uncertainty_pnp": (None, [PTR] * 6 + [INT]),
-    "pvp_uncertainty_pnp_batched": (INT, [PTR] * 7 + [INT] * 5 + [DOUBLE, PTR]),
-})
+_lib = _native.bind("un_pnp_utils", "libpvnet_pnp.so")
 
 
 def rodrigues(w):

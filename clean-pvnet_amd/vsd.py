@@ -11,14 +11,8 @@ reference's any-pair rule and counts the hits on the device; nothing is read bac
 on the current stream in a workspace from the caching allocator.  There is no CPU fallback.
 """
 from . import _native
-from ._native import DOUBLE, INT, PTR, SIZE
 
-_lib = _native.bind("vsd", "libpvnet_vsd.so", {
-    "pvs_render_workspace_bytes": (SIZE, [INT] * 2),
-    "pvs_render_depth_batched": (INT, [PTR] * 6 + [INT] * 6 + [DOUBLE] * 2 + [PTR]),
-    "pvs_vsd_workspace_bytes": (SIZE, [INT] * 6),
-    "pvs_vsd_batched": (INT, [PTR] * 3 + [INT, DOUBLE, PTR, INT, DOUBLE, DOUBLE, INT] + [PTR] * 3 + [INT] * 5 + [PTR]),
-})
+_lib = _native.bind("vsd", "libpvnet_vsd.so")
 
 COSTS = {"step": 0, "tlinear": 1}                                    # PVS_COST_*
 COUNTS = ("union", "inter", "cost")                                  # PVS_UNION, PVS_INTER, PVS_COST

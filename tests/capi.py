@@ -2,16 +2,21 @@
 The GPU parity tests call the library through this (raw device pointers + the current HIP stream)
 as well as through the pybind11 module."""
 import ctypes
+import importlib.util
 import os
-import re
+import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "pvnet_vote.h")
 # PVV_LIBPATH: tools/variant_time.py points the same binding at an experimental build of the library
 LIBPATH = os.environ.get("PVV_LIBPATH") or os.path.join(ROOT, "clean-pvnet_amd", "libpvnet_vote.so")
 
-c_i32, c_i64, c_u64, c_f32, vp, sz = (ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float,
-                                       ctypes.c_void_p, ctypes.c_size_t)
+# clean-pvnet_amd/_native.py on its own (it needs neither torch nor the package): the reader of the headers
+_spec = importlib.util.spec_from_file_location("_pvnet_native", os.path.join(ROOT, "clean-pvnet_amd", "_native.py"))
+native = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(native)
+
+c_i32, c_i64, c_u64, c_f32, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float, ctypes.c_void_p
 
 
 class Problem(ctypes.Structure):
@@ -24,42 +29,35 @@ class Problem(ctypes.Structure):
                 ("d_status", vp), ("ev_marks", vp)]
 
 
+def declared(name="vote"):
+    """The functions include/pvnet_<name>.h declares, as the product's own reader finds them."""
+    return set(native.declarations("pvnet_%s.h" % name))
+
+
+def exported(name="vote"):
+    """The functions libpvnet_<name>.so defines for others (``T`` in the dynamic symbol table)."""
+    nm = subprocess.check_output(["nm", "-D", "--defined-only", libpath(name)]).decode()
+    return {line.split()[-1] for line in nm.splitlines() if " T " in line}
+
+
 def declared_symbols():
-    """Every function the header declares (name, followed by an opening parenthesis at top level)."""
-    txt = open(HEADER).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(pvv_[a-z0-9_]+)\s*\(", txt)))
+    """Every function the voting header declares."""
+    return sorted(declared())
 
 
-_lib = None
+def libpath(name):
+    return LIBPATH if name == "vote" else os.path.join(ROOT, "clean-pvnet_amd", "libpvnet_%s.so" % name)
 
 
-def load():
-    global _lib
-    if _lib is None:
-        L = ctypes.CDLL(LIBPATH)
-        L.pvv_last_error.restype = ctypes.c_char_p
-        L.pvv_workspace_bytes.restype = sz
-        L.pvv_workspace_bytes.argtypes = [ctypes.POINTER(Problem)]
-        L.pvv_default_cap.restype = c_i32
-        L.pvv_default_cap.argtypes = [c_i32, c_i32, c_i32]
-        legacy = [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]
-        L.pvv_generate_hypothesis.argtypes = legacy + [vp]
-        L.pvv_generate_hypothesis_vanishing_point.argtypes = legacy + [vp]
-        L.pvv_voting_for_hypothesis.argtypes = legacy + [c_f32, vp]
-        L.pvv_voting_for_hypothesis_vanishing_point.argtypes = legacy + [c_f32, vp]
-        L.pvv_count_inliers.argtypes = legacy + [c_f32, vp]
-        L.pvv_ransac_voting_v3.argtypes = [ctypes.POINTER(Problem), vp, vp, vp, vp, vp, sz, vp, vp, vp, vp]
-        L.pvv_decode_keypoint_v3.argtypes = [ctypes.POINTER(Problem), vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp]
-        L.pvv_estimate_voting_distribution.argtypes = [ctypes.POINTER(Problem), vp, vp, vp, vp, vp, vp, sz,
-                                                       vp, vp, vp, vp, vp, vp]
-        L.pvv_rerun_count_kernel.argtypes = [ctypes.POINTER(Problem), vp, sz, ctypes.c_int, vp]
-        L.pvv_stream_read_probe.argtypes = [vp, sz, vp, vp]
-        L.pvv_stage_hint_query.argtypes = [ctypes.POINTER(c_f32), ctypes.POINTER(c_f32), ctypes.POINTER(Problem), vp]
-        L.pvv_shutdown.argtypes = []
-        L.pvv_estimate_counts_in_stages.argtypes = [ctypes.POINTER(Problem)]
-        _lib = L
-    return _lib
+_libs = {}
+
+
+def load(name="vote"):
+    """libpvnet_<name>.so with the signature of every function its header declares (a ``pvv_problem *`` is a void pointer:
+    pass ``ctypes.byref(problem)``)."""
+    if name not in _libs:
+        _libs[name] = native.declare(ctypes.CDLL(libpath(name)), "pvnet_%s.h" % name)
+    return _libs[name]
 
 
 def problem(mask, vertex, hn, thresh, min_num=5, max_num=30000, policy=0, seed=0, count_kernel=0, draws_out=None,

@@ -5,17 +5,14 @@ colour jitter is PIL's byte for byte, its fixed-point resampling and blur stay w
 samplers, and the degenerate cases take the stated paths.  The GPU tests (tests/test_gpu_augment.py) then hold the device to
 the twin byte for byte."""
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import augment_twin as twin
-from tests import crop_twin
+from tests import capi, crop_twin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-VOTELIB = os.path.join(ROOT, "clean-pvnet_amd", "libpvnet_vote.so")
 HEADER = os.path.join(ROOT, "include", "pvnet_vote.h")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 FIXTURES = ("augment_mixed_40x66", "augment_mixed_44x40", "augment_defaults_40x66")
@@ -34,10 +31,8 @@ def test_module_imports(pkg):
 
 
 def test_header_declares_and_library_exports_the_entry_points():
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    assert SYMBOLS <= set(re.findall(r"\b(pvv_[a-z0-9_]+)\s*\(", txt))
-    nm = subprocess.check_output(["nm", "-D", "--defined-only", VOTELIB]).decode()
-    assert SYMBOLS <= {l.split()[-1] for l in nm.splitlines() if " T " in l}
+    assert SYMBOLS <= capi.declared()
+    assert SYMBOLS <= capi.exported()
     assert "#define PVV_ABI_VERSION 8" in open(HEADER).read()                      # additive: the version did not move
 
 

@@ -5,17 +5,15 @@ warp against a plain binary64 bilinear sampler, and the two ways back against wh
 (tests/test_gpu_crop.py) then hold the device to the twin bit for bit."""
 import ctypes
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import capi
 from tests import crop_twin as twin
 from tests import tolerances as tol
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-VOTELIB = os.path.join(ROOT, "clean-pvnet_amd", "libpvnet_vote.so")
 HEADER = os.path.join(ROOT, "include", "pvnet_vote.h")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 FIXTURES = ("crop_ct_small", "crop_ct_seams", "crop_ct_full")
@@ -39,19 +37,13 @@ def test_module_imports(pkg):
 
 
 def test_header_declares_and_library_exports_the_five_entry_points():
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = set(re.findall(r"\b(pvv_[a-z0-9_]+)\s*\(", txt))
-    assert SYMBOLS <= declared
-    nm = subprocess.check_output(["nm", "-D", "--defined-only", VOTELIB]).decode()
-    exported = {l.split()[-1] for l in nm.splitlines() if " T " in l}
-    assert SYMBOLS <= exported
+    assert SYMBOLS <= capi.declared()
+    assert SYMBOLS <= capi.exported()
     assert "#define PVV_ABI_VERSION 8" in open(HEADER).read()                      # additive: the version did not move
 
 
 def test_host_side_argument_checks():
-    L = ctypes.CDLL(VOTELIB)
-    L.pvv_ct_workspace_bytes.restype = ctypes.c_size_t
-    L.pvv_last_error.restype = ctypes.c_char_p
+    L = capi.load()
     up = lambda n: (n + 255) // 256 * 256                                          # noqa: E731
     # 135 x 180 = 5 x 6 tiles, 30 classes: 900 lists of 100 keys, then 29
     assert L.pvv_ct_workspace_bytes(1, 30, 135, 180, 100) == up(900 * 100 * 8) + up(29 * 100 * 8)

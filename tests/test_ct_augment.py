@@ -7,17 +7,14 @@ sampler and its ownership rule is the binary64 bilinear sample of the mask.  The
 hold the device to the twin byte for byte."""
 import math
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from tests import crop_twin
+from tests import capi, crop_twin
 from tests import ct_augment_twin as twin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-VOTELIB = os.path.join(ROOT, "clean-pvnet_amd", "libpvnet_vote.so")
 HEADER = os.path.join(ROOT, "include", "pvnet_vote.h")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 FIXTURES = ("ct_augment_mixed_30x50", "ct_augment_wide_30x50", "ct_augment_test_30x50")
@@ -51,10 +48,8 @@ def test_module_imports(pkg):
 
 def test_header_declares_and_library_exports_the_entry_points():
     raw = open(HEADER).read()
-    txt = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    assert SYMBOLS <= set(re.findall(r"\b(pvv_[a-z0-9_]+)\s*\(", txt))
-    nm = subprocess.check_output(["nm", "-D", "--defined-only", VOTELIB]).decode()
-    assert SYMBOLS <= {l.split()[-1] for l in nm.splitlines() if " T " in l}
+    assert SYMBOLS <= capi.declared()
+    assert SYMBOLS <= capi.exported()
     assert "#define PVV_ABI_VERSION 8" in raw                                      # additive: the version did not move
     assert "Detector augmentation" in raw and "#define PVV_CT_AUGMENT_PARAM_BYTES 160" in raw and "#define PVV_CT_AUGMENT_MAX_N 16" in raw
     section = raw[raw.index("Detector augmentation"):raw.index("Detector training")]

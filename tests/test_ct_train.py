@@ -11,18 +11,15 @@ the float32 values of the two.  log(1 - hi) differs by 1.66e-4 between them at e
 float64 run the twin is evaluated with that run's own two constants, and against the float32 run with the contract's.  With the
 contract's constants the distance to the float64 run was 0 ulps (c3_37x53), 2 (c30_34x45_int, no_pos), 145 (clamp12) and
 149 (clamp30): the constants, not the arithmetic."""
-import ctypes
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import capi
 from tests import ct_train_twin as twin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-VOTELIB = os.path.join(ROOT, "clean-pvnet_amd", "libpvnet_vote.so")
 HEADER = os.path.join(ROOT, "include", "pvnet_vote.h")
 SYMBOLS = {"pvv_ct_targets", "pvv_ct_loss_workspace_bytes", "pvv_ct_loss_forward", "pvv_ct_loss_backward"}
 TITLE = "Detector training: heat-map targets and the detector loss"
@@ -160,8 +157,7 @@ def test_zero_weight_padding_changes_neither_loss():
 # ------------------------------------------------------------------------------------------------ 2. the header and the symbols
 def test_header_declares_and_library_exports_the_entry_points(pkg):
     raw = open(HEADER).read()
-    txt = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = re.findall(r"\b(pvv_[a-z0-9_]+)\s*\(", txt)
+    declared = list(capi.native.declarations("pvnet_vote.h"))                                # in the header's order
     assert SYMBOLS <= set(declared) and set(declared[-8:-4]) == SYMBOLS                      # directly before the last section
     assert TITLE in raw and raw.index("Model metadata (ABI v8") < raw.index(TITLE) < raw.index("Training: vote targets and the PVNet loss")
     section = raw[raw.index(TITLE):raw.index("Training: vote targets and the PVNet loss")]
@@ -171,9 +167,7 @@ def test_header_declares_and_library_exports_the_entry_points(pkg):
     for symbol, cite in (("pvv_ct_targets", "P:46-66"), ("pvv_ct_loss_forward", "T:20-26"), ("pvv_ct_loss_backward", "T:20-26")):
         before = section[:section.index("int %s(" % symbol)]
         assert cite in before[before.rindex("/*"):]                                          # each entry point cites what it replaces
-    nm = subprocess.check_output(["nm", "-D", "--defined-only", VOTELIB]).decode()
-    exported = {l.split()[-1] for l in nm.splitlines() if " T " in l}
-    assert SYMBOLS <= exported
+    assert SYMBOLS <= capi.exported()
     assert "#define PVV_ABI_VERSION 8" in raw                                                # additive: the version did not move
     import lib
     table = lib.load_build().HIP_LIBS
@@ -192,18 +186,6 @@ def test_module_imports(pkg):
 
 
 # ------------------------------------------------------------------------------------------------ 3. the host-only checks
-def _lib():
-    L = ctypes.CDLL(VOTELIB)
-    L.pvv_last_error.restype = ctypes.c_char_p
-    P, I, LL, S = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_size_t
-    inputs = [P, LL, P, LL, P, LL, P, P, I, P] + [I] * 5
-    L.pvv_ct_loss_workspace_bytes.restype, L.pvv_ct_loss_workspace_bytes.argtypes = S, [I] * 4
-    L.pvv_ct_loss_forward.argtypes = inputs + [P, S, P, P, P]
-    L.pvv_ct_loss_backward.argtypes = inputs + [P, P, P, P, P]
-    L.pvv_ct_targets.argtypes = [P, I, P, I, P, I] + [I] * 5 + [P] * 7
-    return L
-
-
 def _workspace(B, C, H, W):
     """What the layout of the header gives: per (image, tile) two binary64 and one int64, per image four binary64 and two int64,
     each of the four parts rounded up to 256 bytes."""
@@ -214,13 +196,13 @@ def _workspace(B, C, H, W):
 
 @pytest.mark.parametrize("B,C,H,W", [(2, 3, 37, 53), (1, 4, 8, 12), (1, 30, 135, 180), (32, 30, 135, 180)])
 def test_workspace_sizes(B, C, H, W):
-    got = _lib().pvv_ct_loss_workspace_bytes(B, C, H, W)
+    got = capi.load().pvv_ct_loss_workspace_bytes(B, C, H, W)
     assert got == _workspace(B, C, H, W) and got % 256 == 0
     assert got < 1 << 20                                                                     # partials, not maps
 
 
 def test_host_side_refusals():
-    L = _lib()
+    L = capi.load()
     x = 256                                                                                  # a pointer that is not NULL: never dereferenced
 
     def fwd(B=1, N=4, C=3, H=8, W=8, hp=x, wh=x, ind=x, strides=None, ws=x, nbytes=1 << 20, losses=x, state=x):

@@ -7,17 +7,15 @@ import ctypes
 import ctypes.util
 import importlib.util
 import os
-import re
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+from tests import capi
 from tests import dcn_twin as twin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-VOTELIB = os.path.join(ROOT, "clean-pvnet_amd", "libpvnet_vote.so")
 HEADER = os.path.join(ROOT, "include", "pvnet_vote.h")
 REFERENCE_DCN = "/root/reference/lib/networks/dcn_v2.py"
 SYMBOLS = {"pvv_dcn_forward", "pvv_dcn_columns"}
@@ -32,26 +30,13 @@ def test_module_imports(pkg):
 
 
 def test_header_declares_and_library_exports_the_two_entry_points():
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = set(re.findall(r"\b(pvv_[a-z0-9_]+)\s*\(", txt))
-    assert SYMBOLS <= declared
-    nm = subprocess.check_output(["nm", "-D", "--defined-only", VOTELIB]).decode()
-    exported = {l.split()[-1] for l in nm.splitlines() if " T " in l}
-    assert SYMBOLS <= exported
+    assert SYMBOLS <= capi.declared()
+    assert SYMBOLS <= capi.exported()
     assert "#define PVV_ABI_VERSION 8" in open(HEADER).read()                      # additive: the version did not move
 
 
-def _lib():
-    L = ctypes.CDLL(VOTELIB)
-    L.pvv_last_error.restype = ctypes.c_char_p
-    P, I, LL = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
-    L.pvv_dcn_forward.argtypes = [P, P, P, P, LL, P, LL] + [I] * 14 + [P, P]
-    L.pvv_dcn_columns.argtypes = [P, P, LL, P, LL] + [I] * 13 + [P, P]
-    return L
-
-
 def test_host_side_argument_checks():
-    L = _lib()
+    L = capi.load()
     x = 256                                                                         # a pointer that is not NULL: never dereferenced
     geo = (3, 3, 1, 1, 1, 1, 1, 1)                                                  # kh, kw, stride, pad, dilation
     fwd = lambda ptrs, strides, shape, g=geo, dg=1: L.pvv_dcn_forward(ptrs[0], ptrs[1], ptrs[2], ptrs[3], strides[0], ptrs[4],  # noqa: E731

@@ -4,18 +4,15 @@ function in torch ops in binary64, differentiated by autograd --, its fixed-poin
 not depend on the order of arrival, the module refuses what ``dcn`` refuses, keeps the reference's parameter names and swaps
 into a model, and the library exports what the header declares.  The GPU tests (tests/test_gpu_dcn_train.py) then hold the
 device to the twin bit for bit."""
-import ctypes
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import capi
 from tests import dcn_train_twin as twin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-VOTELIB = os.path.join(ROOT, "clean-pvnet_amd", "libpvnet_vote.so")
 HEADER = os.path.join(ROOT, "include", "pvnet_vote.h")
 F32 = np.float32
 NAMES = ("grad_input", "grad_offset", "grad_mask", "grad_weight", "grad_bias")
@@ -191,24 +188,15 @@ def test_convert_swaps_the_classes_and_keeps_the_parameters(pkg):
 
 # ------------------------------------------------------------------------------------------------ 4. header and library
 def test_header_declares_and_library_exports_the_backward_entry_points():
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = {s for s in re.findall(r"\b(pvv_[a-z0-9_]+)\s*\(", txt) if s.startswith("pvv_dcn_backward")}
+    declared = {s for s in capi.declared() if s.startswith("pvv_dcn_backward")}
     assert declared == {"pvv_dcn_backward", "pvv_dcn_backward_workspace_bytes"}
-    nm = subprocess.check_output(["nm", "-D", "--defined-only", VOTELIB]).decode()
-    exported = {line.split()[-1] for line in nm.splitlines() if " T " in line}
-    assert declared <= exported
-    L = ctypes.CDLL(VOTELIB)
-    assert L.pvv_abi_version() == 8 and "#define PVV_ABI_VERSION 8" in open(HEADER).read()
+    assert declared <= capi.exported()
+    assert capi.load().pvv_abi_version() == 8 and "#define PVV_ABI_VERSION 8" in open(HEADER).read()
     assert "#define PVV_DCN_SLAB %d" % twin.SLAB in open(HEADER).read()
 
 
 def test_workspace_is_bounded_whatever_the_batch_and_the_host_checks():
-    L = ctypes.CDLL(VOTELIB)
-    L.pvv_last_error.restype = ctypes.c_char_p
-    L.pvv_dcn_backward_workspace_bytes.restype = ctypes.c_longlong
-    L.pvv_dcn_backward_workspace_bytes.argtypes = [ctypes.c_int] * 15
-    P, I, LL = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
-    L.pvv_dcn_backward.argtypes = [P, P, P, LL, P, LL, P] + [I] * 14 + [P] * 6 + [ctypes.c_size_t, P]
+    L = capi.load()
     geo = (3, 3, 1, 1, 1, 1, 1, 1, 1)
     ws = lambda B, chunk=0, shape=(64, 135, 180, 64): L.pvv_dcn_backward_workspace_bytes(B, *shape, *geo, chunk)   # noqa: E731
     one = ws(1)

@@ -6,17 +6,15 @@ away from the reference's on the fixture named for it.  The GPU tests (tests/tes
 bit for bit."""
 import os
 import re
-import subprocess
 import types
 
 import numpy as np
 import pytest
 
+from tests import capi
 from tests import det_eval_twin as twin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-VOTELIB = os.path.join(ROOT, "clean-pvnet_amd", "libpvnet_vote.so")
-METRICSLIB = os.path.join(ROOT, "clean-pvnet_amd", "libpvnet_metrics.so")
 HEADER = os.path.join(ROOT, "include", "pvnet_vote.h")
 FIXTURES = tuple(twin.SCENARIOS)
 SYMBOLS = {"pvv_det_box_iou", "pvv_det_map", "pvv_det_match", "pvv_det_accumulate_workspace_bytes", "pvv_det_accumulate"}
@@ -28,11 +26,6 @@ TIE_MARGIN = 1e-7
 
 def _bits(a):
     return np.ascontiguousarray(np.asarray(a, np.float64)).view(np.uint64)
-
-
-def _exported(path):
-    nm = subprocess.check_output(["nm", "-D", "--defined-only", path]).decode()
-    return {l.split()[-1] for l in nm.splitlines() if " T " in l}
 
 
 # ------------------------------------------------------------------------------------------------ 0. the module and the symbols
@@ -47,9 +40,9 @@ def test_module_imports(pkg):
 
 def test_header_declares_and_vote_library_exports_the_entry_points():
     txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    assert SYMBOLS <= set(re.findall(r"\b(pvv_[a-z0-9_]+)\s*\(", txt))
-    assert SYMBOLS <= _exported(VOTELIB)
-    assert not any(s.startswith("pvv_det_") for s in _exported(METRICSLIB))
+    assert SYMBOLS <= capi.declared()
+    assert SYMBOLS <= capi.exported()
+    assert not any(s.startswith("pvv_det_") for s in capi.exported("metrics"))
     assert "#define PVV_ABI_VERSION 8" in open(HEADER).read()                      # additive: the version did not move
     for name, value in (("T", twin.T), ("R", twin.R), ("A", twin.A), ("M", twin.M), ("MAX_K", twin.MAX_K), ("MAX_D", twin.MAX_D),
                         ("MAX_G", twin.MAX_G)):
@@ -58,10 +51,7 @@ def test_header_declares_and_vote_library_exports_the_entry_points():
 
 def test_library_refuses_bad_arguments_before_any_launch():
     import ctypes
-    L = ctypes.CDLL(VOTELIB)
-    L.pvv_det_accumulate_workspace_bytes.restype = ctypes.c_size_t
-    L.pvv_det_accumulate_workspace_bytes.argtypes = [ctypes.c_longlong]
-    L.pvv_last_error.restype = ctypes.c_char_p
+    L = capi.load()
     up = lambda n: (n + 255) // 256 * 256                                          # noqa: E731
     assert L.pvv_det_accumulate_workspace_bytes(1000) == 3 * up(120 * 1000 * 4) + 120 * 1000 * 8
     assert L.pvv_det_accumulate_workspace_bytes(1 << 31) == 0 and b"2^31" in L.pvv_last_error()

@@ -17,7 +17,6 @@ voting batches are new (``synth.make_batch``) and listed at ``VOTE_CASES``.
 Out of reach of this method, and out of scope: the host-pointer launchers (``findNearestPointIdxLauncher`` of libpvnet_nn, the host
 entry of libpvnet_pnp) allocate with ``hipMalloc`` inside the library; ``dist`` / ``rccl``, graph capture and side streams.
 """
-import ctypes
 import functools
 import os
 
@@ -846,8 +845,7 @@ def test_box_iou_and_the_detector_evaluator(pkg, gpu):
 # ------------------------------------------------------------------------------------------------------------ nn
 def test_nn_find_nearest_on_device_pointers(oracle, pkg, gpu):
     """test_nn.test_hip_nearest_neighbour_device_pointers_batched_exclude_self: b = 3, pn = 777, every point's nearest other point."""
-    L = ctypes.CDLL(os.path.join(ROOT, "clean-pvnet_amd", "libpvnet_nn.so"))
-    L.pvv_nn_find_nearest.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_void_p]
+    L = capi.load("nn")
     b, pn, dim = 3, 777, 3
     pts = np.random.RandomState(4).randn(b, pn, dim).astype(np.float32)
 

@@ -258,8 +258,6 @@ def test_no_fp32_copy_of_either_field(synth, pkg, gpu):
     from clean_pvnet_amd import ransac_voting as ext
     from clean_pvnet_amd.decode import decode_keypoint
     L = capi.load()
-    L.pvv_workspace_bytes_un_pnp.restype = ctypes.c_size_t
-    L.pvv_workspace_bytes_un_pnp.argtypes = [ctypes.POINTER(capi.Problem), ctypes.c_int32]
     B, H, W, K = 64, 480, 640, 9
     seg, ver = network_output(synth, gpu, B, H, W, K, torch.bfloat16, seed=64)
     vertex = ver.permute(0, 2, 3, 1).view(B, H, W, K, 2)

@@ -271,12 +271,10 @@ def test_a_refused_call_reads_as_its_binding_says(pkg, gpu):
     """``_native.bind(...).call``: the library refuses NULL pointers in host code, before any launch; bound with the error string
     the failure names the module and says what the library recorded, bound without it reads plainly."""
     from clean_pvnet_amd import _native
-    from clean_pvnet_amd._native import INT, PTR
-    signatures = {"pvv_vertex_target": (INT, [PTR, INT, PTR, INT, INT, INT, INT, INT, PTR, PTR])}
     args = (None, 0, None, 0, 1, 1, 4, 4, None)                                     # B = K = 1, H = W = 4, NULL tensors
     with pytest.raises(RuntimeError) as ei:
-        _native.bind("probe", "libpvnet_vote.so", signatures, last_error="pvv_last_error").call("pvv_vertex_target", gpu, *args)
+        _native.bind("probe", "libpvnet_vote.so", last_error="pvv_last_error").call("pvv_vertex_target", gpu, *args)
     assert str(ei.value) == "clean_pvnet_amd.probe: pvv_vertex_target failed (-1): train: NULL device pointer"
     with pytest.raises(RuntimeError) as ei:
-        _native.bind("probe", "libpvnet_vote.so", signatures).call("pvv_vertex_target", gpu, *args)
+        _native.bind("probe", "libpvnet_vote.so").call("pvv_vertex_target", gpu, *args)
     assert str(ei.value) == "pvv_vertex_target failed (-1)"

@@ -39,8 +39,6 @@ def test_workspace_bytes_are_the_same_for_every_field_dtype():
 
 def test_fused_un_pnp_workspace_and_staging_queries_ignore_the_dtype():
     L = capi.load()
-    L.pvv_workspace_bytes_un_pnp.restype = ctypes.c_size_t
-    L.pvv_workspace_bytes_un_pnp.argtypes = [ctypes.POINTER(capi.Problem), ctypes.c_int32]
     for bits in (0, 2, 4, 8, 16, 4 | 16):
         p = _problem(1 | bits)
         assert L.pvv_workspace_bytes_un_pnp(ctypes.byref(p), 4096) == L.pvv_workspace_bytes_un_pnp(ctypes.byref(_problem(1)), 4096)

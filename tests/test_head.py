@@ -3,18 +3,15 @@ and their argument checks exist; the numpy twin of the contract (tests/head_twin
 reference's own expression -- torch's modules as lib/networks/pvnet/resnet18.py:53-59, 90-92 state it, eval mode, float64 -- and
 leaves that bound as soon as one of the contract's rules is stated wrongly.  The GPU tests (tests/test_gpu_head.py) then hold the
 device to the twin bit for bit."""
-import ctypes
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import capi
 from tests import head_twin as twin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-VOTELIB = os.path.join(ROOT, "clean-pvnet_amd", "libpvnet_vote.so")
 HEADER = os.path.join(ROOT, "include", "pvnet_vote.h")
 SYMBOLS = {"pvv_head_forward", "pvv_head_upsample"}
 F32 = np.float32
@@ -28,26 +25,13 @@ def test_module_imports(pkg):
 
 
 def test_header_declares_and_library_exports_the_two_entry_points():
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = set(re.findall(r"\b(pvv_[a-z0-9_]+)\s*\(", txt))
-    assert SYMBOLS <= declared
-    nm = subprocess.check_output(["nm", "-D", "--defined-only", VOTELIB]).decode()
-    exported = {l.split()[-1] for l in nm.splitlines() if " T " in l}
-    assert SYMBOLS <= exported
+    assert SYMBOLS <= capi.declared()
+    assert SYMBOLS <= capi.exported()
     assert "#define PVV_ABI_VERSION 8" in open(HEADER).read()                      # additive: the version did not move
 
 
-def _lib():
-    L = ctypes.CDLL(VOTELIB)
-    L.pvv_last_error.restype = ctypes.c_char_p
-    P, I, LL = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
-    L.pvv_head_forward.argtypes = [P, LL, P, LL] + [P] * 5 + [I] * 9 + [ctypes.c_float, I, P, P]
-    L.pvv_head_upsample.argtypes = [P, LL] + [I] * 6 + [P, P]
-    return L
-
-
 def test_host_side_argument_checks():
-    L = _lib()
+    L = capi.load()
     x = 256                                                                         # a pointer that is not NULL: never dereferenced
     ok = dict(B=2, C2=4, C0=3, h=5, w=6, H=10, W=12, M1=8, M2=6)
 

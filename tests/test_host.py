@@ -24,9 +24,7 @@ def test_cabi_library_exports_every_declared_symbol():
     L = ctypes.CDLL(capi.LIBPATH)
     for n in names:
         assert hasattr(L, n), "libpvnet_vote.so does not export %s" % n
-    nm = subprocess.check_output(["nm", "-D", "--defined-only", capi.LIBPATH]).decode()
-    exported = {l.split()[-1] for l in nm.splitlines() if " T " in l}
-    assert {e for e in exported if e.startswith("pvv_")} == set(names)     # nothing undeclared leaks out either
+    assert {e for e in capi.exported() if e.startswith("pvv_")} == set(names)     # nothing undeclared leaks out either
 
 
 def test_cabi_version_and_cap_and_validation():
@@ -482,7 +480,7 @@ def test_native_loader_refuses_a_library_that_is_not_built():
     and the library, says how to build it and that nothing stands in for it.  The module itself needs no torch."""
     native = _load_file("_native_alone", ROOT, "clean-pvnet_amd", "_native.py")
     with pytest.raises(ImportError) as ei:
-        native.load("nowhere", "libpvnet_nowhere.so", {})
+        native.load("nowhere", "libpvnet_nowhere.so")
     msg = str(ei.value)
     assert "clean_pvnet_amd.nowhere: libpvnet_nowhere.so is not built" in msg
     assert "`python __graft_entry__.py`" in msg and "no CPU fallback" in msg
@@ -491,17 +489,17 @@ def test_native_loader_refuses_a_library_that_is_not_built():
 
 
 def _probe(native, **kw):
-    return native.bind("probe", "libpvnet_vote.so", {"pvv_ct_loss_workspace_bytes": (native.SIZE, [native.INT] * 4)}, **kw)
+    return native.bind("probe", "libpvnet_vote.so", **kw)
 
 
 def test_native_bind_opens_as_load_does_and_exposes_the_functions():
     """``bind`` is ``load`` with the module's name kept: the same ImportError for a library that is not built, the ctypes
-    functions as attributes with their signatures set, and the error string's signature added when one is named."""
+    functions as attributes with the signatures the header declares, the error string's among them."""
     native = _load_file("_native_bind", ROOT, "clean-pvnet_amd", "_native.py")
     texts = []
     for opener in (native.load, native.bind):
         with pytest.raises(ImportError) as ei:
-            opener("nowhere", "libpvnet_nowhere.so", {})
+            opener("nowhere", "libpvnet_nowhere.so")
         texts.append(str(ei.value))
     assert texts[0] == texts[1] and "clean_pvnet_amd.nowhere: libpvnet_nowhere.so is not built" in texts[1]
     lib = _probe(native, last_error="pvv_last_error")

@@ -2,19 +2,17 @@
 fixtures made by the reference's own ``ICPRefiner.refine`` (tests/golden/make_icp_golden.py), the twin's rotation against an
 SVD, the cases that leave a pose unchanged, the library's exports and its host-side argument checks.  The GPU tests
 (tests/test_gpu_icp.py) then hold the device to the twin bit for bit."""
-import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 
+from tests import capi
 from tests import icp_twin as twin
 from tests import tolerances as tol
 from tests import vsd_twin as vt
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ICPLIB = os.path.join(ROOT, "clean-pvnet_amd", "libpvnet_icp.so")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 FIXTURES = ("icp_720", "icp_360", "icp_edge")
 SYMBOLS = {"pvi_workspace_bytes", "pvi_refine_batched"}
@@ -179,35 +177,24 @@ def test_icp_fixtures_are_reproducible_from_the_reference():
 
 # ------------------------------------------------------------------------------------------- 3. the library and its arguments
 def test_icp_library_exports_what_the_header_declares():
-    txt = open(os.path.join(ROOT, "include", "pvnet_icp.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    names = set(re.findall(r"\b(pvi_[a-z_]+)\s*\(", txt))
+    names = capi.declared("icp")
     assert names == SYMBOLS
-    L = ctypes.CDLL(ICPLIB)
+    L = capi.load("icp")
     for n in names:
         assert hasattr(L, n)
-    import shutil
-    import subprocess
-    nm = shutil.which("nm") or shutil.which("llvm-nm", path=os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin"))
-    if nm:                                                       # and nothing else is exported
-        out = subprocess.run([nm, "-D", "--defined-only", ICPLIB], capture_output=True, text=True, check=True).stdout
-        exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
-        assert {e for e in exported if not e.startswith("_")} == names, exported
+    exported = capi.exported("icp")                              # and nothing else is exported
+    assert {e for e in exported if not e.startswith("_")} == names, exported
 
 
 def test_workspace_size_and_argument_errors():
     """Bad arguments are refused before anything is launched (no GPU is needed to be told so)."""
-    L = ctypes.CDLL(ICPLIB)
-    L.pvi_workspace_bytes.restype = ctypes.c_size_t
+    L = capi.load("icp")
     assert L.pvi_workspace_bytes(0, 540, 720, 3000) == 0 and L.pvi_workspace_bytes(2, 0, 720, 3000) == 0
     assert L.pvi_workspace_bytes(2, 540, 720, 0) == 0 and L.pvi_workspace_bytes(2, 540, 720, 16385) == 0
     one, two = L.pvi_workspace_bytes(1, 540, 720, 3000), L.pvi_workspace_bytes(2, 540, 720, 3000)
     assert 0 < one < two <= 2 * one and two % 16 == 0
     assert one >= 3 * 3 * 3000 * 8 + 12 * 3000 * 12 + 1519 * (24 + 8)            # samples, slab partials, tile sums and counts
-    from clean_pvnet_amd._native import DOUBLE, INT, PTR
     f = L.pvi_refine_batched
-    f.argtypes = [PTR, PTR, INT, DOUBLE, INT, PTR, INT, INT, INT, PTR, PTR, INT, PTR, PTR, PTR, INT, DOUBLE, INT, INT, DOUBLE,
-                  DOUBLE, PTR, PTR, PTR, INT, INT, INT, PTR]
 
     def call(P=0, kind=0, mkind=0, flags=0, n_max=3000, iters=200, tolerance=5e-7, H=48, W=64, per=1):
         return f(None, None, kind, 0.1, per, None, mkind, 1, 0, None, None, 0, None, None, None, flags, 2.0, n_max, iters,

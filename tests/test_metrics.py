@@ -2,17 +2,15 @@
 header declares, there is no CPU fallback, the fixtures are reproducible from the reference's own evaluator, and the numpy
 twin of the arithmetic contract (tests/metrics_twin.py) reproduces every fixture -- which is what lets the GPU tests use the
 twin where the fixtures have no case."""
-import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 
+from tests import capi
 from tests import metrics_twin as twin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-METRICSLIB = os.path.join(ROOT, "clean-pvnet_amd", "libpvnet_metrics.so")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 POSE_FIXTURES = ("metrics_n5841", "metrics_n777")
 
@@ -22,25 +20,17 @@ def load(name):
 
 
 def test_metrics_library_exports_what_the_header_declares():
-    txt = open(os.path.join(ROOT, "include", "pvnet_metrics.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    names = set(re.findall(r"\b(pvm_[a-z_]+)\s*\(", txt))
+    names = capi.declared("metrics")
     assert names == {"pvm_adds_slabs", "pvm_workspace_bytes", "pvm_pose_metrics_batched", "pvm_mask_iou_batched"}
-    L = ctypes.CDLL(METRICSLIB)
+    L = capi.load("metrics")
     for n in names:
         assert hasattr(L, n)
-    import shutil
-    import subprocess
-    nm = shutil.which("nm") or shutil.which("llvm-nm", path=os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin"))
-    if nm:                                                       # and nothing else is exported
-        out = subprocess.run([nm, "-D", "--defined-only", METRICSLIB], capture_output=True, text=True, check=True).stdout
-        exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
-        assert {e for e in exported if not e.startswith("_")} == names, exported
+    exported = capi.exported("metrics")                          # and nothing else is exported
+    assert {e for e in exported if not e.startswith("_")} == names, exported
 
 
 def test_workspace_size_and_slab_rule():
-    L = ctypes.CDLL(METRICSLIB)
-    L.pvm_workspace_bytes.restype = ctypes.c_size_t
+    L = capi.load("metrics")
     assert L.pvm_workspace_bytes(0, 5841, 0) == 0 and L.pvm_workspace_bytes(4, 0, 0) == 0
     s1, s64 = L.pvm_adds_slabs(1, 5841), L.pvm_adds_slabs(64, 5841)
     assert 6 * s1 >= 512 and 5841 // s1 >= 64                    # B = 1: at least two blocks per compute unit, slabs of >= 64 points
@@ -50,7 +40,6 @@ def test_workspace_size_and_slab_rule():
     assert large - small == 2 * 4 * 777 * 8                      # one 64-bit key per (image, slab, point)
     assert L.pvm_workspace_bytes(2, 777, 10 ** 6) == L.pvm_workspace_bytes(2, 777, 777)
     # bad arguments are refused before anything is launched (no GPU is needed to be told so)
-    L.pvm_pose_metrics_batched.argtypes = [ctypes.c_void_p] * 8 + [ctypes.c_int] * 4 + [ctypes.c_void_p]
     assert L.pvm_pose_metrics_batched(None, None, None, None, None, None, None, None, 0, 5, 0, 0, None) == 0
     assert L.pvm_pose_metrics_batched(None, None, None, None, None, None, None, None, 2, 5, 0, 0, None) == -1
     assert L.pvm_pose_metrics_batched(None, None, None, None, None, None, None, None, -1, 5, 0, 0, None) == -1

@@ -3,19 +3,17 @@ twin of the contracts (tests/model_twin.py) reproduces the reference's own resul
 evaluation of the same rule and scipy's ``cdist``; the entry points exist under ABI 8 in the seven libraries, check their
 arguments before any launch and answer the workspace queries on the host; the wrapper refuses CPU tensors and validates
 ``sn``, ``n`` and ``start`` on the host.  The GPU tests (tests/test_gpu_model.py) then hold the device to the twin as bytes."""
-import ctypes
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import capi
 from tests import model_twin as twin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-VOTELIB = os.path.join(ROOT, "clean-pvnet_amd", "libpvnet_vote.so")
 HEADER = os.path.join(ROOT, "include", "pvnet_vote.h")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 REFERENCE_FPS = "/root/reference/lib/csrc/fps/fps_utils.py"
@@ -95,10 +93,8 @@ def test_case_table_holds_what_the_gpu_tests_need():
 
 # ------------------------------------------------------------------------------------------------ 2. the library
 def test_header_declares_and_library_exports_the_entry_points():
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    assert SYMBOLS <= set(re.findall(r"\b(pvv_[a-z0-9_]+)\s*\(", txt))
-    nm = subprocess.check_output(["nm", "-D", "--defined-only", VOTELIB]).decode()
-    assert SYMBOLS <= {l.split()[-1] for l in nm.splitlines() if " T " in l}
+    assert SYMBOLS <= capi.declared()
+    assert SYMBOLS <= capi.exported()
     raw = open(HEADER).read()
     assert "#define PVV_ABI_VERSION 8" in raw                                       # additive: the version did not move
     for cite in ("farthest_point_sampling.cpp", "misc.py:139-154", "handle_custom_dataset.py:19-40"):
@@ -114,20 +110,8 @@ def test_no_eighth_library():
     assert os.path.exists(os.path.join(b.CSRC, "model.hpp")) and not os.path.exists(os.path.join(b.CSRC, "pvnet_model.hip"))
 
 
-def _lib():
-    L = ctypes.CDLL(VOTELIB)
-    L.pvv_last_error.restype = ctypes.c_char_p
-    P, I, S = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
-    L.pvv_fps_workspace_bytes.restype, L.pvv_fps_workspace_bytes.argtypes = S, [I] * 4
-    L.pvv_model_workspace_bytes.restype, L.pvv_model_workspace_bytes.argtypes = S, [I] * 2
-    L.pvv_fps.argtypes = [P, P, P, I, I, I, I, P, S, P, P]
-    L.pvv_model_bounds.argtypes = [P, I, P, I, I, P, S, P, P, P]
-    L.pvv_model_diameter.argtypes = [P, I, P, I, I, P, S, P, P]
-    return L
-
-
 def test_workspace_queries_are_host_only_values():
-    L = _lib()
+    L = capi.load()
     AUTO, ONE, TILED = 0, 1, 2
     assert L.pvv_abi_version() == 8
     assert L.pvv_fps_workspace_bytes(8, 5841, 8, AUTO) == 256 == L.pvv_fps_workspace_bytes(8, 8192, 8, ONE)
@@ -145,7 +129,7 @@ def test_workspace_queries_are_host_only_values():
 
 
 def test_null_pointers_and_bad_sizes_return_minus_one_before_any_launch():
-    L = _lib()
+    L = capi.load()
     x = 256                                                                         # a pointer that is not NULL: never dereferenced
     fps = lambda pts, ws, idx, B=1, N=10, sn=2, path=0, nbytes=1 << 20: L.pvv_fps(pts, None, None, B, N, sn, path, ws, nbytes, idx, None)  # noqa: E731
     assert fps(None, x, x) == -1 and b"NULL device pointer" in L.pvv_last_error()

@@ -2,13 +2,13 @@
 the library's exported symbols; GPU: the HIP kernel against the oracle, bit-exact indices (first minimum wins)."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 
+from tests import capi
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NNLIB = os.path.join(ROOT, "clean-pvnet_amd", "libpvnet_nn.so")
 
 
 def _np_nearest(ref, que, exclude_self=False):
@@ -42,11 +42,9 @@ def test_oracle_matches_numpy_brute_force(oracle, dim, pn1, pn2):
 
 
 def test_nn_library_exports_what_the_header_declares():
-    txt = open(os.path.join(ROOT, "include", "pvnet_nn.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    names = set(re.findall(r"\b(findNearestPointIdxLauncher|pvv_nn_[a-z_]+)\s*\(", txt))
+    names = capi.declared("nn")
     assert names == {"findNearestPointIdxLauncher", "pvv_nn_find_nearest"}
-    L = ctypes.CDLL(NNLIB)
+    L = capi.load("nn")
     for n in names:
         assert hasattr(L, n)
     # the reference's cffi declares exactly this prototype (lib/csrc/nn/src/ext.h)
@@ -77,8 +75,7 @@ def test_hip_nearest_neighbour_bit_exact(oracle, pkg, gpu, dim, pn1, pn2):
 @pytest.mark.gpu
 def test_hip_nearest_neighbour_device_pointers_batched_exclude_self(oracle, pkg, gpu):
     import torch
-    L = ctypes.CDLL(NNLIB)
-    L.pvv_nn_find_nearest.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_void_p]
+    L = capi.load("nn")
     b, pn, dim = 3, 777, 3
     rng = np.random.RandomState(4)
     pts = rng.randn(b, pn, dim).astype(np.float32)
@@ -104,10 +101,8 @@ def test_reference_nn_kernel_pins_oracle_and_product(oracle, pkg, gpu, dim, b, p
     path = os.path.join(ROOT, "oracle", "_ref", "libref_nn.so")
     if not os.path.exists(path):
         pytest.skip("oracle/_ref/libref_nn.so is built only where /root/reference is mounted (see tests/test_host.py)")
-    R, P = ctypes.CDLL(path), ctypes.CDLL(NNLIB)
-    args = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5
-    R.ref_findNearestPointIdxLauncher.argtypes = args
-    P.findNearestPointIdxLauncher.argtypes = args
+    R, P = ctypes.CDLL(path), capi.load("nn")
+    R.ref_findNearestPointIdxLauncher.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5
     rng = np.random.RandomState(9)
     ref = (rng.randn(b, pn1, dim) * 0.05).astype(np.float32)
     if excl:

@@ -11,16 +11,14 @@ Measured (largest over the runs): Adam D 2.80, twin 3.58 from the float32 and 3.
 1.38; RAdam twin 1.68 from its float32 run.  States at the last step in 2^-24 * 12 * max |state| per tensor: Adam m D 0.22, twin
 0.27; v D 0.49, twin 0.40; SGD m D 0.49, twin 0.49; RAdam m 0.24, v 0.16."""
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import capi
 from tests import optim_twin as twin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-VOTELIB = os.path.join(ROOT, "clean-pvnet_amd", "libpvnet_vote.so")
 HEADER = os.path.join(ROOT, "include", "pvnet_vote.h")
 SYMBOLS = {"pvv_optim_step", "pvv_optim_chunk"}
 TITLE = "Optimizer step: the clipped Adam / RAdam / SGD step of every parameter tensor in one launch"
@@ -240,8 +238,7 @@ def test_make_optimizer_groups_as_the_reference_does(optim):
 
 def test_header_declares_and_library_exports_the_entry_points(optim):
     raw = open(HEADER).read()
-    txt = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    assert SYMBOLS <= set(re.findall(r"\b(pvv_[a-z0-9_]+)\s*\(", txt))
+    assert SYMBOLS <= capi.declared()
     assert TITLE in raw and "#define PVV_ABI_VERSION 8" in raw                               # additive: the version did not move
     section = raw[raw.index(TITLE):raw.index("Model metadata (ABI v8")]
     for cite in ("lib/train/trainers/trainer.py:42-45", "lib/train/optimizer.py:12-27", "lib/utils/optimizer/radam.py:29-95"):
@@ -253,8 +250,7 @@ def test_header_declares_and_library_exports_the_entry_points(optim):
         assert "#define PVV_OPTIM_%s %d\n" % (name, value) in section
     assert (optim.ROW_ADAPTIVE, optim.ROW_DECAY, optim.ROW_NO_UPDATE, optim.ROW_FIRST) == \
         (twin.ROW_ADAPTIVE, twin.ROW_DECAY, twin.ROW_NO_UPDATE, twin.ROW_FIRST)
-    nm = subprocess.check_output(["nm", "-D", "--defined-only", VOTELIB]).decode()
-    assert SYMBOLS <= {l.split()[-1] for l in nm.splitlines() if " T " in l}
+    assert SYMBOLS <= capi.exported()
     assert optim._lib.pvv_optim_chunk() == optim.CHUNK
     import lib
     assert len(lib.load_build().HIP_LIBS) == 7                                              # part of libpvnet_vote.so: no new library

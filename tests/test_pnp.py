@@ -8,14 +8,13 @@ GPU: the HIP kernel (batched device entry, the reference's host symbol, the drop
 Parity is defined on the MINIMUM (cost within 1e-9 relative, pose within 1e-6 of the independent minimiser); with the
 default (Ceres) stopping rule the kernel equals its numpy twin iterate for iterate.  Ceres' own iterate path is unpinned.
 """
-import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 
 from oracle import pnp_oracle as po
+from tests import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KMAT = np.array([[572.4114, 0, 325.2611], [0, 573.57043, 242.04899], [0, 0, 1.0]])      # LINEMOD camera
@@ -77,14 +76,12 @@ def test_jacobian_matches_finite_differences():
 
 
 def test_cabi_library_loads_and_exports_the_declared_symbols():
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pvnet_pnp.h")).read(), flags=re.S)
-    names = set(re.findall(r"\b([a-z_0-9]+)\s*\(", txt)) - {"defined"}
+    names = capi.declared("pnp")
     assert names == {"uncertainty_pnp", "pvp_uncertainty_pnp_batched"}
-    L = ctypes.CDLL(os.path.join(ROOT, "clean-pvnet_amd", "libpvnet_pnp.so"))
+    L = capi.load("pnp")
     for n in names:
         assert hasattr(L, n)
     # bad arguments are refused before any launch (no GPU needed)
-    L.pvp_uncertainty_pnp_batched.argtypes = [ctypes.c_void_p] * 7 + [ctypes.c_int] * 5 + [ctypes.c_double, ctypes.c_void_p]
     assert L.pvp_uncertainty_pnp_batched(None, None, None, None, None, None, None, 1, 9, 0, 0, 0, 0.0, None) == -1
 
 

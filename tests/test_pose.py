@@ -13,36 +13,21 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+from tests import capi
 from tests.test_pnp import need_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = os.path.join(ROOT, "include", "pvnet_pose.h")
-SO = os.path.join(ROOT, "clean-pvnet_amd", "libpvnet_pose.so")
-
 _P = ctypes.c_void_p
-_INIT_ARGS = [_P] * 4 + [ctypes.c_int] + [_P] * 2 + [ctypes.c_int] * 4 + [_P]
-_POSE_ARGS = [_P] * 4 + [ctypes.c_int] + [_P] * 5 + [ctypes.c_int] * 5 + [ctypes.c_double, _P]
-
-
-def _lib():
-    L = ctypes.CDLL(SO)
-    L.pvp_initial_pose_batched.argtypes = _INIT_ARGS
-    L.pvp_pose_batched.argtypes = _POSE_ARGS
-    return L
 
 
 def test_header_names_equal_the_library_exports():
-    txt = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    names = set(re.findall(r"\b([a-z_0-9]+)\s*\(", txt)) - {"defined"}
+    names = capi.declared("pose")
     assert names == {"pvp_initial_pose_batched", "pvp_pose_batched"}
-    L = ctypes.CDLL(SO)
+    L = capi.load("pose")
     for n in names:
         assert hasattr(L, n)
-    import subprocess
-    nm = subprocess.run(["nm", "-D", "--defined-only", SO], capture_output=True, text=True)
-    if nm.returncode == 0:                                  # every exported pvp_ symbol is declared
-        exported = {ln.split()[-1] for ln in nm.stdout.splitlines() if ln.split() and ln.split()[-1].startswith("pvp_")}
-        assert exported == names
+    assert {e for e in capi.exported("pose") if e.startswith("pvp_")} == names      # every exported pvp_ symbol is declared
 
 
 def test_status_and_method_codes_match_the_header(pkg):
@@ -54,7 +39,7 @@ def test_status_and_method_codes_match_the_header(pkg):
 
 
 def test_bad_arguments_are_refused_before_any_launch():
-    L = _lib()
+    L = capi.load("pose")
     buf = (ctypes.c_double * 64)()
     ibuf = (ctypes.c_int * 4)()
     d, i = ctypes.cast(buf, _P), ctypes.cast(ibuf, _P)

@@ -6,16 +6,15 @@ The GPU tests (tests/test_gpu_render.py) then hold the device to the twin byte f
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import capi
 from tests import render_twin as twin
 from tests import vsd_twin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-VOTELIB = os.path.join(ROOT, "clean-pvnet_amd", "libpvnet_vote.so")
 HEADER = os.path.join(ROOT, "include", "pvnet_vote.h")
 SYMBOLS = {"pvv_render_workspace_bytes", "pvv_render_color"}
 TITLE = "Colour renders"
@@ -38,10 +37,8 @@ def test_module_imports(pkg):
 
 def test_header_declares_and_library_exports_the_entry_points():
     raw = open(HEADER).read()
-    txt = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    assert SYMBOLS <= set(re.findall(r"\b(pvv_[a-z0-9_]+)\s*\(", txt))
-    nm = subprocess.check_output(["nm", "-D", "--defined-only", VOTELIB]).decode()
-    assert SYMBOLS <= {l.split()[-1] for l in nm.splitlines() if " T " in l}
+    assert SYMBOLS <= capi.declared()
+    assert SYMBOLS <= capi.exported()
     assert "#define PVV_ABI_VERSION 8" in raw                                      # additive: the version did not move
     # the newest section: behind every section but the two whose place at the end other tests pin
     assert raw.index("Detector augmentation") < raw.index(TITLE) < raw.index("Detector training")
@@ -57,17 +54,8 @@ def test_header_declares_and_library_exports_the_entry_points():
     assert len(table) == 7 and list(table)[-1] == "icp"
 
 
-def _lib():
-    L = ctypes.CDLL(VOTELIB)
-    L.pvv_last_error.restype = ctypes.c_char_p
-    P, I, D, S = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_size_t
-    L.pvv_render_workspace_bytes.restype, L.pvv_render_workspace_bytes.argtypes = S, [I] * 5
-    L.pvv_render_color.argtypes = [P] * 3 + [I, I, P] + [I] * 3 + [P] * 3 + [I, P, P] + [I] * 4 + [D] * 3 + [P, S] + [P] * 6
-    return L
-
-
 def test_workspace_sizes_are_the_stated_values():
-    L = _lib()
+    L = capi.load()
     assert L.pvv_abi_version() == 8
     up = lambda v: (v + 255) // 256 * 256                                          # noqa: E731
     assert L.pvv_render_workspace_bytes(2, 3, 301, 45, 70) == up(32 * 2 * 3 * 301) + up(8 * 2 * 45 * 70)
@@ -80,7 +68,7 @@ def test_workspace_sizes_are_the_stated_values():
 
 
 def test_bad_arguments_return_minus_one_before_any_launch():
-    L = _lib()
+    L = capi.load()
     x = 256                                                                         # a pointer that is not NULL: never dereferenced
     bgc = (ctypes.c_uint8 * 3)(0, 0, 0)
 

@@ -6,19 +6,16 @@ canvases, the final image, the mask, the branch, ``visible``, ``pixel_num``, the
 warped image and the warped mask; within derived bounds in ``trans_input``, the keypoints and the float image.  The GPU tests
 (tests/test_gpu_tless_augment.py) then hold the device to the twin byte for byte."""
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from tests import crop_twin
+from tests import capi, crop_twin
 from tests import ct_augment_twin as ct
 from tests import tless_augment_twin as twin
 from tests.test_ct_augment import inp_bound
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-VOTELIB = os.path.join(ROOT, "clean-pvnet_amd", "libpvnet_vote.so")
 HEADER = os.path.join(ROOT, "include", "pvnet_vote.h")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 FIXTURES = ("tless_augment_mixed_30x50", "tless_augment_random_30x50")
@@ -59,10 +56,8 @@ def test_module_imports(pkg):
 
 def test_header_declares_and_library_exports_the_entry_points():
     raw = open(HEADER).read()
-    txt = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    assert SYMBOLS <= set(re.findall(r"\b(pvv_[a-z0-9_]+)\s*\(", txt))
-    nm = subprocess.check_output(["nm", "-D", "--defined-only", VOTELIB]).decode()
-    assert SYMBOLS <= {l.split()[-1] for l in nm.splitlines() if " T " in l}
+    assert SYMBOLS <= capi.declared()
+    assert SYMBOLS <= capi.exported()
     assert "#define PVV_ABI_VERSION 8" in raw                                      # additive: the version did not move
     title = "T-LESS PVNet augmentation"
     assert title in raw and "#define PVV_TLESS_CUT_BYTES 112" in raw and "#define PVV_TLESS_MAX_N 16" in raw

@@ -4,18 +4,15 @@ on the CPU (tests/golden/train_*.npz, made by tests/golden/make_train_golden.py)
 losses and the seg gradient within the bounds derived in the twin; its sums do not depend on the order tiles are evaluated in;
 the header, the symbols, the host-side refusals and the wrapper's checks are there.  The GPU tests (tests/test_gpu_train.py)
 then hold the device to the twin."""
-import ctypes
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import capi
 from tests import train_twin as twin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-VOTELIB = os.path.join(ROOT, "clean-pvnet_amd", "libpvnet_vote.so")
 HEADER = os.path.join(ROOT, "include", "pvnet_vote.h")
 SYMBOLS = {"pvv_vertex_target", "pvv_pvnet_loss_workspace_bytes", "pvv_pvnet_loss_forward", "pvv_pvnet_loss_backward"}
 
@@ -138,17 +135,14 @@ def test_block_sum_order():
 # ------------------------------------------------------------------------------------------------ 3. the header and the symbols
 def test_header_declares_and_library_exports_the_entry_points(pkg):
     raw = open(HEADER).read()
-    txt = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = re.findall(r"\b(pvv_[a-z0-9_]+)\s*\(", txt)
+    declared = list(capi.native.declarations("pvnet_vote.h"))                       # in the header's order
     assert SYMBOLS <= set(declared) and set(declared[-4:]) == SYMBOLS               # the last section of the header
     assert "Training: vote targets and the PVNet loss" in raw
     section = raw[raw.index("Training: vote targets and the PVNet loss"):]
     for cite in ("pvnet_data_utils.py:30-44", "lib/train/trainers/pvnet.py:25-34", "resnet18.py:93-94"):
         assert cite in section
-    nm = subprocess.check_output(["nm", "-D", "--defined-only", VOTELIB]).decode()
-    exported = {l.split()[-1] for l in nm.splitlines() if " T " in l}
-    assert SYMBOLS <= exported
-    assert "#define PVV_ABI_VERSION 8" in raw                                       # additive: the version did not move
+    assert SYMBOLS <= capi.exported()
+    assert "#define PVV_ABI_VERSION 8" in raw                                      # additive: the version did not move
     import lib
     table = lib.load_build().HIP_LIBS
     assert len(table) == 7 and list(table)[-1] == "icp"
@@ -163,18 +157,6 @@ def test_module_imports(pkg):
 
 
 # ------------------------------------------------------------------------------------------------ 4. the host-only checks
-def _lib():
-    L = ctypes.CDLL(VOTELIB)
-    L.pvv_last_error.restype = ctypes.c_char_p
-    P, I, LL, S = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_size_t
-    inputs = [P, LL, P, LL, P, I, P, I, P, LL] + [I] * 5
-    L.pvv_pvnet_loss_workspace_bytes.restype, L.pvv_pvnet_loss_workspace_bytes.argtypes = S, [I] * 3
-    L.pvv_pvnet_loss_forward.argtypes = inputs + [P, S, P, P, P]
-    L.pvv_pvnet_loss_backward.argtypes = inputs + [P, P, P, P, P]
-    L.pvv_vertex_target.argtypes = [P, I, P, I, I, I, I, I, P, P]
-    return L
-
-
 def _workspace(B, H, W):
     """What the layout of the header gives: per (image, tile) two binary64 and two int64, the same per image, each of the four
     parts rounded up to 256 bytes."""
@@ -185,13 +167,13 @@ def _workspace(B, H, W):
 
 @pytest.mark.parametrize("B,H,W", [(1, 37, 53), (1, 480, 640), (64, 480, 640)])
 def test_workspace_sizes(B, H, W):
-    got = _lib().pvv_pvnet_loss_workspace_bytes(B, H, W)
+    got = capi.load().pvv_pvnet_loss_workspace_bytes(B, H, W)
     assert got == _workspace(B, H, W) and got % 256 == 0
     assert got < 1 << 20                                                            # partials, not fields
 
 
 def test_host_side_refusals():
-    L = _lib()
+    L = capi.load()
     x = 256                                                                         # a pointer that is not NULL: never dereferenced
 
     def fwd(B=1, K=9, C=2, H=8, W=8, kpt=x, target=None, vp=x, strides=None, kind=0, ws=x, nbytes=1 << 20):

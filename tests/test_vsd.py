@@ -2,17 +2,15 @@
 rasteriser's contract against an independent ray caster, the twin's VSD arithmetic against fixtures made by the reference's
 own functions (tests/golden/make_vsd_golden.py), the library's exports and its host-side argument checks.  The GPU tests
 (tests/test_gpu_vsd.py) then hold the device to the twin bit for bit."""
-import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 
+from tests import capi
 from tests import vsd_twin as twin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-VSDLIB = os.path.join(ROOT, "clean-pvnet_amd", "libpvnet_vsd.so")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 FIXTURES = ("vsd_720", "vsd_360", "vsd_near")
 RULES = "vsd_rules"                                  # constructed images, stored whole (make_vsd_golden.py::make_rules)
@@ -330,34 +328,24 @@ def test_twin_vsd_reproduces_the_rules_fixture():
 
 # ------------------------------------------------------------------------------------------- 4. the library and its arguments
 def test_vsd_library_exports_what_the_header_declares():
-    txt = open(os.path.join(ROOT, "include", "pvnet_vsd.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    names = set(re.findall(r"\b(pvs_[a-z_]+)\s*\(", txt))
+    names = capi.declared("vsd")
     assert names == {"pvs_render_workspace_bytes", "pvs_render_depth_batched", "pvs_vsd_workspace_bytes", "pvs_vsd_batched"}
-    L = ctypes.CDLL(VSDLIB)
+    L = capi.load("vsd")
     for n in names:
         assert hasattr(L, n)
-    import shutil
-    import subprocess
-    nm = shutil.which("nm") or shutil.which("llvm-nm", path=os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin"))
-    if nm:                                                       # and nothing else is exported
-        out = subprocess.run([nm, "-D", "--defined-only", VSDLIB], capture_output=True, text=True, check=True).stdout
-        exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
-        assert {e for e in exported if not e.startswith("_")} == names, exported
+    exported = capi.exported("vsd")                              # and nothing else is exported
+    assert {e for e in exported if not e.startswith("_")} == names, exported
 
 
 def test_workspace_sizes_and_argument_errors():
     """Bad arguments are refused before anything is launched (no GPU is needed to be told so)."""
-    L = ctypes.CDLL(VSDLIB)
-    L.pvs_render_workspace_bytes.restype = ctypes.c_size_t
-    L.pvs_vsd_workspace_bytes.restype = ctypes.c_size_t
+    L = capi.load("vsd")
     assert L.pvs_render_workspace_bytes(0, 100) == 0 and L.pvs_render_workspace_bytes(3, 0) == 0
     assert L.pvs_render_workspace_bytes(3, 100) == 3 * 100 * 32          # three binary64 and two int32 per (pose, vertex)
     assert L.pvs_vsd_workspace_bytes(2, 2, 2, 540, 720, 0) == 0          # 'step': integers only
     assert L.pvs_vsd_workspace_bytes(2, 2, 2, 540, 720, 1) == 8 * 8 * -(-540 * 720 // 256)
     assert L.pvs_vsd_workspace_bytes(0, 2, 2, 540, 720, 1) == 0
     render = L.pvs_render_depth_batched
-    render.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_int] * 6 + [ctypes.c_double] * 2 + [ctypes.c_void_p]
     assert render(None, None, None, None, None, None, 0, 5, 4, 0, 64, 48, 100.0, 1e4, None) == 0      # no pose: nothing to do
     assert render(None, None, None, None, None, None, 2, 5, 4, 0, 64, 48, 100.0, 1e4, None) == -1     # null pointers
     assert render(None, None, None, None, None, None, -1, 5, 4, 0, 64, 48, 100.0, 1e4, None) == -1
@@ -367,9 +355,6 @@ def test_workspace_sizes_and_argument_errors():
     assert render(None, None, None, None, None, None, 0, 5, 4, 0, 64, 48, 100.0, 50.0, None) == -1    # far < near
     assert render(None, None, None, None, None, None, 0, 5, 4, 0, 64, 48, float("nan"), 1e4, None) == -1
     vsd = L.pvs_vsd_batched
-    vsd.argtypes = ([ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_int, ctypes.c_double,
-                                             ctypes.c_double, ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 +
-                    [ctypes.c_void_p])
     args = lambda n, kind=0, cost=0, H=48, W=64: (None, None, None, kind, 0.1, None, 0, 15.0, 20.0, cost, None, None, None,   # noqa: E731
                                                   n, 2, 2, H, W, None)
     assert vsd(*args(0)) == 0

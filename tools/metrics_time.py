@@ -15,7 +15,6 @@ k_adds_search + k_adds_merge kernel against kernel.  The model is a seeded synth
     python tools/metrics_time.py [--batches 1,64] [--points 5841] [--rounds 20] [--warmup 5] [--only device|host|nn] [--slabs 0]
 """
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -30,7 +29,7 @@ import lib  # noqa: E402
 
 lib._register_clean_pvnet_amd()
 from _timing import alternate, summary  # noqa: E402
-from clean_pvnet_amd import metrics  # noqa: E402
+from clean_pvnet_amd import _native, metrics  # noqa: E402
 from lib.csrc.nn.nn_utils import find_nearest_point_idx  # noqa: E402
 
 KMAT = np.array([[572.4114, 0, 325.2611], [0, 573.57043, 242.04899], [0, 0, 1.0]])
@@ -93,8 +92,7 @@ def main():
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     N = a.points
-    nn = ctypes.CDLL(os.path.join(ROOT, "clean-pvnet_amd", "libpvnet_nn.so"))
-    nn.pvv_nn_find_nearest.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 5 + [ctypes.c_void_p]
+    nn = _native.load("metrics_time", "libpvnet_nn.so")
     for B in [int(s) for s in a.batches.split(",")]:
         Pp, Pg, md, Kt, model = inputs(B, N, dev)
         m64 = md.double()

@@ -26,17 +26,7 @@ def _synth():
 
 
 def _load(path):
-    L = ctypes.CDLL(os.path.abspath(path))
-    L.pvv_last_error.restype = ctypes.c_char_p
-    L.pvv_workspace_bytes.restype = ctypes.c_size_t
-    L.pvv_workspace_bytes.argtypes = [ctypes.POINTER(capi.Problem)]
-    L.pvv_default_cap.restype = ctypes.c_int32
-    L.pvv_default_cap.argtypes = [ctypes.c_int32] * 3
-    vp = ctypes.c_void_p
-    L.pvv_ransac_voting_v3.argtypes = [ctypes.POINTER(capi.Problem), vp, vp, vp, vp, vp, ctypes.c_size_t, vp, vp, vp, vp]
-    L.pvv_rerun_count_kernel.argtypes = [ctypes.POINTER(capi.Problem), vp, ctypes.c_size_t, ctypes.c_int, vp]
-    L.pvv_decode_keypoint_v3.argtypes = [ctypes.POINTER(capi.Problem), vp, vp, vp, vp, vp, ctypes.c_size_t, vp, vp, vp, vp, vp]
-    return L
+    return capi.native.declare(ctypes.CDLL(os.path.abspath(path)), "pvnet_vote.h")
 
 
 def main():
