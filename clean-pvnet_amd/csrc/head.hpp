@@ -326,6 +326,10 @@ int head_launch(const HeadShape &s, const float *fm, const float *x, const float
     return check_launch("k_head_forward");
 }
 
+// The bfloat16 matrix-core mode of the same function (head_bf16.hpp, included after this file).
+int head_bf16_forward(const HeadShape &s, const float *fm, const float *x, const float *weight1, const float *scale, const float *shift,
+                      const float *weight2, const float *bias2, void *out, hipStream_t st);
+
 }  // namespace
 
 PVV_EXPORT int pvv_head_forward(const float *d_fm, long long fm_image_stride, const float *d_x, long long x_image_stride,
@@ -334,10 +338,13 @@ PVV_EXPORT int pvv_head_forward(const float *d_fm, long long fm_image_stride, co
                                 float negative_slope, int out_kind, void *d_out, void *stream)
 {
     HeadShape s;
+    const bool bf16 = (out_kind & ~0xFF) == PVV_HEAD_COMPUTE_BF16;    // any other bit above the dtype code stays and is refused with it
+    if (bf16) out_kind &= 0xFF;
     if (int e = head_shape(s, B, C2, C0, h, w, H, W, M1, M2, fm_image_stride, x_image_stride, negative_slope, out_kind)) return e;
     if (!d_fm || (C0 > 0 && !d_x) || !d_weight1 || !d_scale || !d_shift || !d_weight2 || !d_bias2 || !d_out)
         return fail(PVV_E_ARG, "head: NULL device pointer");
     hipStream_t st = (hipStream_t)stream;
+    if (bf16) return head_bf16_forward(s, d_fm, d_x, d_weight1, d_scale, d_shift, d_weight2, d_bias2, d_out, st);
     if (M1 > 32)
         return M2 > 32 ? head_launch<2, 2>(s, d_fm, d_x, d_weight1, d_scale, d_shift, d_weight2, d_bias2, d_out, st)
                        : head_launch<2, 1>(s, d_fm, d_x, d_weight1, d_scale, d_shift, d_weight2, d_bias2, d_out, st);

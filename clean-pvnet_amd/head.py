@@ -5,7 +5,9 @@ image and ``convraw``: Conv3x3 without bias, BatchNorm2d, LeakyReLU(0.1), Conv1x
 resolution.  ``pvnet_head`` is one launch that reads ``fm`` and the image and writes the ``seg_dim + ver_dim`` output channels,
 with no full-resolution intermediate in memory; ``PVNetHead`` holds ``convraw`` under the reference's parameter names, so the
 ``convraw.*`` entries of a reference checkpoint load unchanged.  The result equals the numpy twin (tests/head_twin.py) bit for bit
-(-0 == +0); parity with torch's own upsample kernel and with MIOpen's convolution is unpinned.  Forward
+(-0 == +0); parity with torch's own upsample kernel and with MIOpen's convolution is unpinned.  ``compute="bfloat16"`` is the opt-in matrix-core mode
+(``PVV_HEAD_COMPUTE_BF16`` in ``pvv_head_forward``'s ``out_kind``): operands rounded to bfloat16, float32 accumulation in an unpinned order, held to the bound of
+tests/head_bf16_twin.py.  Forward
 only, BatchNorm in eval mode: inference.  CUDA float32 tensors, the current stream, nothing read back, no CPU fallback.
 """
 import torch
@@ -18,6 +20,7 @@ _lib = _native.bind("head", "libpvnet_vote.so", last_error="pvv_last_error")
 MAX_UPSAMPLE = 1 << 28             # elements ``upsample2x`` agrees to write
 MAX_M = 64                         # output channels of either convolution
 OUT_KINDS = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+COMPUTE_MODES = {"float32": 0, "bfloat16": 0x100}                   # or-ed into out_kind; 0x100: PVV_HEAD_COMPUTE_BF16
 
 
 def _check(named):
@@ -25,6 +28,12 @@ def _check(named):
     if torch.is_grad_enabled() and any(t.requires_grad for _, t in named):
         raise RuntimeError("clean_pvnet_amd.head: forward only -- there is no backward pass; call under torch.no_grad() "
                            "or with tensors that do not require grad")
+
+
+def _compute(compute):
+    if not isinstance(compute, str) or compute not in COMPUTE_MODES:
+        raise ValueError("clean_pvnet_amd.head: compute must be one of %s, got %r" % (", ".join(map(repr, COMPUTE_MODES)), compute))
+    return COMPUTE_MODES[compute]
 
 
 def _fm(fm):
@@ -35,7 +44,8 @@ def _fm(fm):
     return (B, C2, h, w), t, stride
 
 
-def pvnet_head(fm, x, weight1, scale, shift, weight2, bias2, *, negative_slope=0.1, out_dtype=torch.float32):
+def pvnet_head(fm, x, weight1, scale, shift, weight2, bias2, *, negative_slope=0.1, out_dtype=torch.float32,
+               compute="float32"):
     """``convraw(cat([up2storaw(fm), x], 1))`` with the BatchNorm folded into ``scale`` and ``shift`` (``fold_bn``).
     :param fm:       [B,C2,h,w] float32 CUDA tensor, the half-resolution feature map
     :param x:        [B,C0,2h,2w], the image; C0 may be 0
@@ -44,7 +54,11 @@ def pvnet_head(fm, x, weight1, scale, shift, weight2, bias2, *, negative_slope=0
     :return:         [B,M2,2h,2w] of ``out_dtype``: float32, or float16 / bfloat16 rounded to nearest even at the store
     ``fm`` and ``x`` may be views (channel slices of larger tensors): they are read by their image strides.  The contract is in
     include/pvnet_vote.h: torch's float32 align_corners source index and blend, zero padding ring, one ``fmaf`` chain per output
-    over k = channel*9 + tap from +0, ``fmaf(acc, scale, shift)``, the leaky slope, one ``fmaf`` chain over M1 from the bias."""
+    over k = channel*9 + tap from +0, ``fmaf(acc, scale, shift)``, the leaky slope, one ``fmaf`` chain over M1 from the bias.
+    :param compute:  ``"float32"`` (that contract, that kernel), or ``"bfloat16"``, the matrix-core mode of
+                     ``PVV_HEAD_COMPUTE_BF16``: every operand of the two convolutions is rounded once to bfloat16 and the
+                     products are accumulated in float32 in an order that is not pinned: tests/head_bf16_twin.py bounds it."""
+    mode = _compute(compute)
     named = [("fm", fm), ("x", x), ("weight1", weight1), ("scale", scale), ("shift", shift), ("weight2", weight2), ("bias2", bias2)]
     _check(named)
     if out_dtype not in OUT_KINDS:
@@ -71,7 +85,7 @@ def pvnet_head(fm, x, weight1, scale, shift, weight2, bias2, *, negative_slope=0
     w1, sc, sh, w2, b2 = (t.detach().contiguous() for t in (weight1, scale, shift, weight2, bias2))
     _lib.call("pvv_head_forward", fm.device, f.data_ptr(), f_stride, xi.data_ptr() if C0 else None, x_stride, w1.data_ptr(),
               sc.data_ptr(), sh.data_ptr(), w2.data_ptr(), b2.data_ptr(), B, C2, C0, h, w, H, W, M1, M2, float(negative_slope),
-              OUT_KINDS[out_dtype], out.data_ptr())
+              OUT_KINDS[out_dtype] | mode, out.data_ptr())
     return out
 
 
@@ -107,11 +121,13 @@ def fold_bn(bn):
 
 class PVNetHead(nn.Module):
     """``up2storaw`` and ``convraw`` of the reference's ``Resnet18`` (resnet18.py:53-59) as one module: ``self.convraw`` has the
-    reference's layers and names, ``forward(fm, x)`` is resnet18.py:90-96 up to the dict, through ``pvnet_head``."""
+    reference's layers and names, ``forward(fm, x)`` is resnet18.py:90-96 up to the dict, through ``pvnet_head``.  ``compute`` is
+    ``pvnet_head``'s mode, an attribute that may be set between calls; the parameters stay float32 in every mode."""
 
-    def __init__(self, ver_dim, seg_dim, s2dim=32, raw_dim=32, image_dim=3):
+    def __init__(self, ver_dim, seg_dim, s2dim=32, raw_dim=32, image_dim=3, compute="float32"):
         super().__init__()
-        self.ver_dim, self.seg_dim = ver_dim, seg_dim
+        _compute(compute)
+        self.ver_dim, self.seg_dim, self.compute = ver_dim, seg_dim, compute
         self.convraw = nn.Sequential(
             nn.Conv2d(image_dim + s2dim, raw_dim, 3, 1, 1, bias=False),
             nn.BatchNorm2d(raw_dim),
@@ -121,11 +137,12 @@ class PVNetHead(nn.Module):
         self._folded = None
 
     @classmethod
-    def from_state_dict(cls, sd, seg_dim=2, prefix="convraw.", image_dim=3):
+    def from_state_dict(cls, sd, seg_dim=2, prefix="convraw.", image_dim=3, compute="float32"):
         """A head sized from the ``<prefix>*`` tensors of a state dict (a whole ``Resnet18`` checkpoint will do), loaded with
         them, in eval mode.  ``seg_dim`` of the output channels are the segmentation's (2 in PVNet), the rest the vertex field's."""
         w1, w2 = sd[prefix + "0.weight"], sd[prefix + "3.weight"]
-        m = cls(int(w2.shape[0]) - seg_dim, seg_dim, s2dim=int(w1.shape[1]) - image_dim, raw_dim=int(w1.shape[0]), image_dim=image_dim)
+        m = cls(int(w2.shape[0]) - seg_dim, seg_dim, s2dim=int(w1.shape[1]) - image_dim, raw_dim=int(w1.shape[0]), image_dim=image_dim,
+                compute=compute)
         m.load_state_dict({"convraw." + k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)})
         return m.eval()
 
@@ -149,5 +166,6 @@ class PVNetHead(nn.Module):
         named = [("fm", fm), ("x", x), ("weight1", conv1.weight), ("weight2", conv2.weight), ("bias2", conv2.bias)]
         _check(named)
         scale, shift = self.folded()
-        out = pvnet_head(fm, x, conv1.weight, scale, shift, conv2.weight, conv2.bias, negative_slope=act.negative_slope)
+        out = pvnet_head(fm, x, conv1.weight, scale, shift, conv2.weight, conv2.bias, negative_slope=act.negative_slope,
+                         compute=self.compute)
         return {"seg": out[:, :self.seg_dim], "vertex": out[:, self.seg_dim:]}

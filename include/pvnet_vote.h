@@ -561,6 +561,30 @@ int pvv_head_forward(const float *d_fm, long long fm_image_stride, const float *
 int pvv_head_upsample(const float *d_fm, long long fm_image_stride, int B, int C2, int h, int w, int H, int W, float *d_u,
                       void *stream);
 
+/* The bfloat16 matrix-core compute mode of the same function (ABI v8, additive, opt-in): PVV_HEAD_COMPUTE_BF16 or-ed into
+ * pvv_head_forward's `out_kind`, whose low byte stays the output dtype code -- PVV_HEAD_OUT_BF16 | PVV_HEAD_COMPUTE_BF16 computes
+ * and stores in bfloat16.  No symbol is added and no signature changes; without the flag the call is what it was.  Any other bit
+ * above the low byte is refused together with an unknown dtype code.  Arguments, limits and refusals are otherwise the same.  One
+ * launch, no workspace, no atomics (reruns give the same bytes), nothing read back.  The operands are stated bit for bit:
+ *  1. u is the float32 upsample above, unchanged; z = cat([u, x]) inside its ring of zeros, fm's channels first.
+ *  2. Conv1's operands are z and weight1.  bf16(v) is float32 v rounded to nearest even to bfloat16 (a NaN keeps its upper bits
+ *     and gets the quiet bit); every operand v enters as bf16(v).
+ *  3. acc1 is a float32 sum, from +0, of the exact products (v_mfma_f32_32x32x16_bf16).  The ORDER of the sum is not part of
+ *     the contract, nor are zero terms added for channel padding.
+ *  4. t = fmaf(acc1, scale[o], shift[o]);  a = t > 0 ? t : t * negative_slope, float32 as above.
+ *  5. Conv2's operands are a and weight2, rounded as in 2; acc2 is a float32 sum, in any order, of bias2[o] (float32,
+ *     not rounded) and the products.
+ *  6. Store: float32, or rounded to nearest even to float16 / bfloat16.
+ * Because the order is free a result is held to a bound, not to bits: tests/head_bf16_twin.py evaluates 1-6 in binary64 on the
+ * bit-exact operands (step 4 rounded to float32) and gives bound_acc, the reach of any float32 summation order, and
+ * bound_mode, the distance from the float32 contract's function.  Where every partial sum is exact (the twin's exact-sum
+ * cases) the result is pinned bit for bit.  Non-finite values: a NaN operand gives NaN; the NaN outputs and the +-Inf outputs are
+ * the twin's.  -0 compares as +0.
+ * A split mode (hi = bf16(v), lo = bf16(v - hi), the products hi*hi + hi*lo + lo*hi: near float32) is stated by the twin as
+ * "bfloat16x3" but is NOT offered: built on this kernel it measured slower than the float32 launch; the
+ * flag 0x200 is kept free for it. */
+#define PVV_HEAD_COMPUTE_BF16 0x100
+
 /* ------------------------------------------------------------------------
  * Optimizer step: the clipped Adam / RAdam / SGD step of every parameter tensor in one launch (ABI v8, additive).  Citations:
  *   T = lib/train/trainers/trainer.py:42-45 (zero_grad, clip_grad_value_(..., 40), optimizer.step)
