@@ -3,6 +3,8 @@
 // Conv1x1 with its bias.  Included at the end of pvnet_vote.hip: built with -ffp-contract=off, so the upsample rounds once per
 // operation in the order written; the only fused multiply-adds are the ones the contract asks for, inside v_mfma_f32_32x32x2_f32
 // and the one fmaf of the BatchNorm.  The numpy twin (tests/head_twin.py) gives the same bits.
+// pvv_head_forward below also dispatches the two modes of its `out_kind`: the bfloat16 matrix-core mode (head_bf16.hpp) and the
+// stage mode, PVNet's decoder stages (head_stage.hpp); both branch off after the checks all three share.
 //
 // Reference behaviour restated: lib/networks/pvnet/resnet18.py:53-59, 90-94 of the reference.
 #pragma once
@@ -285,17 +287,21 @@ size_t head_lds_bytes(const HeadShape &s)
     return sizeof(float) * (region + 2 * (size_t)kHeadKs * 32 * N1 + (size_t)s.M1pad * (32 * N2 + 1));
 }
 
-// The checks the two entry points share; fills `s`.  M1 = M2 = 1 for the upsample alone.
+// The checks the two entry points share; fills `s`.  M1 = M2 = 1 for the upsample alone.  `stage`: the stage mode's limits --
+// M1 up to PVV_HEAD_STAGE_MAX_M, the output is [M1,H,W] (the caller passes M2 = 1) -- and with `same_res` H = h, W = w.
 int head_shape(HeadShape &s, int B, int C2, int C0, int h, int w, int H, int W, int M1, int M2, long long fm_stride, long long x_stride,
-               float slope, int out_kind)
+               float slope, int out_kind, bool stage = false, bool same_res = false)
 {
     if (B <= 0 || C2 <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0 || M1 <= 0 || M2 <= 0 || C0 < 0)
         return fail(PVV_E_ARG, "head: B, C2, h, w, H, W, M1, M2 must be positive and C0 not negative");
     if (B > 65535) return fail(PVV_E_ARG, "head: B > 65535: split the batch");
-    if (M1 > PVV_HEAD_MAX_M || M2 > PVV_HEAD_MAX_M) return fail(PVV_E_ARG, "head: M1 and M2 must be <= 64");
-    if (H != 2ll * h || W != 2ll * w) return fail(PVV_E_ARG, "head: H must be 2*h and W must be 2*w");
+    if (stage && M1 > PVV_HEAD_STAGE_MAX_M) return fail(PVV_E_ARG, "head: a stage's M1 must be <= 128");
+    if (!stage && (M1 > PVV_HEAD_MAX_M || M2 > PVV_HEAD_MAX_M)) return fail(PVV_E_ARG, "head: M1 and M2 must be <= 64");
+    if (same_res && (H != h || W != w)) return fail(PVV_E_ARG, "head: with PVV_HEAD_SAME_RES H must be h and W must be w");
+    if (!same_res && (H != 2ll * h || W != 2ll * w)) return fail(PVV_E_ARG, "head: H must be 2*h and W must be 2*w");
     const long long lim = 1ll << 31, P = (long long)H * W, C = (long long)C2 + C0;
-    if (C2 * P >= lim || C0 * P >= lim || C * 9 >= lim || (long long)M2 * P >= lim || (long long)M1 * C * 9 >= lim)
+    if (C2 * P >= lim || C0 * P >= lim || C * 9 >= lim || (long long)M2 * P >= lim || (long long)M1 * C * 9 >= lim ||
+        (stage && (long long)M1 * P >= lim))
         return fail(PVV_E_ARG, "head: a per-image tensor has 2^31 elements or more (int32 indexing)");
     if (fm_stride < (long long)C2 * h * w || (C0 > 0 && x_stride < C0 * P))
         return fail(PVV_E_ARG, "head: an image stride of fm / x is smaller than its planes");
@@ -330,6 +336,10 @@ int head_launch(const HeadShape &s, const float *fm, const float *x, const float
 int head_bf16_forward(const HeadShape &s, const float *fm, const float *x, const float *weight1, const float *scale, const float *shift,
                       const float *weight2, const float *bias2, void *out, hipStream_t st);
 
+// The stage mode of the same function (head_stage.hpp, included after this file): out = a, [B,M1,H,W].
+int head_stage_forward(const HeadShape &s, bool same_res, const float *fm, const float *x, const float *weight1, const float *scale,
+                       const float *shift, void *out, hipStream_t st);
+
 }  // namespace
 
 PVV_EXPORT int pvv_head_forward(const float *d_fm, long long fm_image_stride, const float *d_x, long long x_image_stride,
@@ -338,12 +348,18 @@ PVV_EXPORT int pvv_head_forward(const float *d_fm, long long fm_image_stride, co
                                 float negative_slope, int out_kind, void *d_out, void *stream)
 {
     HeadShape s;
-    const bool bf16 = (out_kind & ~0xFF) == PVV_HEAD_COMPUTE_BF16;    // any other bit above the dtype code stays and is refused with it
-    if (bf16) out_kind &= 0xFF;
-    if (int e = head_shape(s, B, C2, C0, h, w, H, W, M1, M2, fm_image_stride, x_image_stride, negative_slope, out_kind)) return e;
-    if (!d_fm || (C0 > 0 && !d_x) || !d_weight1 || !d_scale || !d_shift || !d_weight2 || !d_bias2 || !d_out)
+    const int flags = out_kind & ~0xFF;
+    const bool bf16 = flags == PVV_HEAD_COMPUTE_BF16;                 // any other bit above the dtype code stays and is refused with it
+    const bool stage = flags == PVV_HEAD_STAGE || flags == (PVV_HEAD_STAGE | PVV_HEAD_SAME_RES);
+    const bool same_res = stage && (flags & PVV_HEAD_SAME_RES);
+    if (bf16 || stage) out_kind &= 0xFF;
+    if (int e = head_shape(s, B, C2, C0, h, w, H, W, M1, stage ? 1 : M2, fm_image_stride, x_image_stride, negative_slope, out_kind,
+                           stage, same_res))
+        return e;
+    if (!d_fm || (C0 > 0 && !d_x) || !d_weight1 || !d_scale || !d_shift || (!stage && (!d_weight2 || !d_bias2)) || !d_out)
         return fail(PVV_E_ARG, "head: NULL device pointer");
     hipStream_t st = (hipStream_t)stream;
+    if (stage) return head_stage_forward(s, same_res, d_fm, d_x, d_weight1, d_scale, d_shift, d_out, st);
     if (bf16) return head_bf16_forward(s, d_fm, d_x, d_weight1, d_scale, d_shift, d_weight2, d_bias2, d_out, st);
     if (M1 > 32)
         return M2 > 32 ? head_launch<2, 2>(s, d_fm, d_x, d_weight1, d_scale, d_shift, d_weight2, d_bias2, d_out, st)

@@ -502,5 +502,8 @@ PVV_EXPORT int pvv_count_inliers(const float *d_direct, const float *d_coords, c
 // ---- PVNet output head: upsample, cat, conv3x3, BatchNorm, LeakyReLU, conv1x1 in one launch (ABI v8, additive) -----
 #include "head.hpp"
 
+// ---- the stage mode of the output head: PVNet's decoder stages, the channels in chunks (ABI v8, additive) -----
+#include "head_stage.hpp"
+
 // ---- the bfloat16 matrix-core modes of the output head (ABI v8, additive) -----
 #include "head_bf16.hpp"

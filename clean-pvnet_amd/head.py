@@ -9,6 +9,12 @@ with no full-resolution intermediate in memory; ``PVNetHead`` holds ``convraw`` 
 (``PVV_HEAD_COMPUTE_BF16`` in ``pvv_head_forward``'s ``out_kind``): operands rounded to bfloat16, float32 accumulation in an unpinned order, held to the bound of
 tests/head_bf16_twin.py.  Forward
 only, BatchNorm in eval mode: inference.  CUDA float32 tensors, the current stream, nothing read back, no CPU fallback.
+
+``pvnet_stage`` is the stage mode of the same entry point (``PVV_HEAD_STAGE``): one of the three decoder steps before the head
+(resnet18.py:31-51, 81-89) -- upsample or none, ``cat`` with the skip tensor, Conv3x3, BatchNorm, LeakyReLU -- in one launch for
+any number of input channels and up to 128 output channels.  ``PVNetDecoder`` holds ``conv8s``, ``conv4s``, ``conv2s`` and
+``convraw`` under the reference's names and takes the backbone's outputs to ``{'seg', 'vertex'}`` in four launches; its stages
+equal tests/decoder_twin.py bit for bit.
 """
 import torch
 from torch import nn
@@ -19,6 +25,8 @@ _lib = _native.bind("head", "libpvnet_vote.so", last_error="pvv_last_error")
 
 MAX_UPSAMPLE = 1 << 28             # elements ``upsample2x`` agrees to write
 MAX_M = 64                         # output channels of either convolution
+MAX_STAGE_M = 128                  # output channels of a decoder stage (PVV_HEAD_STAGE_MAX_M)
+STAGE, SAME_RES = 0x400, 0x800     # or-ed into out_kind: PVV_HEAD_STAGE, PVV_HEAD_SAME_RES
 OUT_KINDS = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 COMPUTE_MODES = {"float32": 0, "bfloat16": 0x100}                   # or-ed into out_kind; 0x100: PVV_HEAD_COMPUTE_BF16
 
@@ -119,6 +127,62 @@ def fold_bn(bn):
         return scale.float(), shift.float()
 
 
+def cached_fold(cache, slot, bn):
+    """``fold_bn(bn)`` kept in ``cache[slot]``: computed once and again whenever one of the BatchNorm's tensors changes
+    (``_version`` counts the in-place writes; a loaded or moved tensor is another object)."""
+    if bn.weight is None or bn.running_mean is None:
+        return fold_bn(bn)                                          # raises
+    tensors = (bn.weight, bn.bias, bn.running_mean, bn.running_var)
+    key = tuple((id(t), t._version, t.device) for t in tensors) + (bn.eps,)
+    if cache.get(slot) is None or cache[slot][0] != key:
+        cache[slot] = (key, fold_bn(bn))
+    return cache[slot][1]
+
+
+def pvnet_stage(a, skip, weight, scale, shift, *, upsample=True, negative_slope=0.1, out_dtype=torch.float32):
+    """One decoder stage, ``LeakyReLU(BatchNorm(Conv3x3(cat([up(a), skip], 1))))`` with the BatchNorm folded into ``scale`` and
+    ``shift`` (``fold_bn``), in one launch: ``pvv_head_forward`` with ``PVV_HEAD_STAGE``.
+    :param a:        [B,C2,h,w] float32 CUDA tensor: the coarser feature map (``upsample=True``: ``UpsamplingBilinear2d(2)``
+                     by the head's float32 formula), or one at the output's resolution (``upsample=False``: ``conv8s``)
+    :param skip:     [B,C0,H,W] with H, W = 2h, 2w (h, w without the upsample); C0 may be 0
+    :param weight:   [M, C2+C0, 3, 3], ``a``'s channels first; [M] ``scale`` and ``shift``; M <= 128, any C2 + C0
+    :return:         [B,M,H,W] of ``out_dtype``: float32, or float16 / bfloat16 rounded to nearest even at the store
+    ``a`` and ``skip`` may be views (channel slices of larger tensors): they are read by their image strides.  The contract
+    is the head's up to the activation (include/pvnet_vote.h, "PVNet decoder stage")."""
+    named = [("a", a), ("skip", skip), ("weight", weight), ("scale", scale), ("shift", shift)]
+    _check(named)
+    if out_dtype not in OUT_KINDS:
+        raise RuntimeError("clean_pvnet_amd.head: out_dtype must be float32, float16 or bfloat16, got %s" % (out_dtype,))
+    if a.dim() != 4 or a.shape[1] < 1:
+        raise RuntimeError("clean_pvnet_amd.head: a must be [B, C2 >= 1, h, w], got %s" % (tuple(a.shape),))
+    B, C2, h, w = (int(v) for v in a.shape)
+    H, W = (2 * h, 2 * w) if upsample else (h, w)
+    if skip.dim() != 4 or skip.shape[0] != B:
+        raise RuntimeError("clean_pvnet_amd.head: skip must be [B = %d, C0, %d, %d], got %s" % (B, H, W, tuple(skip.shape)))
+    if tuple(skip.shape[2:]) != (H, W):
+        raise RuntimeError("clean_pvnet_amd.head: skip must be %d x %d, %s a's %d x %d, got %d x %d -- a skip tensor of another "
+                           "size needs the reference's resample of fm (the fm.shape[2]==136 branch, resnet18.py:83-84), which "
+                           "is not supported" % (H, W, "twice" if upsample else "as", h, w, skip.shape[2], skip.shape[3]))
+    C0 = int(skip.shape[1])
+    f, f_stride = _native.per_image(a.detach(), "a", C2, h, w)
+    xi, x_stride = _native.per_image(skip.detach(), "skip", C0, H, W)
+    if weight.dim() != 4 or tuple(weight.shape[1:]) != (C2 + C0, 3, 3):
+        raise RuntimeError("clean_pvnet_amd.head: weight must be [M, C2 + C0 = %d, 3, 3], got %s" % (C2 + C0, tuple(weight.shape)))
+    M = int(weight.shape[0])
+    if tuple(scale.shape) != (M,) or tuple(shift.shape) != (M,):
+        raise RuntimeError("clean_pvnet_amd.head: scale and shift must be [%d], got %s, %s" % (M, tuple(scale.shape), tuple(shift.shape)))
+    if not 1 <= M <= MAX_STAGE_M:
+        raise ValueError("clean_pvnet_amd.head: a stage's M must lie in [1, %d], got %d" % (MAX_STAGE_M, M))
+    out = torch.empty(B, M, H, W, dtype=out_dtype, device=a.device)
+    if out.numel() == 0:
+        return out
+    w1, sc, sh = (t.detach().contiguous() for t in (weight, scale, shift))
+    _lib.call("pvv_head_forward", a.device, f.data_ptr(), f_stride, xi.data_ptr() if C0 else None, x_stride, w1.data_ptr(),
+              sc.data_ptr(), sh.data_ptr(), None, None, B, C2, C0, h, w, H, W, M, 1, float(negative_slope),
+              OUT_KINDS[out_dtype] | STAGE | (0 if upsample else SAME_RES), out.data_ptr())
+    return out
+
+
 class PVNetHead(nn.Module):
     """``up2storaw`` and ``convraw`` of the reference's ``Resnet18`` (resnet18.py:53-59) as one module: ``self.convraw`` has the
     reference's layers and names, ``forward(fm, x)`` is resnet18.py:90-96 up to the dict, through ``pvnet_head``.  ``compute`` is
@@ -134,7 +198,7 @@ class PVNetHead(nn.Module):
             nn.LeakyReLU(0.1, True),
             nn.Conv2d(raw_dim, seg_dim + ver_dim, 1, 1)
         )
-        self._folded = None
+        self._folded = {}
 
     @classmethod
     def from_state_dict(cls, sd, seg_dim=2, prefix="convraw.", image_dim=3, compute="float32"):
@@ -149,14 +213,7 @@ class PVNetHead(nn.Module):
     def folded(self):
         """``fold_bn`` of the BatchNorm, computed once and again whenever one of its tensors changes (``_version`` counts the
         in-place writes; a loaded or moved tensor is another object)."""
-        bn = self.convraw[1]
-        if bn.weight is None or bn.running_mean is None:
-            return fold_bn(bn)                                      # raises
-        tensors = (bn.weight, bn.bias, bn.running_mean, bn.running_var)
-        key = tuple((id(t), t._version, t.device) for t in tensors) + (bn.eps,)
-        if self._folded is None or self._folded[0] != key:
-            self._folded = (key, fold_bn(bn))
-        return self._folded[1]
+        return cached_fold(self._folded, "convraw", self.convraw[1])
 
     def forward(self, fm, x):
         if self.training:
@@ -167,5 +224,81 @@ class PVNetHead(nn.Module):
         _check(named)
         scale, shift = self.folded()
         out = pvnet_head(fm, x, conv1.weight, scale, shift, conv2.weight, conv2.bias, negative_slope=act.negative_slope,
+                         compute=self.compute)
+        return {"seg": out[:, :self.seg_dim], "vertex": out[:, self.seg_dim:]}
+
+
+class PVNetDecoder(nn.Module):
+    """The decoder of the reference's ``Resnet18`` (resnet18.py:31-59, 81-96): ``conv8s``, ``conv4s``, ``conv2s`` and
+    ``convraw`` with the reference's layers and names, so the matching entries of a ``Resnet18`` checkpoint load unchanged.
+    ``forward(x, x2s, x4s, x8s, xfc)`` takes the image and the backbone's outputs to ``{'seg', 'vertex'}`` in four launches:
+    three ``pvnet_stage`` calls and ``pvnet_head``.  ``compute`` is the head's mode only; the stages are float32.  The
+    reference's resample of a 136-row map to 135 x 180 (resnet18.py:83-84) is not supported: the skip tensors must have
+    twice the size of the map below them."""
+    STAGES = ("conv8s", "conv4s", "conv2s")
+
+    def __init__(self, ver_dim, seg_dim, fcdim=256, s8dim=128, s4dim=64, s2dim=32, raw_dim=32, compute="float32"):
+        super().__init__()
+        _compute(compute)
+        self.ver_dim, self.seg_dim, self.compute = ver_dim, seg_dim, compute
+
+        def stage(cin, cout):
+            return nn.Sequential(nn.Conv2d(cin, cout, 3, 1, 1, bias=False), nn.BatchNorm2d(cout), nn.LeakyReLU(0.1, True))
+        self.conv8s = stage(128 + fcdim, s8dim)
+        self.conv4s = stage(64 + s8dim, s4dim)
+        self.conv2s = stage(64 + s4dim, s2dim)
+        self.convraw = nn.Sequential(
+            nn.Conv2d(3 + s2dim, raw_dim, 3, 1, 1, bias=False),
+            nn.BatchNorm2d(raw_dim),
+            nn.LeakyReLU(0.1, True),
+            nn.Conv2d(raw_dim, seg_dim + ver_dim, 1, 1)
+        )
+        self._folded = {}
+
+    @classmethod
+    def from_state_dict(cls, sd, seg_dim=2, compute="float32"):
+        """A decoder sized from the ``conv8s.*``, ``conv4s.*``, ``conv2s.*`` and ``convraw.*`` tensors of a state dict (a
+        whole ``Resnet18`` checkpoint will do), loaded with them, in eval mode."""
+        w8, w4, w2, wr, wo = (sd[k] for k in ("conv8s.0.weight", "conv4s.0.weight", "conv2s.0.weight", "convraw.0.weight",
+                                              "convraw.3.weight"))
+        m = cls(int(wo.shape[0]) - seg_dim, seg_dim, fcdim=int(w8.shape[1]) - 128, s8dim=int(w8.shape[0]), s4dim=int(w4.shape[0]),
+                s2dim=int(w2.shape[0]), raw_dim=int(wr.shape[0]), compute=compute)
+        m.load_state_dict({k: v for k, v in sd.items() if k.split(".")[0] in cls.STAGES + ("convraw",)})
+        return m.eval()
+
+    @classmethod
+    def from_module(cls, net, compute="float32"):
+        """A decoder that shares ``net.conv8s``, ``net.conv4s``, ``net.conv2s`` and ``net.convraw`` -- the four ``Sequential``s
+        of a reference network -- without copying them: it follows the network's parameters and its train / eval mode."""
+        m = cls.__new__(cls)
+        nn.Module.__init__(m)
+        _compute(compute)
+        m.ver_dim, m.seg_dim, m.compute = net.ver_dim, net.seg_dim, compute
+        for name in cls.STAGES + ("convraw",):
+            setattr(m, name, getattr(net, name))
+        m._folded = {}
+        m.train(net.training)
+        return m
+
+    def folded(self, name):
+        """``fold_bn`` of ``<name>``'s BatchNorm, cached by ``PVNetHead.folded``'s rule."""
+        return cached_fold(self._folded, name, getattr(self, name)[1])
+
+    def forward(self, x, x2s, x4s, x8s, xfc):
+        if self.training or any(getattr(self, name).training for name in self.STAGES + ("convraw",)):
+            raise RuntimeError("clean_pvnet_amd.head: forward only -- the BatchNorms are folded from their running statistics; "
+                               "call .eval() first")
+        convs = [getattr(self, name)[0].weight for name in self.STAGES]
+        raw1, act, raw2 = self.convraw[0], self.convraw[2], self.convraw[3]
+        _check([("x", x), ("x2s", x2s), ("x4s", x4s), ("x8s", x8s), ("xfc", xfc)]
+               + [(name + ".weight", w) for name, w in zip(self.STAGES, convs)]
+               + [("convraw.weight1", raw1.weight), ("convraw.weight2", raw2.weight), ("convraw.bias2", raw2.bias)])
+        fm = xfc
+        for name, w, skip in zip(self.STAGES, convs, (x8s, x4s, x2s)):
+            scale, shift = self.folded(name)
+            fm = pvnet_stage(fm, skip, w, scale, shift, upsample=name != "conv8s",
+                             negative_slope=getattr(self, name)[2].negative_slope)
+        scale, shift = self.folded("convraw")
+        out = pvnet_head(fm, x, raw1.weight, scale, shift, raw2.weight, raw2.bias, negative_slope=act.negative_slope,
                          compute=self.compute)
         return {"seg": out[:, :self.seg_dim], "vertex": out[:, self.seg_dim:]}

@@ -550,7 +550,8 @@ int pvv_dcn_backward(const float *d_input, const float *d_weight, const float *d
 #define PVV_HEAD_MAX_M 64
 
 /* One fused launch; no workspace, nothing read back.  Per-image element counts must stay below 2^31, B <= 65535, and the
- * halo of C2+C0 channels must fit a CU's 160 KiB of LDS (about 90 channels). */
+ * halo of C2+C0 channels must fit a CU's 160 KiB of LDS (about 90 channels).  With PVV_HEAD_STAGE in `out_kind` ("PVNet
+ * decoder stage" below) the call stops after the activation, takes any number of channels and M1 up to 128. */
 int pvv_head_forward(const float *d_fm, long long fm_image_stride, const float *d_x, long long x_image_stride,
                      const float *d_weight1, const float *d_scale, const float *d_shift, const float *d_weight2,
                      const float *d_bias2, int B, int C2, int C0, int h, int w, int H, int W, int M1, int M2,
@@ -584,6 +585,34 @@ int pvv_head_upsample(const float *d_fm, long long fm_image_stride, int B, int C
  * "bfloat16x3" but is NOT offered: built on this kernel it measured slower than the float32 launch; the
  * flag 0x200 is kept free for it. */
 #define PVV_HEAD_COMPUTE_BF16 0x100
+
+/* PVNet decoder stage: the stage mode of the same function (ABI v8, additive): PVV_HEAD_STAGE or-ed into pvv_head_forward's
+ * `out_kind`, whose low byte stays the output dtype code.  No symbol is added and no signature changes; without the flag the
+ * call is what it was, every refusal included.  A stage is one of the three steps of Resnet18.forward before the head
+ * (lib/networks/pvnet/resnet18.py:31-51, 81-89), for inference, BatchNorm in eval mode, in one launch:
+ *   fm = conv8s(cat([xfc, x8s], 1))                  PVV_HEAD_STAGE | PVV_HEAD_SAME_RES: no upsample, 256+128 -> 128
+ *   fm = conv4s(cat([up8sto4s(fm), x4s], 1))         PVV_HEAD_STAGE: 128+64 -> 64
+ *   fm = conv2s(cat([up4sto2s(fm), x2s], 1))         PVV_HEAD_STAGE: 64+64 -> 32
+ * each Conv3x3(C2+C0 -> M1, padding 1, no bias), BatchNorm2d, LeakyReLU: the head without its Conv1x1.  The call stops after
+ * the activation: d_out = a, [B,M1,H,W] contiguous, float32 / float16 / bfloat16 by the low byte.  d_weight2, d_bias2 and M2
+ * are not read and may be NULL / anything.  The contract is the head's, word for word, up to a:
+ *   u = the float32 align_corners=True source index and blend above, one rounding per operation in the order written; under
+ *     PVV_HEAD_SAME_RES d_fm is already [C2,H,W] (h = H, w = W) and u = fm.
+ *   z = cat([u, x]) inside a ring of zeros, d_fm's channels first; d_x is the skip tensor at output resolution, image b at
+ *     d_x + b * x_image_stride, and may be NULL when C0 = 0.
+ *   acc = +0;  for k = c*9 + dy*3 + dx ascending over all C = C2 + C0 channels:  acc = fmaf(weight1[o, k], z.., acc)
+ *   t = fmaf(acc, scale[o], shift[o]);   a = t > 0 ? t : t * negative_slope;   a is stored.
+ * Zero terms (0 * 0) may be added anywhere to fill an instruction or a chunk; results compare as bit patterns with -0 as +0.
+ * tests/decoder_twin.py is this contract in numpy, bit for bit.
+ * Limits: 1 <= M1 <= PVV_HEAD_STAGE_MAX_M; any C2 >= 1 and C0 >= 0 -- no LDS limit on C2 + C0: the kernel takes the channels
+ * in chunks --; per-image element counts below 2^31, B <= 65535; H = 2h and W = 2w, or H = h and W = w under
+ * PVV_HEAD_SAME_RES.  Every refusal goes through pvv_last_error before any launch.  One launch on the caller's stream, no
+ * workspace, no atomics, nothing read back.
+ * PVV_HEAD_STAGE | PVV_HEAD_COMPUTE_BF16 and PVV_HEAD_SAME_RES without PVV_HEAD_STAGE are refused as unknown dtype codes: a
+ * bfloat16 stage is not offered. */
+#define PVV_HEAD_STAGE     0x400   /* stop after the activation: out = a, [B,M1,H,W]; d_weight2, d_bias2 and M2 are not read */
+#define PVV_HEAD_SAME_RES  0x800   /* only with PVV_HEAD_STAGE: d_fm is already [C2,H,W] (h = H, w = W), no upsample */
+#define PVV_HEAD_STAGE_MAX_M 128
 
 /* ------------------------------------------------------------------------
  * Optimizer step: the clipped Adam / RAdam / SGD step of every parameter tensor in one launch (ABI v8, additive).  Citations:
