@@ -1,6 +1,7 @@
 // head.hpp -- PVNet's full-resolution output head in one launch (include/pvnet_vote.h, "PVNet output head"): the bilinear 2x
 // upsample of the half-resolution feature map, the concatenation with the image, Conv3x3 + folded BatchNorm + LeakyReLU and the
-// Conv1x1 with its bias.  Included at the end of pvnet_vote.hip: built with -ffp-contract=off, so the upsample rounds once per
+// Conv1x1 with its bias.  Included at the end of pvnet_vote.hip, after head_tile.hpp -- the tile's
+// shared pieces -- and the two modes' files: built with -ffp-contract=off, so the upsample rounds once per
 // operation in the order written; the only fused multiply-adds are the ones the contract asks for, inside v_mfma_f32_32x32x2_f32
 // and the one fmaf of the BatchNorm.  The numpy twin (tests/head_twin.py) gives the same bits.
 // pvv_head_forward below also dispatches the two modes of its `out_kind`: the bfloat16 matrix-core mode (head_bf16.hpp) and the
@@ -11,87 +12,11 @@
 
 namespace {
 
-constexpr int kHeadG = 2;                                   // rows of 32 pixels per wave: independent accumulators on one weight operand
-constexpr int kHeadTh = 4 * kHeadG, kHeadTw = 32;           // output pixels of a workgroup: a 2-D tile, wave w its rows w*kHeadG ...
-constexpr int kHeadPix = kHeadTh * kHeadTw;
-constexpr int kHeadHh = kHeadTh + 2, kHeadHw = kHeadTw + 2; // the tile with its ring of one
-constexpr int kHeadHalo = kHeadHh * kHeadHw;                // floats of one channel's halo in LDS
-constexpr int kHeadKc = 36;                                 // k values per staged chunk of weight1: four channels, two pairs
-constexpr int kHeadKs = kHeadKc + 1;                        // floats of a staged row: odd, so 32 rows fall into 32 banks
-constexpr size_t kHeadMaxLds = 160 * 1024;                  // a CU's LDS; more than 64 KiB of it has to be asked for
-
-static_assert(kBlock == 4 * 64 && kHeadTw == 32 && kHeadKc == 4 * 9, "4 waves, each kHeadG rows of 32 pixels");
-
-struct HeadShape {
-    int B, C2, C0, h, w, H, W, M1, M2;
-    int C, Cpad, K, M1pad;            // C = C2 + C0 and rounded up to even, K = 9 * C, M1pad = M1 rounded up to even
-    long long fm_stride, x_stride;    // elements between two images of fm / x
-    float rh, rw, slope;
-    int out_kind;
-};
-
-// One axis of torch's align_corners=True source index (ATen/native/UpSample.h, the CUDA bilinear kernel), float32:
-// src = r * dst, i0 = (int)src, i1 = i0 + (i0 < n_in - 1), l1 = src - i0, l0 = 1 - l1.  src never exceeds n_in - 1 by a whole
-// step for n_in <= 2^23; the clamp keeps the address inside the plane whatever r is.
-struct HeadAxis { int i0, i1; float l0, l1; };
-
-__device__ __forceinline__ HeadAxis head_axis(float r, int dst, int n_in)
-{
-    HeadAxis a;
-    const float src = r * (float)dst;
-    a.i0 = min((int)src, n_in - 1);
-    a.i1 = a.i0 + (a.i0 < n_in - 1 ? 1 : 0);
-    a.l1 = src - (float)a.i0;
-    a.l0 = 1.f - a.l1;
-    return a;
-}
-
-// u = hl0*(wl0*v00 + wl1*v01) + hl1*(wl0*v10 + wl1*v11): a zero weight still multiplies its sample.
-__device__ __forceinline__ float head_blend(const float *__restrict__ plane, int w, const HeadAxis &ay, const HeadAxis &ax)
-{
-    const float v00 = plane[ay.i0 * w + ax.i0], v01 = plane[ay.i0 * w + ax.i1];
-    const float v10 = plane[ay.i1 * w + ax.i0], v11 = plane[ay.i1 * w + ax.i1];
-    return ay.l0 * (ax.l0 * v00 + ax.l1 * v01) + ay.l1 * (ax.l0 * v10 + ax.l1 * v11);
-}
-
-// One thread per element of u [B, C2, H, W].
-__global__ __launch_bounds__(kBlock) void k_head_upsample(HeadShape s, const float *__restrict__ fm, float *__restrict__ u)
-{
-    const long long idx = (long long)blockIdx.x * kBlock + threadIdx.x;
-    if (idx >= (long long)s.B * s.C2 * s.H * s.W) return;
-    const int x = (int)(idx % s.W), y = (int)(idx / s.W % s.H);
-    const int c = (int)(idx / s.W / s.H % s.C2), b = (int)(idx / s.W / s.H / s.C2);
-    u[idx] = head_blend(fm + (size_t)b * s.fm_stride + (size_t)c * s.h * s.w, s.w, head_axis(s.rh, y, s.h), head_axis(s.rw, x, s.w));
-}
-
-__device__ __forceinline__ unsigned short head_bf16(float v)     // round to nearest even; a NaN stays a quiet NaN
-{
-    const unsigned bits = __float_as_uint(v);
-    if (v != v) return (unsigned short)((bits >> 16) | 0x40u);
-    return (unsigned short)((bits + 0x7FFFu + ((bits >> 16) & 1u)) >> 16);
-}
-
-__device__ __forceinline__ void head_store(void *__restrict__ out, int kind, size_t at, float v)
-{
-    if (kind == PVV_HEAD_OUT_F32) ((float *)out)[at] = v;
-    else if (kind == PVV_HEAD_OUT_F16) ((_Float16 *)out)[at] = (_Float16)v;
-    else ((unsigned short *)out)[at] = head_bf16(v);
-}
-
-typedef float head_f16v __attribute__((ext_vector_type(16)));
-
-// Where k = 2j + hi of a pair of channels lies in the halo, past the pixel's window origin: channel k / 9, tap k % 9.
-__device__ __forceinline__ constexpr int head_k_offset(int k)
-{
-    return (k / 9) * kHeadHalo + ((k % 9) / 3) * kHeadHw + (k % 9) % 3;
-}
-
 // One workgroup per (kHeadTh x kHeadTw output pixels, image); N1 / N2 = 32-row blocks of M1 / M2.  A wave owns kHeadG rows of 32
 // pixels: kHeadG accumulators per row block, independent of each other, multiplied by one read of the weight operand.
-//  1. The tile's halo -- (kHeadTh + 2) x (kHeadTw + 2) positions of all C channels of the concatenated tensor: the upsampled fm
-//     channels, then the image's; zero outside the image (the convolution's padding ring, and whatever a partial tile overhangs)
-//     and in the channel that fills an odd C -- is written to LDS once: wave w takes the channels c = w, w + 4, ..., its lanes
-//     the positions, whose source indices and weights are computed once for all channels.  weight2 is staged transposed.
+//  1. The tile's halo (HeadHaloLane) of all C channels of the concatenated tensor -- the upsampled fm channels, then the image's,
+//     zeros in the channel that fills an odd C -- is written to LDS once: wave w takes the channels c = w, w + 4, ..., its lanes
+//     the positions.  weight2 is staged transposed.
 //  2. Conv1: weight1 goes through LDS in chunks of kHeadKc values of k -- four channels -- as rows of kHeadKs floats, in two
 //     buffers (the next chunk is loaded into registers before this one is multiplied and written after: one barrier per
 //     chunk; each thread's share of a chunk has the same offsets in every chunk, computed once).  Each wave feeds its pixels --
@@ -116,39 +41,27 @@ __global__ __launch_bounds__(kBlock) void k_head_forward(HeadShape s, const floa
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane & 31, hi = lane >> 5;
     const int x0 = blockIdx.x * kHeadTw, y0 = blockIdx.y * kHeadTh, b = blockIdx.z;
 
-    // ---- 1. the halo and weight2.  A lane's positions r = lane, lane + 64, lane + 128: their neighbours and weights once for
-    // every channel; a position outside the image loads element 0 and stores a zero, so no load waits on a branch.
-    constexpr int NP = (kHeadHalo + 63) / 64;
+    // ---- 1. the halo and weight2
     const float *fmb = fm + (size_t)b * s.fm_stride, *xb = x + (size_t)b * s.x_stride;
     const int plane = s.h * s.w, Plane = s.H * s.W;
-    int n00[NP], n01[NP], n10[NP], n11[NP], nx[NP];
-    float hl0[NP], hl1[NP], wl0[NP], wl1[NP];
-    bool inside[NP];
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-        const int r = lane + 64 * i, hy = r / kHeadHw, gy = y0 - 1 + hy, gx = x0 - 1 + (r - hy * kHeadHw);
-        inside[i] = r < kHeadHalo && gy >= 0 && gy < s.H && gx >= 0 && gx < s.W;
-        const HeadAxis ay = head_axis(s.rh, inside[i] ? gy : 0, s.h), ax = head_axis(s.rw, inside[i] ? gx : 0, s.w);
-        n00[i] = ay.i0 * s.w + ax.i0, n01[i] = ay.i0 * s.w + ax.i1, n10[i] = ay.i1 * s.w + ax.i0, n11[i] = ay.i1 * s.w + ax.i1;
-        hl0[i] = ay.l0, hl1[i] = ay.l1, wl0[i] = ax.l0, wl1[i] = ax.l1;
-        nx[i] = inside[i] ? gy * s.W + gx : 0;
-    }
+    HeadHaloLane<true> halo;
+    halo.init(s, x0, y0, lane);
 #pragma unroll 2
     for (int c = wave; c < s.C2; c += 4) {
         const float *pl = fmb + (size_t)c * plane;
 #pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            const float u = hl0[i] * (wl0[i] * pl[n00[i]] + wl1[i] * pl[n01[i]]) + hl1[i] * (wl0[i] * pl[n10[i]] + wl1[i] * pl[n11[i]]);
-            if (lane + 64 * i < kHeadHalo) s_halo[c * kHeadHalo + lane + 64 * i] = inside[i] ? u : 0.f;
+        for (int i = 0; i < halo.NP; ++i) {
+            const float u = halo.up(pl, i);
+            if (halo.in_halo(lane, i)) s_halo[c * kHeadHalo + lane + 64 * i] = halo.held(i, u);
         }
     }
     for (int c = s.C2 + wave; c < s.Cpad; c += 4) {                // the image's channels; zeros in the one that fills an odd C
         const bool real = c < s.C;
         const float *pl = xb + (size_t)(real ? c - s.C2 : 0) * Plane;
 #pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            const float v = real ? pl[nx[i]] : 0.f;
-            if (lane + 64 * i < kHeadHalo) s_halo[c * kHeadHalo + lane + 64 * i] = inside[i] ? v : 0.f;
+        for (int i = 0; i < halo.NP; ++i) {
+            const float v = real ? halo.at(pl, i) : 0.f;
+            if (halo.in_halo(lane, i)) s_halo[c * kHeadHalo + lane + 64 * i] = halo.held(i, v);
         }
     }
     for (int e = tid; e < s.M1pad * MT2; e += kBlock) {
@@ -180,13 +93,7 @@ __global__ __launch_bounds__(kBlock) void k_head_forward(HeadShape s, const floa
         for (int i = 0; i < NE; ++i)
             if (tid + i * kBlock < MT1 * kHeadKc) dst[w_lds[i]] = w_reg[i];
     };
-    head_f16v acc[kHeadG][N1];
-#pragma unroll
-    for (int g = 0; g < kHeadG; ++g)
-#pragma unroll
-        for (int n = 0; n < N1; ++n)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[g][n][r] = 0.f;
+    head_f16v acc[kHeadG][N1] = {};
 
     const int pix = wave * kHeadG * 32 + q;                        // this lane's pixel of its wave's first row; + 32 per row
     const float *window = s_halo + wave * kHeadG * kHeadHw + q;
@@ -199,23 +106,8 @@ __global__ __launch_bounds__(kBlock) void k_head_forward(HeadShape s, const floa
     for (int chunk = 0; chunk < chunks; ++chunk) {
         __syncthreads();                                           // this chunk (and the halo) is there; the last chunk's readers are done
         if (chunk + 1 < chunks) fetch(chunk + 1);                  // in flight while this chunk is multiplied
-        const int pairs = min(2, (s.Cpad - 4 * chunk) / 2);
-        const float *wb = s_wt + (chunk & 1) * MT1 * kHeadKs + q * kHeadKs + hi;
-        const float *hb = window + 4 * chunk * kHeadHalo;
-        for (int p = 0; p < pairs; ++p, wb += 18, hb += 2 * kHeadHalo) {
-#pragma unroll
-            for (int j = 0; j < 9; ++j) {
-                float av[N1];
-#pragma unroll
-                for (int a = 0; a < N1; ++a) av[a] = wb[2 * j + 32 * a * kHeadKs];
-#pragma unroll
-                for (int g = 0; g < kHeadG; ++g) {
-                    const float bv = hb[koff[j] + g * kHeadHw];
-#pragma unroll
-                    for (int a = 0; a < N1; ++a) acc[g][a] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[a], bv, acc[g][a], 0, 0, 0);
-                }
-            }
-        }
+        head_conv1_chunk<N1>(s_wt + (chunk & 1) * MT1 * kHeadKs + q * kHeadKs + hi, window + 4 * chunk * kHeadHalo,
+                             min(2, (s.Cpad - 4 * chunk) / 2), koff, acc);
         if (chunk + 1 < chunks) put(chunk + 1);                    // the other buffer: its readers passed this round's barrier
     }
 
@@ -225,18 +117,12 @@ __global__ __launch_bounds__(kBlock) void k_head_forward(HeadShape s, const floa
     for (int n = 0; n < N1; ++n)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int o = 32 * n + (r & 3) + 8 * (r >> 2) + 4 * hi;
+            const int o = head_row(n, r, hi);
             if (o < s.M1pad) {
                 const float sc = o < s.M1 ? scale[o] : 0.f, sh = o < s.M1 ? shift[o] : 0.f;
 #pragma unroll
-                for (int g = 0; g < kHeadG; ++g) {
-                    float a = 0.f;
-                    if (o < s.M1) {
-                        const float t = __builtin_fmaf(acc[g][n][r], sc, sh);
-                        a = t > 0.f ? t : t * s.slope;
-                    }
-                    s_act[o * kHeadPix + pix + 32 * g] = a;
-                }
+                for (int g = 0; g < kHeadG; ++g)
+                    s_act[o * kHeadPix + pix + 32 * g] = o < s.M1 ? head_act(acc[g][n][r], sc, sh, s.slope) : 0.f;
             }
         }
     __builtin_amdgcn_wave_barrier();                               // a wave reads only the columns it wrote: no workgroup barrier
@@ -247,7 +133,7 @@ __global__ __launch_bounds__(kBlock) void k_head_forward(HeadShape s, const floa
     for (int n = 0; n < N2; ++n)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int o = 32 * n + (r & 3) + 8 * (r >> 2) + 4 * hi;
+            const int o = head_row(n, r, hi);
             const float bs = o < s.M2 ? bias2[o] : 0.f;
 #pragma unroll
             for (int g = 0; g < kHeadG; ++g) acc2[g][n][r] = bs;
@@ -273,7 +159,7 @@ __global__ __launch_bounds__(kBlock) void k_head_forward(HeadShape s, const floa
             for (int n = 0; n < N2; ++n)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int o = 32 * n + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                    const int o = head_row(n, r, hi);
                     if (o < s.M2) head_store(out, s.out_kind, (((size_t)b * s.M2 + o) * s.H + gy) * s.W + gx, acc2[g][n][r]);
                 }
         }
@@ -321,24 +207,13 @@ int head_launch(const HeadShape &s, const float *fm, const float *x, const float
                 const float *weight2, const float *bias2, void *out, hipStream_t st)
 {
     const size_t lds = head_lds_bytes<N1, N2>(s);
-    if (lds > kHeadMaxLds) return fail(PVV_E_ARG, "head: C2 + C0 channels of the tile's halo do not fit 160 KiB of LDS");
-    if (lds > 64 * 1024 &&                                         // per launch: the limit belongs to the current device's copy of the kernel
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_head_forward<N1, N2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)kHeadMaxLds) != hipSuccess)
-        return fail(PVV_E_ARG, "head: the kernel's LDS limit could not be raised");
-    const dim3 grid((s.W + kHeadTw - 1) / kHeadTw, (s.H + kHeadTh - 1) / kHeadTh, s.B);
-    if (grid.y > 65535) return fail(PVV_E_ARG, "head: H is too large for one launch");
+    int tiles_x, tiles_y;
+    if (int e = head_raise_lds(reinterpret_cast<const void *>(&k_head_forward<N1, N2>), lds)) return e;
+    if (int e = head_tiles(s, tiles_x, tiles_y)) return e;
+    const dim3 grid(tiles_x, tiles_y, s.B);
     hipLaunchKernelGGL((k_head_forward<N1, N2>), grid, dim3(kBlock), lds, st, s, fm, x, weight1, scale, shift, weight2, bias2, out);
     return check_launch("k_head_forward");
 }
-
-// The bfloat16 matrix-core mode of the same function (head_bf16.hpp, included after this file).
-int head_bf16_forward(const HeadShape &s, const float *fm, const float *x, const float *weight1, const float *scale, const float *shift,
-                      const float *weight2, const float *bias2, void *out, hipStream_t st);
-
-// The stage mode of the same function (head_stage.hpp, included after this file): out = a, [B,M1,H,W].
-int head_stage_forward(const HeadShape &s, bool same_res, const float *fm, const float *x, const float *weight1, const float *scale,
-                       const float *shift, void *out, hipStream_t st);
 
 }  // namespace
 
@@ -361,11 +236,9 @@ PVV_EXPORT int pvv_head_forward(const float *d_fm, long long fm_image_stride, co
     hipStream_t st = (hipStream_t)stream;
     if (stage) return head_stage_forward(s, same_res, d_fm, d_x, d_weight1, d_scale, d_shift, d_out, st);
     if (bf16) return head_bf16_forward(s, d_fm, d_x, d_weight1, d_scale, d_shift, d_weight2, d_bias2, d_out, st);
-    if (M1 > 32)
-        return M2 > 32 ? head_launch<2, 2>(s, d_fm, d_x, d_weight1, d_scale, d_shift, d_weight2, d_bias2, d_out, st)
-                       : head_launch<2, 1>(s, d_fm, d_x, d_weight1, d_scale, d_shift, d_weight2, d_bias2, d_out, st);
-    return M2 > 32 ? head_launch<1, 2>(s, d_fm, d_x, d_weight1, d_scale, d_shift, d_weight2, d_bias2, d_out, st)
-                   : head_launch<1, 1>(s, d_fm, d_x, d_weight1, d_scale, d_shift, d_weight2, d_bias2, d_out, st);
+    return head_rows(M1, M2, [&](auto n1, auto n2) {
+        return head_launch<decltype(n1)::value, decltype(n2)::value>(s, d_fm, d_x, d_weight1, d_scale, d_shift, d_weight2, d_bias2, d_out, st);
+    });
 }
 
 PVV_EXPORT int pvv_head_upsample(const float *d_fm, long long fm_image_stride, int B, int C2, int h, int w, int H, int W, float *d_u,

@@ -1,8 +1,10 @@
 // head_bf16.hpp -- the bfloat16 matrix-core mode of PVNet's output head (include/pvnet_vote.h, "PVNet output head", compute
 // mode): the function of head.hpp with every matrix operand rounded once to bfloat16 (PVV_HEAD_COMPUTE_BF16 in pvv_head_forward's
-// out_kind) and multiplied by
-// v_mfma_f32_32x32x16_bf16 with float32 accumulation.  Included after head.hpp at the end of pvnet_vote.hip: -ffp-contract=off,
-// the upsample is head.hpp's expression.  The order of the sums is free (tests/head_bf16_twin.py holds the result to a bound).
+// out_kind) and multiplied by v_mfma_f32_32x32x16_bf16 with float32 accumulation.  On the head's tile (head_tile.hpp, included
+// in front of this file in pvnet_vote.hip): head_axis, head_blend, the row mapping, the activation and the store are the float32
+// kernel's.  A lane's halo positions are set up here, not through HeadHaloLane: with it the kernel, at the 256-register ceiling,
+// spilled two or three more SGPRs and measured 0.15 % slower at B = 32.  The order of the sums is free (tests/head_bf16_twin.py
+// holds the result to a bound).
 #pragma once
 
 namespace {
@@ -31,8 +33,8 @@ __device__ __forceinline__ head_f16v head_mfma_bf16(uint4 a, uint4 b, head_f16v 
 //   w1   [9][CS][2][32*N1]           slot ((tap*CS + cs)*2 + hh)*32*N1 + o: weight1[o, 16*cs + 8*hh + j, tap], j = 0..7
 //   w2   [N2][N1][2][2][32]          slot (((n2*N1 + n)*2 + st)*2 + hh)*32 + r: weight2[32*n2 + r, 32*n + 16*st + 8*(j>>2) + 4*hh + (j&3)]
 // then float scale [32*N1], shift [32*N1], bias2 [32*N2].
-//  1. Per tile the halo as head.hpp's step 1 computes it, eight channels of a position per 16-byte store: wave w the channel
-//     groups w, w + 4, ...
+//  1. Per tile the halo by HeadHaloLane's rule (head_tile.hpp), eight channels of a position per 16-byte store: wave w the
+//     channel groups w, w + 4, ...
 //  2. Conv1, k = (tap, channel): per tap and k-step one read of the weight fragment per row block and one of the halo per row.
 //  3. t = fmaf(acc, scale, shift), a = t > 0 ? t : t * slope in registers: conv1's accumulator has the pixel on the lane and the
 //     channels in its registers, so registers 8*st .. 8*st + 7 are the B fragment of conv2's k-step st (w2 is staged in that
@@ -88,7 +90,6 @@ __global__ __launch_bounds__(kBlock) void k_head_forward_bf16(HeadShape s, int T
         s_halo[at] = make_uint4(0, 0, 0, 0);
     }
 
-    constexpr int NP = (kHeadHalo + 63) / 64;
     const int plane = s.h * s.w, Plane = s.H * s.W;
     for (int it = 0; it < T; ++it) {
         const long long tile = (long long)blockIdx.x * T + it;
@@ -97,8 +98,8 @@ __global__ __launch_bounds__(kBlock) void k_head_forward_bf16(HeadShape s, int T
         const int x0 = tx * kHeadTw, y0 = ty * kHeadTh;
         const float *fmb = fm + (size_t)b * s.fm_stride, *xb = x + (size_t)b * s.x_stride;
 
-        // ---- 1. the halo.  A lane's positions r = lane + 64 i: neighbours and weights once for every channel; a position
-        // outside the image loads element 0 and stores a zero, so no load waits on a branch.
+        // ---- 1. the halo.  A lane's positions r = lane + 64 i, as HeadHaloLane<true>::init computes them
+        constexpr int NP = (kHeadHalo + 63) / 64;
         int n00[NP], n01[NP], n10[NP], n11[NP], nx[NP];
         float hl0[NP], hl1[NP], wl0[NP], wl1[NP];
         bool inside[NP];
@@ -122,7 +123,7 @@ __global__ __launch_bounds__(kBlock) void k_head_forward_bf16(HeadShape s, int T
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
                         const float *p = pl + (size_t)j * plane;
-                        const float u = hl0[i] * (wl0[i] * p[n00[i]] + wl1[i] * p[n01[i]]) + hl1[i] * (wl0[i] * p[n10[i]] + wl1[i] * p[n11[i]]);
+                        const float u = head_blend(hl0[i], hl1[i], wl0[i], wl1[i], p[n00[i]], p[n01[i]], p[n10[i]], p[n11[i]]);
                         v[j] = inside[i] ? u : 0.f;
                     }
                     if (lane + 64 * i < kHeadHalo) s_halo[(lane + 64 * i) * PS + g8] = head_pack8(v);
@@ -137,7 +138,7 @@ __global__ __launch_bounds__(kBlock) void k_head_forward_bf16(HeadShape s, int T
                         float u = 0.f;
                         if (c < s.C2) {
                             const float *p = fmb + (size_t)c * plane;
-                            u = hl0[i] * (wl0[i] * p[n00[i]] + wl1[i] * p[n01[i]]) + hl1[i] * (wl0[i] * p[n10[i]] + wl1[i] * p[n11[i]]);
+                            u = head_blend(hl0[i], hl1[i], wl0[i], wl1[i], p[n00[i]], p[n01[i]], p[n10[i]], p[n11[i]]);
                         } else if (c < s.C) {
                             u = xb[(size_t)(c - s.C2) * Plane + nx[i]];
                         }
@@ -150,13 +151,7 @@ __global__ __launch_bounds__(kBlock) void k_head_forward_bf16(HeadShape s, int T
         __syncthreads();                                           // the halo (and, the first time, step 0) is there
 
         // ---- 2. conv1
-        head_f16v acc[kHeadG][N1];
-#pragma unroll
-        for (int g = 0; g < kHeadG; ++g)
-#pragma unroll
-            for (int n = 0; n < N1; ++n)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[g][n][r] = 0.f;
+        head_f16v acc[kHeadG][N1] = {};
         const uint4 *hb = s_halo + (wave * kHeadG * kHeadHw + q) * PS + hi, *wb = s_w1 + hi * MT1 + q;
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
@@ -182,7 +177,7 @@ __global__ __launch_bounds__(kBlock) void k_head_forward_bf16(HeadShape s, int T
 #pragma unroll
             for (int n2 = 0; n2 < N2; ++n2)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc2[n2][r] = s_b2[32 * n2 + (r & 3) + 8 * (r >> 2) + 4 * hi];
+                for (int r = 0; r < 16; ++r) acc2[n2][r] = s_b2[head_row(n2, r, hi)];
 #pragma unroll
             for (int n = 0; n < N1; ++n)
 #pragma unroll
@@ -190,9 +185,8 @@ __global__ __launch_bounds__(kBlock) void k_head_forward_bf16(HeadShape s, int T
                     float a[8];
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
-                        const int r = 8 * st + j, o = 32 * n + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                        const float t = __builtin_fmaf(acc[g][n][r], s_sc[o], s_sh[o]);
-                        a[j] = o < s.M1 ? (t > 0.f ? t : t * s.slope) : 0.f;
+                        const int r = 8 * st + j, o = head_row(n, r, hi);
+                        a[j] = o < s.M1 ? head_act(acc[g][n][r], s_sc[o], s_sh[o], s.slope) : 0.f;
                     }
                     const uint4 bv = head_pack8(a);
 #pragma unroll
@@ -205,7 +199,7 @@ __global__ __launch_bounds__(kBlock) void k_head_forward_bf16(HeadShape s, int T
                 for (int n2 = 0; n2 < N2; ++n2)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int o = 32 * n2 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                        const int o = head_row(n2, r, hi);
                         if (o < s.M2) head_store(out, s.out_kind, (((size_t)b * s.M2 + o) * s.H + gy) * s.W + gx, acc2[n2][r]);
                     }
             }
@@ -225,13 +219,9 @@ int head_bf16_launch(const HeadShape &s, const float *fm, const float *x, const 
                      const float *weight2, const float *bias2, void *out, hipStream_t st)
 {
     const size_t lds = head_bf16_lds_bytes<N1, N2>(s);
-    if (lds > kHeadMaxLds) return fail(PVV_E_ARG, "head: C2 + C0 channels of the tile's halo do not fit 160 KiB of LDS");
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_head_forward_bf16<N1, N2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)kHeadMaxLds) != hipSuccess)
-        return fail(PVV_E_ARG, "head: the kernel's LDS limit could not be raised");
-    const int tiles_x = (s.W + kHeadTw - 1) / kHeadTw, tiles_y = (s.H + kHeadTh - 1) / kHeadTh;
-    if (tiles_y > 65535) return fail(PVV_E_ARG, "head: H is too large for one launch");
+    int tiles_x, tiles_y;
+    if (int e = head_raise_lds(reinterpret_cast<const void *>(&k_head_forward_bf16<N1, N2>), lds)) return e;
+    if (int e = head_tiles(s, tiles_x, tiles_y)) return e;
     const long long tiles = (long long)tiles_x * tiles_y * s.B;
     // Tiles per workgroup: one while the launch is small, up to eight once there are thousands (the weights are staged once per
     // workgroup), more only to keep the grid below 2^30 workgroups.
@@ -247,11 +237,9 @@ int head_bf16_launch(const HeadShape &s, const float *fm, const float *x, const 
 int head_bf16_forward(const HeadShape &s, const float *fm, const float *x, const float *weight1, const float *scale, const float *shift,
                       const float *weight2, const float *bias2, void *out, hipStream_t st)
 {
-    if (s.M1 > 32)
-        return s.M2 > 32 ? head_bf16_launch<2, 2>(s, fm, x, weight1, scale, shift, weight2, bias2, out, st)
-                         : head_bf16_launch<2, 1>(s, fm, x, weight1, scale, shift, weight2, bias2, out, st);
-    return s.M2 > 32 ? head_bf16_launch<1, 2>(s, fm, x, weight1, scale, shift, weight2, bias2, out, st)
-                     : head_bf16_launch<1, 1>(s, fm, x, weight1, scale, shift, weight2, bias2, out, st);
+    return head_rows(s.M1, s.M2, [&](auto n1, auto n2) {
+        return head_bf16_launch<decltype(n1)::value, decltype(n2)::value>(s, fm, x, weight1, scale, shift, weight2, bias2, out, st);
+    });
 }
 
 }  // namespace

@@ -500,10 +500,9 @@ PVV_EXPORT int pvv_count_inliers(const float *d_direct, const float *d_coords, c
 #include "optim.hpp"
 
 // ---- PVNet output head: upsample, cat, conv3x3, BatchNorm, LeakyReLU, conv1x1 in one launch (ABI v8, additive) -----
-#include "head.hpp"
-
-// ---- the stage mode of the output head: PVNet's decoder stages, the channels in chunks (ABI v8, additive) -----
+// head_tile.hpp: the 8 x 32 tile the three kernels share; then the two modes pvv_head_forward (head.hpp) branches into:
+// the stage mode -- PVNet's decoder stages, the channels in chunks -- and the bfloat16 matrix-core mode
+#include "head_tile.hpp"
 #include "head_stage.hpp"
-
-// ---- the bfloat16 matrix-core modes of the output head (ABI v8, additive) -----
 #include "head_bf16.hpp"
+#include "head.hpp"

@@ -10,7 +10,8 @@
 ``e_a``.  ``decoder`` composes three stages and ``head_twin.forward`` as lib/networks/pvnet/resnet18.py:81-92 of the reference does.
 
 ``split_rows`` is beyond the issue's cases: an upsampling stage with more than 64 output channels, which the kernel splits over
-two workgroups of two row blocks (four row blocks with the upsample's state spill).
+two workgroups of two row blocks (four row blocks with the upsample's state spill).  So are ``same_res_one_block`` and
+``same_res_two_blocks``: the kernel without the upsample at one and two row blocks, which no other case reaches.
 """
 import functools
 
@@ -89,8 +90,11 @@ CASES = {
     "stage_8s": dict(B=1, C2=256, C0=128, h=9, w=33, M=128, up=False),           # conv8s's channels, the largest M
     "stage_2s": dict(B=1, C2=64, C0=64, h=4, w=16, M=32, up=True),               # conv2s's channels, exactly one full tile
     "split_rows": dict(B=1, C2=5, C0=2, h=5, w=5, M=70, up=True),                # M > 64 with the upsample: two workgroups per tile
+    "same_res_one_block": dict(B=1, C2=3, C0=2, h=5, w=6, M=5, up=False),        # no upsample with one row block
+    "same_res_two_blocks": dict(B=1, C2=2, C0=3, h=5, w=6, M=40, up=False),      # no upsample with two row blocks
 }
-ISSUE_CASES = tuple(n for n in CASES if n != "split_rows")
+BEYOND_ISSUE = ("split_rows", "same_res_one_block", "same_res_two_blocks")
+ISSUE_CASES = tuple(n for n in CASES if n not in BEYOND_ISSUE)
 DECODER = dict(B=1, H=16, W=24, ver_dim=18, seg_dim=2, fcdim=256, s8dim=128, s4dim=64, s2dim=32, raw_dim=32)
 
 

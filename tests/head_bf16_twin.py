@@ -33,7 +33,7 @@ The operands are stated bit for bit; the order of the two float32 sums is not.  
 Non-finite values come out of the binary64 arithmetic as they do on the device: NaN in, NaN out; in ``bfloat16x3`` an Inf operand has
 lo = NaN, which is why only the set of non-finite outputs is pinned there.
 
-CASES: head_twin's six with their plants -- but the last output row's weights of 2e38 against a bias of -3e38, finite only in
+CASES: head_twin's with their plants -- but the last output row's weights of 2e38 against a bias of -3e38, finite only in
 one summation order, are ordinary draws again -- and ``c16`` / ``c17``: C = 16, exactly one K-step of 16 channels, and one channel
 more.  EXACT_CASES: inputs whose every partial sum has fewer than 24 bits, so that any order gives out64's bits.
 """
@@ -244,7 +244,7 @@ EXACT_SLOPE = 0.125
 
 
 def make_inputs(name):
-    """head_twin's tensors and plants for its six cases, the last output row drawn again; ``c16`` and ``c17`` by the same recipe."""
+    """head_twin's tensors and plants for its cases, the last output row drawn again; ``c16`` and ``c17`` by the same recipe."""
     if name in ht.CASES:
         d = ht.make_inputs(name)
         if d["M1"] >= 5:

@@ -214,6 +214,8 @@ CASES = {
     "two_blocks": dict(B=1, C2=4, C0=3, h=6, w=6, M1=33, M2=38),              # two 32-row blocks for M1 and M2; M1 odd
     "no_image": dict(B=2, C2=3, C0=0, h=6, w=7, M1=4, M2=2),                  # no image channels; K = 27
     "max_rows": dict(B=1, C2=2, C0=1, h=5, w=5, M1=64, M2=64),                # the largest M1 and M2: the kernel's LDS limit is raised
+    "rows_2_1": dict(B=1, C2=2, C0=1, h=5, w=5, M1=34, M2=3),                 # two row blocks for M1, one for M2
+    "rows_1_2": dict(B=1, C2=3, C0=2, h=5, w=5, M1=5, M2=33),                 # one row block for M1, two for M2
 }
 
 

@@ -2,6 +2,7 @@
 pybind module keeps the reference's surface, the drop-in import path and signatures match the reference, and the
 product fails loudly (no CPU fallback) -- no compute call is made here."""
 import ctypes
+import functools
 import inspect
 import os
 import subprocess
@@ -390,24 +391,38 @@ def _kernel_isa(asm, mangled_fragment):
     return body, asm[start:end if end > 0 else len(asm)]
 
 
-def test_count_kernel_isa_guard(tmp_path):
+@functools.lru_cache(maxsize=None)
+def _vote_isa():
+    """The gfx950 ISA listing of the voting translation unit, compiled once with the shipped flags for every guard below."""
+    import shutil
+    import tempfile
+    from importlib import util
+    spec = util.spec_from_file_location("_b", os.path.join(ROOT, "clean-pvnet_amd", "_build.py"))
+    b = util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    hipcc = shutil.which("hipcc") or os.path.join(b.ROCM, "bin", "hipcc")
+    flags = [f for f in b.HIPCC_FLAGS if f not in ("-fPIC", "-shared")]
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, "pvv.s")
+        subprocess.check_call([hipcc, *flags, "-I" + b.INCLUDE, "-I" + b.CSRC, "-S", "--cuda-device-only", "-o", out,
+                               os.path.join(b.CSRC, "pvnet_vote.hip")], stderr=subprocess.DEVNULL)
+        with open(out) as f:
+            return f.read()
+
+
+def _meta(meta, field):
+    import re
+    return int(re.search(r"\.%s:\s+(\d+)" % field, meta).group(1))
+
+
+def test_count_kernel_isa_guard():
     """VERDICT r2 #2d / weak #9.  k_count_bf16 sits at the 96-register cliff (5 waves per SIMD): compile the translation
     unit to gfx950 ISA with the shipped flags and assert, for ALL instantiations (full, staged-first, staged-filter) and for
     k_count_filter_runs, 8 matrix-core
     instructions, at most 96 VGPRs, and no scratch access between the first and the last of them (a spill inside the hot
     loop would not fail any parity test, only the clock); no spilled VGPR and no scratch at all outside round 3's filter kernel."""
     import re
-    import shutil
-    from importlib import util
-    spec = util.spec_from_file_location("_b", os.path.join(ROOT, "clean-pvnet_amd", "_build.py"))
-    b = util.module_from_spec(spec)
-    spec.loader.exec_module(b)
-    hipcc = shutil.which("hipcc") or os.path.join(b.ROCM, "bin", "hipcc")
-    out = tmp_path / "pvv.s"
-    flags = [f for f in b.HIPCC_FLAGS if f not in ("-fPIC", "-shared")]
-    subprocess.check_call([hipcc, *flags, "-I" + b.INCLUDE, "-I" + b.CSRC, "-S", "--cuda-device-only", "-o", str(out),
-                           os.path.join(b.CSRC, "pvnet_vote.hip")], stderr=subprocess.DEVNULL)
-    asm = out.read_text()
+    asm = _vote_isa()
     # full, staged-first, round 3's staged-filter, round 4's run-owning filter launch -- the staged ones for both chunk
     # schedules (first stage = a quarter of the chunks: mask 0x22 = 34; an eighth: 2)
     for frag in ("k_count_bf16ILi0ELj34E", "k_count_bf16ILi1ELj34E", "k_count_bf16ILi1ELj2E", "k_count_bf16ILi2ELj34E",
@@ -432,6 +447,25 @@ def test_count_kernel_isa_guard(tmp_path):
             assert spills <= 9 and scratch <= 40, (frag, spills, scratch)
         else:
             assert spills == 0 and scratch == 0, (frag, spills, scratch)
+
+
+def test_head_kernel_isa_guard():
+    """The 14 instantiations of the head's kernels (csrc/head_tile.hpp and the three files on it) read from their metadata: no
+    spilled VGPR and no scratch in any -- two of them sit at the 256-register ceiling, and k_head_stage<4, true> is not built
+    because it spilled --; k_head_forward's VGPRs within 168, three waves per SIMD; the stage kernels' static LDS within 64 KiB
+    and their VGPRs within 256: two workgroups per CU."""
+    asm = _vote_isa()
+    kernels = (["k_head_upsampleE"] + ["k_head_forwardILi%dELi%dE" % (a, b) for a in (1, 2) for b in (1, 2)] +
+               ["k_head_stageILi%dELb0E" % n for n in (1, 2, 4)] + ["k_head_stageILi%dELb1E" % n for n in (1, 2)] +
+               ["k_head_forward_bf16ILi%dELi%dE" % (a, b) for a in (1, 2) for b in (1, 2)])
+    assert len(kernels) == 14
+    for frag in kernels:
+        _, meta = _kernel_isa(asm, frag)
+        assert _meta(meta, "vgpr_spill_count") == 0 and _meta(meta, "private_segment_fixed_size") == 0, frag
+        if "k_head_forwardIL" in frag:                                   # three waves per SIMD: 512 / 3, in granules of 8
+            assert _meta(meta, "vgpr_count") <= 168, frag
+        if "k_head_stage" in frag:
+            assert 0 < _meta(meta, "group_segment_fixed_size") <= 65536 and _meta(meta, "vgpr_count") <= 256, frag
 
 
 def test_stage_hint_thresholds_and_no_data_without_a_gpu():
