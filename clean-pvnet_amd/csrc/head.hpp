@@ -4,8 +4,9 @@
 // shared pieces -- and the two modes' files: built with -ffp-contract=off, so the upsample rounds once per
 // operation in the order written; the only fused multiply-adds are the ones the contract asks for, inside v_mfma_f32_32x32x2_f32
 // and the one fmaf of the BatchNorm.  The numpy twin (tests/head_twin.py) gives the same bits.
-// pvv_head_forward below also dispatches the two modes of its `out_kind`: the bfloat16 matrix-core mode (head_bf16.hpp) and the
-// stage mode, PVNet's decoder stages (head_stage.hpp); both branch off after the checks all three share.
+// pvv_head_forward below also dispatches the modes of its `out_kind`: the bfloat16 matrix-core mode (head_bf16.hpp), the
+// stage mode, PVNet's decoder stages (head_stage.hpp), and the stage's own bfloat16 mode (head_stage_bf16.hpp); all branch off
+// after the checks they share.
 //
 // Reference behaviour restated: lib/networks/pvnet/resnet18.py:53-59, 90-94 of the reference.
 #pragma once
@@ -225,8 +226,9 @@ PVV_EXPORT int pvv_head_forward(const float *d_fm, long long fm_image_stride, co
     HeadShape s;
     const int flags = out_kind & ~0xFF;
     const bool bf16 = flags == PVV_HEAD_COMPUTE_BF16;                 // any other bit above the dtype code stays and is refused with it
-    const bool stage = flags == PVV_HEAD_STAGE || flags == (PVV_HEAD_STAGE | PVV_HEAD_SAME_RES);
-    const bool same_res = stage && (flags & PVV_HEAD_SAME_RES);
+    const int stage_flags = flags & ~PVV_HEAD_STAGE_BF16;             // PVV_HEAD_STAGE_BF16 counts only beside PVV_HEAD_STAGE
+    const bool stage = stage_flags == PVV_HEAD_STAGE || stage_flags == (PVV_HEAD_STAGE | PVV_HEAD_SAME_RES);
+    const bool same_res = stage && (flags & PVV_HEAD_SAME_RES), stage_bf16 = stage && (flags & PVV_HEAD_STAGE_BF16);
     if (bf16 || stage) out_kind &= 0xFF;
     if (int e = head_shape(s, B, C2, C0, h, w, H, W, M1, stage ? 1 : M2, fm_image_stride, x_image_stride, negative_slope, out_kind,
                            stage, same_res))
@@ -234,6 +236,7 @@ PVV_EXPORT int pvv_head_forward(const float *d_fm, long long fm_image_stride, co
     if (!d_fm || (C0 > 0 && !d_x) || !d_weight1 || !d_scale || !d_shift || (!stage && (!d_weight2 || !d_bias2)) || !d_out)
         return fail(PVV_E_ARG, "head: NULL device pointer");
     hipStream_t st = (hipStream_t)stream;
+    if (stage_bf16) return head_stage_bf16_forward(s, same_res, d_fm, d_x, d_weight1, d_scale, d_shift, d_out, st);
     if (stage) return head_stage_forward(s, same_res, d_fm, d_x, d_weight1, d_scale, d_shift, d_out, st);
     if (bf16) return head_bf16_forward(s, d_fm, d_x, d_weight1, d_scale, d_shift, d_weight2, d_bias2, d_out, st);
     return head_rows(M1, M2, [&](auto n1, auto n2) {

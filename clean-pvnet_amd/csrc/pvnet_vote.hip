@@ -501,8 +501,10 @@ PVV_EXPORT int pvv_count_inliers(const float *d_direct, const float *d_coords, c
 
 // ---- PVNet output head: upsample, cat, conv3x3, BatchNorm, LeakyReLU, conv1x1 in one launch (ABI v8, additive) -----
 // head_tile.hpp: the 8 x 32 tile the three kernels share; then the two modes pvv_head_forward (head.hpp) branches into:
-// the stage mode -- PVNet's decoder stages, the channels in chunks -- and the bfloat16 matrix-core mode
+// the stage mode -- PVNet's decoder stages, the channels in chunks --, the bfloat16 matrix-core mode, and the stage's
+// bfloat16 mode (after head_bf16.hpp: it takes head_pack8 and the operand layout from there)
 #include "head_tile.hpp"
 #include "head_stage.hpp"
 #include "head_bf16.hpp"
+#include "head_stage_bf16.hpp"
 #include "head.hpp"

@@ -14,7 +14,9 @@ only, BatchNorm in eval mode: inference.  CUDA float32 tensors, the current stre
 (resnet18.py:31-51, 81-89) -- upsample or none, ``cat`` with the skip tensor, Conv3x3, BatchNorm, LeakyReLU -- in one launch for
 any number of input channels and up to 128 output channels.  ``PVNetDecoder`` holds ``conv8s``, ``conv4s``, ``conv2s`` and
 ``convraw`` under the reference's names and takes the backbone's outputs to ``{'seg', 'vertex'}`` in four launches; its stages
-equal tests/decoder_twin.py bit for bit.
+equal tests/decoder_twin.py bit for bit.  ``compute="bfloat16"`` of ``pvnet_stage``
+(``stage_compute`` of the decoder) is the stages' own opt-in matrix-core mode, ``PVV_HEAD_STAGE_BF16``, held to the bound
+of tests/decoder_bf16_twin.py.
 """
 import torch
 from torch import nn
@@ -27,6 +29,7 @@ MAX_UPSAMPLE = 1 << 28             # elements ``upsample2x`` agrees to write
 MAX_M = 64                         # output channels of either convolution
 MAX_STAGE_M = 128                  # output channels of a decoder stage (PVV_HEAD_STAGE_MAX_M)
 STAGE, SAME_RES = 0x400, 0x800     # or-ed into out_kind: PVV_HEAD_STAGE, PVV_HEAD_SAME_RES
+STAGE_BF16 = 0x2000                # or-ed into out_kind beside STAGE: PVV_HEAD_STAGE_BF16, the stage's bfloat16 mode
 OUT_KINDS = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 COMPUTE_MODES = {"float32": 0, "bfloat16": 0x100}                   # or-ed into out_kind; 0x100: PVV_HEAD_COMPUTE_BF16
 
@@ -139,7 +142,8 @@ def cached_fold(cache, slot, bn):
     return cache[slot][1]
 
 
-def pvnet_stage(a, skip, weight, scale, shift, *, upsample=True, negative_slope=0.1, out_dtype=torch.float32):
+def pvnet_stage(a, skip, weight, scale, shift, *, upsample=True, negative_slope=0.1, out_dtype=torch.float32,
+                compute="float32"):
     """One decoder stage, ``LeakyReLU(BatchNorm(Conv3x3(cat([up(a), skip], 1))))`` with the BatchNorm folded into ``scale`` and
     ``shift`` (``fold_bn``), in one launch: ``pvv_head_forward`` with ``PVV_HEAD_STAGE``.
     :param a:        [B,C2,h,w] float32 CUDA tensor: the coarser feature map (``upsample=True``: ``UpsamplingBilinear2d(2)``
@@ -148,7 +152,12 @@ def pvnet_stage(a, skip, weight, scale, shift, *, upsample=True, negative_slope=
     :param weight:   [M, C2+C0, 3, 3], ``a``'s channels first; [M] ``scale`` and ``shift``; M <= 128, any C2 + C0
     :return:         [B,M,H,W] of ``out_dtype``: float32, or float16 / bfloat16 rounded to nearest even at the store
     ``a`` and ``skip`` may be views (channel slices of larger tensors): they are read by their image strides.  The contract
-    is the head's up to the activation (include/pvnet_vote.h, "PVNet decoder stage")."""
+    is the head's up to the activation (include/pvnet_vote.h, "PVNet decoder stage").
+    :param compute:  ``"float32"`` (that contract, that kernel), or ``"bfloat16"``, the matrix-core mode of
+                     ``PVV_HEAD_STAGE_BF16``: ``cat([up(a), skip])`` and ``weight`` are rounded once to bfloat16 inside the
+                     launch and the products are accumulated in float32 in an order that is not pinned:
+                     tests/decoder_bf16_twin.py bounds it.  ``a``, ``skip`` and ``weight`` stay float32 tensors."""
+    mode = STAGE_BF16 if _compute(compute) else 0
     named = [("a", a), ("skip", skip), ("weight", weight), ("scale", scale), ("shift", shift)]
     _check(named)
     if out_dtype not in OUT_KINDS:
@@ -179,7 +188,7 @@ def pvnet_stage(a, skip, weight, scale, shift, *, upsample=True, negative_slope=
     w1, sc, sh = (t.detach().contiguous() for t in (weight, scale, shift))
     _lib.call("pvv_head_forward", a.device, f.data_ptr(), f_stride, xi.data_ptr() if C0 else None, x_stride, w1.data_ptr(),
               sc.data_ptr(), sh.data_ptr(), None, None, B, C2, C0, h, w, H, W, M, 1, float(negative_slope),
-              OUT_KINDS[out_dtype] | STAGE | (0 if upsample else SAME_RES), out.data_ptr())
+              OUT_KINDS[out_dtype] | STAGE | (0 if upsample else SAME_RES) | mode, out.data_ptr())
     return out
 
 
@@ -232,15 +241,18 @@ class PVNetDecoder(nn.Module):
     """The decoder of the reference's ``Resnet18`` (resnet18.py:31-59, 81-96): ``conv8s``, ``conv4s``, ``conv2s`` and
     ``convraw`` with the reference's layers and names, so the matching entries of a ``Resnet18`` checkpoint load unchanged.
     ``forward(x, x2s, x4s, x8s, xfc)`` takes the image and the backbone's outputs to ``{'seg', 'vertex'}`` in four launches:
-    three ``pvnet_stage`` calls and ``pvnet_head``.  ``compute`` is the head's mode only; the stages are float32.  The
+    three ``pvnet_stage`` calls and ``pvnet_head``.  ``compute`` is the head's mode only; ``stage_compute`` is the three
+    stages' (``pvnet_stage``'s ``compute``: ``"float32"``, or ``"bfloat16"``, held to tests/decoder_bf16_twin.py's bound).
+    Both are attributes that may be set between calls; the parameters stay float32 in every mode.  The
     reference's resample of a 136-row map to 135 x 180 (resnet18.py:83-84) is not supported: the skip tensors must have
     twice the size of the map below them."""
     STAGES = ("conv8s", "conv4s", "conv2s")
 
-    def __init__(self, ver_dim, seg_dim, fcdim=256, s8dim=128, s4dim=64, s2dim=32, raw_dim=32, compute="float32"):
+    def __init__(self, ver_dim, seg_dim, fcdim=256, s8dim=128, s4dim=64, s2dim=32, raw_dim=32, compute="float32",
+                 stage_compute="float32"):
         super().__init__()
-        _compute(compute)
-        self.ver_dim, self.seg_dim, self.compute = ver_dim, seg_dim, compute
+        _compute(compute), _compute(stage_compute)
+        self.ver_dim, self.seg_dim, self.compute, self.stage_compute = ver_dim, seg_dim, compute, stage_compute
 
         def stage(cin, cout):
             return nn.Sequential(nn.Conv2d(cin, cout, 3, 1, 1, bias=False), nn.BatchNorm2d(cout), nn.LeakyReLU(0.1, True))
@@ -256,24 +268,24 @@ class PVNetDecoder(nn.Module):
         self._folded = {}
 
     @classmethod
-    def from_state_dict(cls, sd, seg_dim=2, compute="float32"):
+    def from_state_dict(cls, sd, seg_dim=2, compute="float32", stage_compute="float32"):
         """A decoder sized from the ``conv8s.*``, ``conv4s.*``, ``conv2s.*`` and ``convraw.*`` tensors of a state dict (a
         whole ``Resnet18`` checkpoint will do), loaded with them, in eval mode."""
         w8, w4, w2, wr, wo = (sd[k] for k in ("conv8s.0.weight", "conv4s.0.weight", "conv2s.0.weight", "convraw.0.weight",
                                               "convraw.3.weight"))
         m = cls(int(wo.shape[0]) - seg_dim, seg_dim, fcdim=int(w8.shape[1]) - 128, s8dim=int(w8.shape[0]), s4dim=int(w4.shape[0]),
-                s2dim=int(w2.shape[0]), raw_dim=int(wr.shape[0]), compute=compute)
+                s2dim=int(w2.shape[0]), raw_dim=int(wr.shape[0]), compute=compute, stage_compute=stage_compute)
         m.load_state_dict({k: v for k, v in sd.items() if k.split(".")[0] in cls.STAGES + ("convraw",)})
         return m.eval()
 
     @classmethod
-    def from_module(cls, net, compute="float32"):
+    def from_module(cls, net, compute="float32", stage_compute="float32"):
         """A decoder that shares ``net.conv8s``, ``net.conv4s``, ``net.conv2s`` and ``net.convraw`` -- the four ``Sequential``s
         of a reference network -- without copying them: it follows the network's parameters and its train / eval mode."""
         m = cls.__new__(cls)
         nn.Module.__init__(m)
-        _compute(compute)
-        m.ver_dim, m.seg_dim, m.compute = net.ver_dim, net.seg_dim, compute
+        _compute(compute), _compute(stage_compute)
+        m.ver_dim, m.seg_dim, m.compute, m.stage_compute = net.ver_dim, net.seg_dim, compute, stage_compute
         for name in cls.STAGES + ("convraw",):
             setattr(m, name, getattr(net, name))
         m._folded = {}
@@ -297,7 +309,7 @@ class PVNetDecoder(nn.Module):
         for name, w, skip in zip(self.STAGES, convs, (x8s, x4s, x2s)):
             scale, shift = self.folded(name)
             fm = pvnet_stage(fm, skip, w, scale, shift, upsample=name != "conv8s",
-                             negative_slope=getattr(self, name)[2].negative_slope)
+                             negative_slope=getattr(self, name)[2].negative_slope, compute=self.stage_compute)
         scale, shift = self.folded("convraw")
         out = pvnet_head(fm, x, raw1.weight, scale, shift, raw2.weight, raw2.bias, negative_slope=act.negative_slope,
                          compute=self.compute)

@@ -609,10 +609,33 @@ int pvv_head_upsample(const float *d_fm, long long fm_image_stride, int B, int C
  * PVV_HEAD_SAME_RES.  Every refusal goes through pvv_last_error before any launch.  One launch on the caller's stream, no
  * workspace, no atomics, nothing read back.
  * PVV_HEAD_STAGE | PVV_HEAD_COMPUTE_BF16 and PVV_HEAD_SAME_RES without PVV_HEAD_STAGE are refused as unknown dtype codes: a
- * bfloat16 stage is not offered. */
+ * bfloat16 stage is not offered under that spelling (PVV_HEAD_STAGE_BF16 below is the stage's compute mode). */
 #define PVV_HEAD_STAGE     0x400   /* stop after the activation: out = a, [B,M1,H,W]; d_weight2, d_bias2 and M2 are not read */
 #define PVV_HEAD_SAME_RES  0x800   /* only with PVV_HEAD_STAGE: d_fm is already [C2,H,W] (h = H, w = W), no upsample */
 #define PVV_HEAD_STAGE_MAX_M 128
+
+/* PVNet decoder stage, compute mode (ABI v8, additive, opt-in): PVV_HEAD_STAGE_BF16 or-ed into `out_kind` beside
+ * PVV_HEAD_STAGE, with or without PVV_HEAD_SAME_RES, the low byte still the output dtype code.  The flag is a bit of its own,
+ * not PVV_HEAD_STAGE | PVV_HEAD_COMPUTE_BF16: that combination has been a pinned refusal since the stage mode exists, and a
+ * caller that relies on the refusal must keep getting it; a new bit changes no answer any earlier call got.  It is valid only
+ * beside PVV_HEAD_STAGE: alone, with PVV_HEAD_COMPUTE_BF16, with PVV_HEAD_SAME_RES but no PVV_HEAD_STAGE, or with any other
+ * high bit it is refused with the unknown dtype codes.  No symbol is added and no signature changes.  Arguments, limits and
+ * refusals are the stage's: M1 <= PVV_HEAD_STAGE_MAX_M, any C2 + C0, d_weight2, d_bias2 and M2 not read.  One launch on the
+ * caller's stream, no workspace, no atomics (reruns give the same bytes), nothing read back; weight1 crosses the ABI as the
+ * caller's float32 and is rounded inside the launch.  The head's bfloat16 contract above, cut after the activation -- the
+ * operands are stated bit for bit:
+ *  1. u is the float32 upsample above, unchanged, or u = fm under PVV_HEAD_SAME_RES; z = cat([u, x]) inside its ring of zeros,
+ *     d_fm's channels first.
+ *  2. z and weight1 each enter as bf16(v): rounded once to nearest even to bfloat16, a NaN quieted.
+ *  3. acc is a float32 sum, from +0, of the exact products (v_mfma_f32_32x32x16_bf16).  The ORDER of the sum is not part of the
+ *     contract, nor are zero terms added for channel padding.
+ *  4. t = fmaf(acc, scale[o], shift[o]);  a = t > 0 ? t : t * negative_slope, float32.
+ *  5. Store: a as float32, or rounded to nearest even to float16 / bfloat16.
+ * A result is held to a bound, not to bits: tests/decoder_bf16_twin.py evaluates 1-5 in binary64 on the bit-exact operands (t
+ * and a rounded to float32) and gives bound_acc, the reach of any float32 summation order, and bound_mode, the distance from
+ * the float32 stage.  Where every partial sum is exact (the twin's exact-sum cases) the result is pinned bit for bit.  The NaN
+ * outputs and the +-Inf outputs are the twin's.  -0 compares as +0. */
+#define PVV_HEAD_STAGE_BF16 0x2000 /* only with PVV_HEAD_STAGE: z and weight1 rounded to bfloat16, the sum's order free */
 
 /* ------------------------------------------------------------------------
  * Optimizer step: the clipped Adam / RAdam / SGD step of every parameter tensor in one launch (ABI v8, additive).  Citations:

@@ -1,19 +1,29 @@
 #!/usr/bin/env python
 """``clean_pvnet_amd.head.pvnet_stage`` and ``PVNetDecoder`` at PVNet's own shapes -- a 480 x 640 image, the backbone's outputs at
 1/8 (256 + 128 channels), 1/4 (64) and 1/2 (64) -- timed by tools/head_time.py's method: device events after warm-up (ms per
-call, median and range over the timed rounds; each round is ``--reps`` calls back to back), the legs alternated in one process on
-the same inputs.  For each of ``conv8s``, ``conv4s``, ``conv2s`` and for the whole decoder (the three stages and the head):
+call, median, quartiles and range over the timed rounds; each round is ``--reps`` calls back to back), the legs alternated in
+one process on the same inputs.  For each of ``conv8s``, ``conv4s``, ``conv2s`` and for the whole decoder (the three stages and
+the head):
 
-  fused    the float32 launch(es) of this package: one per stage, four for the decoder
-  torch    the same function as the reference network runs it (lib/networks/pvnet/resnet18.py:31-59, 81-92): torch's own
-           ``UpsamplingBilinear2d``, ``cat``, ``Conv2d``, ``BatchNorm2d`` in eval mode and ``LeakyReLU`` with their defaults
+  fused     the float32 launch(es) of this package: one per stage, four for the decoder
+  bf16      the stage with ``compute="bfloat16"``; the decoder with ``stage_compute="bfloat16", compute="bfloat16"``
+  head_bf16 the decoder only: ``stage_compute="float32", compute="bfloat16"``, the fastest the float32 stages offer
+  torch     the same function as the reference network runs it (lib/networks/pvnet/resnet18.py:31-59, 81-92): torch's own
+            ``UpsamplingBilinear2d``, ``cat``, ``Conv2d``, ``BatchNorm2d`` in eval mode and ``LeakyReLU`` with their defaults
+  autocast  ``torch`` under ``torch.autocast("cuda", torch.bfloat16)``: information
 
-Before anything is timed the device's bytes are checked against the numpy twin (tests/decoder_twin.py) on three stage cases and
-on the whole decoder at 16 x 24; the run fails otherwise.  At the first batch size max |fused - torch| of the decoder's output
-is printed: information, not a check, because MIOpen's order of summation is not ours.  Two floors go with every stage:
+Before anything is timed the device's bytes are checked against the numpy twins: tests/decoder_twin.py bit for bit on three
+stage cases and on the whole decoder at 16 x 24, tests/decoder_bf16_twin.py's bound on five; the run fails otherwise.  At the
+first batch size max |fused - torch| of the decoder's output is printed: information, not a check, because MIOpen's order of
+summation is not ours.  Three floors go with every stage:
 
-  matrix   2 * 9 * C * M * H * W flop per image on ``v_mfma_f32_32x32x2_f32`` at the 155 TFLOP/s measured for that instruction
-  bytes    the two inputs and the output once at the 6.29 TB/s measured for a copy
+  matrix        2 * 9 * C * M * H * W flop per image on ``v_mfma_f32_32x32x2_f32`` at the 155 TFLOP/s measured for that instruction
+  matrix_bf16   the same flop on ``v_mfma_f32_32x32x16_bf16`` at 16 times that rate, 2.48 PFLOP/s: the instruction issues in 32
+                cycles per SIMD against the float32 one's 64 and carries eight times the k
+  bytes         the two inputs and the output once at the 6.29 TB/s measured for a copy
+
+The bfloat16 stages are kept if at B = 32 the ``bf16`` decoder is faster than the ``head_bf16`` decoder by more than the
+spread of the two: their inter-quartile ranges over the rounds do not overlap (``bf16_stages_kept`` in the decoder's record).
 
     python tools/decoder_time.py [--batches 1,32] [--rounds 20] [--warmup 3] [--reps 5] [--out profiles/decoder_time.json]
 """
@@ -35,9 +45,12 @@ from _timing import alternate, summary  # noqa: E402
 from clean_pvnet_amd import head  # noqa: E402
 
 MATRIX_F32 = 155e12                # measured rate of the f32-input MFMA
+MATRIX_BF16 = 16 * MATRIX_F32      # v_mfma_f32_32x32x16_bf16: 32 cycles per SIMD for 8 times the k of the float32 one's 64
 COPY_BYTES = 6.29e12               # measured HBM copy bandwidth
 STAGES = ("conv8s", "conv4s", "conv2s")
 FEATURES = ("x", "x2s", "x4s", "x8s", "xfc")
+STAGE_LEGS = ("fused", "bf16", "torch", "autocast")
+DECODER_LEGS = ("fused", "head_bf16", "bf16", "torch", "autocast")
 
 
 def stage_shapes(H, W):
@@ -78,10 +91,16 @@ def torch_decoder(m, up, f):
     return m.convraw(torch.cat([up(fm), f["x"]], 1))
 
 
-def fused_stage(m, name, a, skip):
+def autocast(f, *args):
+    with torch.autocast("cuda", torch.bfloat16):
+        return f(*args)
+
+
+def fused_stage(m, name, a, skip, compute="float32"):
     seq = getattr(m, name)
     scale, shift = m.folded(name)
-    return head.pvnet_stage(a, skip, seq[0].weight, scale, shift, upsample=name != "conv8s", negative_slope=seq[2].negative_slope)
+    return head.pvnet_stage(a, skip, seq[0].weight, scale, shift, upsample=name != "conv8s", negative_slope=seq[2].negative_slope,
+                            compute=compute)
 
 
 def fused_decoder(m, f):
@@ -90,8 +109,10 @@ def fused_decoder(m, f):
 
 
 def check_against_the_twin(dev):
-    """The device's bytes against the numpy twin: several halo chunks with a partial last one, one full tile of conv2s's
-    channels, four row blocks without the upsample, and the whole decoder."""
+    """The device's bytes against the numpy twins: several halo chunks with a partial last one, one full tile of conv2s's
+    channels, four row blocks without the upsample, and the whole decoder; the bfloat16 stage within its bound on those
+    three, on a straddling group of channels and on the workgroups of four row blocks."""
+    from tests import decoder_bf16_twin as bf16_twin
     from tests import decoder_twin as twin
     for name in ("odd_chunks", "stage_2s", "no_skip_same_res"):
         d = twin.reference(name)
@@ -103,6 +124,20 @@ def check_against_the_twin(dev):
     out = m(*(torch.tensor(np.asarray(d[k]), device=dev) for k in FEATURES))
     assert twin.same_bits(torch.cat([out["seg"], out["vertex"]], 1).cpu().numpy(), d["out"]), "the decoder differs from its twin"
     print("device == twin, bit for bit (-0 as +0), on odd_chunks, stage_2s, no_skip_same_res and decoder_16x24", flush=True)
+    shares = {}
+    for name in ("odd_chunks", "stage_2s", "no_skip_same_res", "straddle", "wide_c16_up"):
+        d = bf16_twin.reference(name)
+        t = [torch.tensor(np.asarray(d[k]), device=dev) for k in bf16_twin.KEYS]
+        got = head.pvnet_stage(*t, upsample=d["up"], negative_slope=d["slope"], compute="bfloat16").cpu().numpy()
+        assert bf16_twin.within(got, d), "the bfloat16 stage leaves the twin's bound on %s" % name
+        shares[name] = round(bf16_twin.worst(got, d), 3)
+    print("bfloat16 stage within bound_acc; worst share per case: %s" % shares, flush=True)
+
+
+def spread(ms, digits=4):
+    """``summary`` with the quartiles: the acceptance compares inter-quartile ranges."""
+    q1, q3 = np.percentile(np.asarray(ms), [25, 75])
+    return dict(summary(ms, digits), q1=round(float(q1), digits), q3=round(float(q3), digits))
 
 
 def main():
@@ -120,8 +155,9 @@ def main():
     for B in batches:
         for name, shape in stage_shapes(H, W).items():
             flop, nbytes, t_mat, t_mem = floors(B, *shape)
-            print("B = %d, %s: %.2f GFLOP -> %.4f ms at the matrix rate; %.1f MB -> %.4f ms at the copy rate"
-                  % (B, name, flop / 1e9, t_mat, nbytes / 1e6, t_mem), flush=True)
+            print("B = %d, %s: %.2f GFLOP -> %.4f ms at the float32 matrix rate, %.4f ms at the bfloat16 one (%.2f PFLOP/s); "
+                  "%.1f MB -> %.4f ms at the copy rate"
+                  % (B, name, flop / 1e9, t_mat, flop / MATRIX_BF16 * 1e3, MATRIX_BF16 / 1e15, nbytes / 1e6, t_mem), flush=True)
     if not torch.cuda.is_available():
         raise SystemExit("decoder_time: no GPU: nothing is measured")
     dev = torch.device("cuda", 0)
@@ -131,6 +167,8 @@ def main():
         check_against_the_twin(dev)
         for B in batches:
             m, f = make(B, H, W, dev)
+            decoders = {"fused": m, "head_bf16": head.PVNetDecoder.from_module(m, compute="bfloat16"),
+                        "bf16": head.PVNetDecoder.from_module(m, compute="bfloat16", stage_compute="bfloat16")}
             ins = {"conv8s": (f["xfc"], f["x8s"])}                                  # every stage on its predecessor's fused output
             ins["conv4s"] = (fused_stage(m, "conv8s", *ins["conv8s"]), f["x4s"])
             ins["conv2s"] = (fused_stage(m, "conv4s", *ins["conv4s"]), f["x2s"])
@@ -140,32 +178,50 @@ def main():
                 return lambda: [f(*args) for _ in range(a.reps)]
             for name in STAGES:
                 forms["fused_" + name] = leg(fused_stage, m, name, *ins[name])
+                forms["bf16_" + name] = leg(fused_stage, m, name, *ins[name], "bfloat16")
                 forms["torch_" + name] = leg(torch_stage, m, up, name, *ins[name])
-            forms["fused_decoder"] = lambda: [fused_decoder(m, f) for _ in range(a.reps)]
-            forms["torch_decoder"] = lambda: [torch_decoder(m, up, f) for _ in range(a.reps)]
+                forms["autocast_" + name] = leg(autocast, torch_stage, m, up, name, *ins[name])
+            for which, dec in decoders.items():
+                forms[which + "_decoder"] = leg(fused_decoder, dec, f)
+            forms["torch_decoder"] = leg(torch_decoder, m, up, f)
+            forms["autocast_decoder"] = leg(autocast, torch_decoder, m, up, f)
             diff = float((fused_decoder(m, f) - torch_decoder(m, up, f)).abs().max())
-            print("B = %d: max |fused decoder - torch decoder| = %.3g (informational)" % (B, diff), flush=True)
+            diff_bf16 = float((fused_decoder(decoders["bf16"], f) - torch_decoder(m, up, f)).abs().max())
+            print("B = %d: max |fused decoder - torch decoder| = %.3g, with bfloat16 stages and head %.3g (informational)"
+                  % (B, diff, diff_bf16), flush=True)
             ms = alternate(forms, a.rounds, a.warmup)
             for name in STAGES + ("decoder",):
                 res = {"B": B, "H": H, "W": W, "what": name, "rounds": a.rounds, "warmup": a.warmup, "reps": a.reps}
-                for leg in ("fused", "torch"):
-                    res[leg + "_ms"] = summary([v / a.reps for v in ms[leg + "_" + name]], 4)
-                med = res["fused_ms"]["median"]
+                for leg_name in (STAGE_LEGS if name in STAGES else DECODER_LEGS):
+                    res[leg_name + "_ms"] = spread([v / a.reps for v in ms[leg_name + "_" + name]])
+                med, med_bf16 = res["fused_ms"]["median"], res["bf16_ms"]["median"]
                 res["torch_over_fused"] = round(res["torch_ms"]["median"] / med, 2)
+                res["fused_over_bf16"] = round(med / med_bf16, 2)
                 res["fused_round_spread"] = round(res["fused_ms"]["max"] / res["fused_ms"]["min"], 3)
                 if name in STAGES:
                     C2, C0, M, Ho, Wo, ups = stage_shapes(H, W)[name]
                     flop, nbytes, t_mat, t_mem = floors(B, C2, C0, M, Ho, Wo, ups)
+                    t_bf16 = flop / MATRIX_BF16 * 1e3
                     res.update({"C2": C2, "C0": C0, "M": M, "out_h": Ho, "out_w": Wo, "upsample": ups, "flop": flop, "bytes": nbytes,
-                                "floor_matrix_ms": round(t_mat, 4), "floor_bytes_ms": round(t_mem, 4),
+                                "floor_matrix_ms": round(t_mat, 4), "floor_matrix_bf16_ms": round(t_bf16, 4),
+                                "matrix_bf16_flops": MATRIX_BF16, "floor_bytes_ms": round(t_mem, 4),
                                 "fused_tflops": round(flop / (med * 1e-3) / 1e12, 2), "fused_over_floor_matrix": round(med / t_mat, 2),
-                                "fused_over_floor_bytes": round(med / t_mem, 2)})
+                                "fused_over_floor_bytes": round(med / t_mem, 2),
+                                "bf16_tflops": round(flop / (med_bf16 * 1e-3) / 1e12, 2),
+                                "bf16_over_floor_matrix_bf16": round(med_bf16 / t_bf16, 2),
+                                "bf16_over_floor_bytes": round(med_bf16 / t_mem, 2)})
                 else:
+                    flop = sum(floors(B, *s)[0] for s in stage_shapes(H, W).values())
                     res["launches"] = 4
                     res["fused_vs_torch_max_abs"] = diff
+                    res["bf16_vs_torch_max_abs"] = diff_bf16
+                    res["stages_floor_matrix_ms"] = round(flop / MATRIX_F32 * 1e3, 4)
+                    res["stages_floor_matrix_bf16_ms"] = round(flop / MATRIX_BF16 * 1e3, 4)
+                    res["head_bf16_over_bf16"] = round(res["head_bf16_ms"]["median"] / med_bf16, 2)
+                    res["bf16_stages_kept"] = bool(res["bf16_ms"]["q3"] < res["head_bf16_ms"]["q1"])   # faster, by more than the spread
                 print(json.dumps(res), flush=True)
                 lines.append(res)
-            del m, f, ins
+            del m, f, ins, decoders, forms
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as fh:
